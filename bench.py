@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- LPs solved/sec on BASELINE.json's headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -18,10 +18,13 @@ into oracle/_ref) timed on one host core on a bounded sample of the same workloa
 With one GPU and the default workload the line also carries `secondary`: the other single-GPU configurations of this
 path (configs[1] 4 096 x (16, 32); configs[4]'s per-GPU share on the reference's algorithm and on the homogeneous
 self-dual variant; per-problem values of A on that structure; a dense LP beyond the lane-group kernels, m = 100) --
-each measured the same way (resident inputs, HIP events around the launches, barrier-free wall clock with a device
-synchronise either side), each with its own roofline figures, its parity against the committed golden vectors of the
-reference solver and the reference solver's own time on a bounded sample of THAT workload.  They are records, not the
-headline: `value` is always the configs[2] figure.
+each measured the same way (the same --steps and --warmup, resident inputs, HIP events around the launches,
+barrier-free wall clock with a device synchronise either side), each with its own roofline figures, its parity against
+the committed golden vectors of the reference solver and the reference solver's own time on a bounded sample of THAT
+workload.  They are records, not the headline: `value` is always the configs[2] figure.
+
+--dump-outputs DIR writes what the headline's last timed step computed as DIR/<name>.npy (dump_outputs); the inputs are
+generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -53,6 +56,29 @@ def flops_per_lp_sparse(m, N, iters, n_terms, nnz_e):
 def bytes_per_lp(m, N):
     """Compulsory HBM traffic of the fused solve: b, c in; x, y, z out; objectives, status, iters."""
     return 8 * (m + N) + 8 * (N + m) + 8 * N + 16 + 8
+
+
+DUMP_FIELDS = ("pobj", "dobj", "status", "iters", "x", "y", "z")
+DUMP_SCALAR_LPS = 1 << 19        # pobj, dobj, status, iters of at most this many LPs: 16 MB
+DUMP_VECTOR_BYTES = 32 << 20     # x, y, z of a sample of LPs: at most 32 MB
+DUMP_SEED = 0
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: the result arrays of the last timed step, one float64 file <path>/<name>.npy each (48 MB at most),
+    so that two builds run with the same arguments can be compared output for output.  The per-LP scalars cover the whole
+    batch (up to DUMP_SCALAR_LPS LPs) and the vectors x, y, z a sample of LPs; a sample is drawn with the fixed DUMP_SEED
+    from the batch size alone and kept in batch order, so both builds dump the same LPs."""
+    os.makedirs(path, exist_ok=True)
+    res = {k: np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in res.items()}
+    B = res["pobj"].shape[0]
+    vec_bytes = 8 * sum(v.shape[1] for v in res.values() if v.ndim == 2)
+
+    def rows(k):
+        return np.arange(B) if k >= B else np.sort(np.random.RandomState(DUMP_SEED).choice(B, k, replace=False))
+    scalar_rows, vector_rows = rows(DUMP_SCALAR_LPS), rows(DUMP_VECTOR_BYTES // vec_bytes)
+    for name, v in res.items():
+        np.save(os.path.join(path, name + ".npy"), v[vector_rows if v.ndim == 2 else scalar_rows].astype(np.float64))
 
 
 def usable_cores():
@@ -382,10 +408,16 @@ def main():
     ap.add_argument("--force-collectives", action="store_true",
                     help="development aid: take the multi-rank code path (process group, result gather, barriers) even "
                          "with one rank -- exercises the RCCL calls on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed (rank 0's results after the gather with "
+                         "N > 1) as DIR/<name>.npy in float64: pobj, dobj, status, iters of every LP, x, y (, z) of a "
+                         "seeded sample of LPs")
     ap.add_argument("--rehearse", action="store_true",
                     help="development aid: run the N-rank path on ONE GPU (all ranks share cuda:0, gloo backend, "
                          "results gathered through host memory); the numbers it prints are not benchmark results")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # stdout carries exactly ONE line, the JSON result of rank 0.  Libraries write there too (RCCL prints a five-line
     # version banner to stdout when its communicator comes up), so file descriptor 1 is pointed at stderr for the whole
     # run and the result goes to the saved descriptor at the end.
@@ -483,6 +515,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     gathered = pg.results(args.steps - 1, names=fields) if multi else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered if multi else {k: buf[k] for k in DUMP_FIELDS})
 
     kern_ms = float(np.mean([a.elapsed_time(b_) for a, b_ in ev]))
     info = wl.launch_info()      # of the timed launches (the parity solve below launches again, with another batch)
@@ -531,7 +565,7 @@ def main():
                 try:
                     # same LPs, same reference solver: timed once (the headline's own CPU leg serves dense3_predcorr)
                     reuse = cpu5 if (name == "sparse5" and (hsd or pc)) else (cpu if name == "dense3" else None)
-                    r = measure_secondary(name, Bs, dev, steps=5, warmup=2, hsd=hsd, predcorr=pc, r=rr,
+                    r = measure_secondary(name, Bs, dev, steps=args.steps, warmup=args.warmup, hsd=hsd, predcorr=pc, r=rr,
                                           cpu_seconds=None if args.no_cpu_baseline else 4.0, cpu_from=reuse)
                     if name == "sparse5" and not hsd and not pc:
                         cpu5 = r["cpu_baseline"]

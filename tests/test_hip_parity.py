@@ -896,7 +896,7 @@ def _sparse_case(m, n, B, density, seed):
 @pytest.mark.parametrize("m,n,B,density", [(128, 256, 96, 0.025), (128, 256, 16, 0.1), (40, 90, 64, 0.1), (12, 20, 33, 0.3),
                                            (100, 80, 8, 1.0)])
 def test_sparse_solver_matches_oracle_and_reference_solver(m, n, B, density):
-    from oracle import port, hsd_ref
+    from oracle import port
     A, b, c, lp, s, st = _sparse_case(m, n, B, density, seed=m + n)
     r = port.dense_solve(lp.A.todense(), lp.b, lp.c, nthreads=8)
     np.testing.assert_array_equal(st, r["status"])
@@ -904,11 +904,14 @@ def test_sparse_solver_matches_oracle_and_reference_solver(m, n, B, density):
     assert np.abs(s.iters.astype(int) - r["iters"]).max() <= 1
     assert rel_err(s.primal_obj, r["pobj"]).max() < 1e-9 and rel_err(s.dual_obj, r["dobj"]).max() < 1e-9
     np.testing.assert_allclose(s.x, r["x"], rtol=1e-5, atol=1e-6)
-    if hsd_ref.available():   # the reference's own CPU solver on the same StandardLPs (first few: it is slow at this size)
-        k = min(B, 8)
-        g = hsd_ref.solve_standard(np.asarray(A.todense()), b[:k], c[:k])
-        assert (g["status"] == 0).all()
-        assert rel_err(s.primal_obj[:k], g["pobj"]).max() < OBJ_TOL and rel_err(s.dual_obj[:k], g["dobj"]).max() < OBJ_TOL
+    # the reference's own CPU solver on the same StandardLPs (first few: it is slow at this size), stored by
+    # tools/gen_golden.py sparse_solver_cases
+    g = golden("sparse_solver_cases.npz")
+    key = "%dx%d_B%d_d%g_" % (m, n, B, density)
+    np.testing.assert_allclose(g[key + "input_checksum"], [A.sum(), b.sum(), c.sum()], rtol=1e-12)
+    k = len(g[key + "pobj"])
+    assert k == min(B, 8) and (g[key + "status"] == 0).all()
+    assert rel_err(s.primal_obj[:k], g[key + "pobj"]).max() < OBJ_TOL and rel_err(s.dual_obj[:k], g[key + "dobj"]).max() < OBJ_TOL
 
 
 def test_sparse_solver_guarded_path_agrees():

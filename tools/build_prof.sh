@@ -2,7 +2,7 @@
 # diagnostic build with in-kernel phase stamps: proflib/libpycllp_hip_prof.so (use with PYCLLP_HIP_LIB=...)
 # (the per-problem-A and predictor-corrector wave kernels are linked unstamped from the product build)
 set -e
-cd /root/repo
+cd "$(dirname "$0")/.."
 mkdir -p proflib
 F="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -DPYCLLP_PROFILE"
 C=pycllp_amd/csrc

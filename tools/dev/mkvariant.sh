@@ -3,7 +3,7 @@
 # builds ONLY the (32, 96) group kernels of ipm_dense.hip (PYCLLP_DEV_ONLY_3296) with the given macros and links them with the
 # product's other objects into proflib/NAME.so (use with PYCLLP_HIP_LIB=$GRAFT_REPO_ROOT/proflib/NAME.so)
 set -e
-cd /root/repo
+cd "$(dirname "$0")/../.."
 name=$1; shift
 mkdir -p proflib
 C=pycllp_amd/csrc

@@ -2,7 +2,7 @@
 # development variant of the library with ONLY the (8, 6) table variant of the wave kernel rebuilt (BASELINE config 5):
 #   tools/dev/mkvariant_w.sh NAME [-Dmacro ...]  ->  proflib/NAME.so   (the other objects come from the product build)
 set -e
-cd /root/repo
+cd "$(dirname "$0")/../.."
 name=$1; shift
 mkdir -p proflib
 C=pycllp_amd/csrc

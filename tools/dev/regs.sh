@@ -1,7 +1,7 @@
 #!/bin/bash
 # register / spill figures of the (32, 96) group kernels for a set of macros, without building a library:
 #   tools/dev/regs.sh [-Dmacro ...]     (device-only assembly goes to /tmp/regs.s)
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -DPYCLLP_DEV_ONLY_3296 "$@" --cuda-device-only -S -o /tmp/regs.s /root/repo/pycllp_amd/csrc/ipm_dense.hip 2>&1 | grep -v "hip-link" 
+/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -DPYCLLP_DEV_ONLY_3296 "$@" --cuda-device-only -S -o /tmp/regs.s "$(dirname "$0")"/../../pycllp_amd/csrc/ipm_dense.hip 2>&1 | grep -v "hip-link" 
 python - <<'PY'
 import re
 t = open("/tmp/regs.s").read()

@@ -175,6 +175,25 @@ def per_problem_a_config(m=128, n=256, density=0.025, nlp=32, batch=16384):
           "max gap", (np.abs(po - du) / np.maximum(1.0, np.abs(po))).max())
 
 
+SPARSE_SOLVER_CASES = ((128, 256, 96, 0.025), (128, 256, 16, 0.1), (40, 90, 64, 0.1), (12, 20, 33, 0.3), (100, 80, 8, 1.0))
+
+
+def sparse_solver_cases(nlp=8):
+    """The cases of tests/test_hip_parity.py::test_sparse_solver_matches_oracle_and_reference_solver (m, n, batch B,
+    density; generator seed m + n): the reference solver's objectives and statuses on the first `nlp` StandardLPs of each
+    batch (c is drawn after all of b, so B is part of the recipe; a checksum pins the inputs)."""
+    out = {}
+    for m, n, B, density in SPARSE_SOLVER_CASES:
+        A, b, c = problems.random_sparse_arrays(m, n, B, density=density, seed=m + n)
+        k = min(B, nlp)
+        g = hsd(np.asarray(A.todense()), b[:k], c[:k])
+        key = "%dx%d_B%d_d%g_" % (m, n, B, density)
+        out.update({key + "input_checksum": np.array([A.sum(), b.sum(), c.sum()]), key + "pobj": g["pobj"],
+                    key + "dobj": g["dobj"], key + "status": g["status"].astype(np.int8)})
+        print("sparse solver case %s: status" % key, np.bincount(g["status"]))
+    np.savez_compressed(os.path.join(OUT, "sparse_solver_cases.npz"), **out)
+
+
 def status_cases(nshape=8, nlp=32):
     """Mixed-sign random LPs, most of them infeasible or unbounded: inputs, the status the reference's HSD solver
     reports (ipo/hsd.c:156-177: 0 optimal, 2 primal infeasible, 4 dual infeasible) and, as an independent arbiter,
@@ -222,4 +241,5 @@ if __name__ == "__main__":
     dense_image_config()
     dense_image_config(200, 200, 16)
     per_problem_a_config()
+    sparse_solver_cases()
     status_cases()
