@@ -130,6 +130,21 @@ int pycllp_hip_dense_solve(pycllp_hip_dense *handle, long B, const double *b_dev
                            double *dobj_dev, int *status_dev, int *iters_dev,
                            const pycllp_hip_opts *opts, void *stream);
 
+/* Solve B LPs with UPPER BOUNDS, maximise c'x s.t. A x = b, 0 <= x <= u (the bounded equality form of a GeneralLP,
+ * pycllp_amd/lp.py GeneralLP.to_bounded_equality_form), on the bounded slack-aware lane-group kernel.  The handle's A must be
+ * [A_dense | I_m] with m <= 32 and at most 96 dense columns (the slack-aware kernels of pycllp_hip_dense_solve).
+ *   u_dev [B,n]      upper bounds: +inf = no bound, 0 = the column is fixed at 0 (it ends at x = 0)
+ *   s_dev [B,n]      (optional) duals of x <= u; z_dev (optional) those of x >= 0: A'y - z + s = c
+ *   dobj_dev [B]     b'y + u's over the finite u; the other arguments as pycllp_hip_dense_solve
+ * Options: PYCLLP_FLAG_AUTOSCALE (u scales with b) and PYCLLP_FLAG_FORCE_GUARD_PATH apply.
+ * Returns PYCLLP_E_BADARG for a NULL u_dev or any of the flags HSD, PREDCORR, WARM_START, WAVE_KERNEL, NO_SLACK_PATH, and
+ * PYCLLP_E_UNSUPPORTED when the handle has no slack-aware lane-group kernel; both before any HIP call.
+ * Asynchronous on `stream`. */
+int pycllp_hip_dense_solve_bounded(pycllp_hip_dense *handle, long B, const double *b_dev, const double *c_dev,
+                                   const double *u_dev, double *x_dev, double *y_dev, double *z_dev, double *s_dev,
+                                   double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
+                                   const pycllp_hip_opts *opts, void *stream);
+
 /* One Newton step of the primal normal equations for B independent states:
  *   dy <- solve( A diag(x/z) A' , -(b - A x - A diag(x/z) (c - A'y + mu/x)) )
  * x,z,c [B,n]; y,b,dy [B,m].  nrefine_dev [B] (optional) receives the refinement passes used. */

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("PYCLLP_HIP_LIB") or os.path.join(_HERE, "csrc", "libp
 EXPORTS = (
     "pycllp_hip_abi_version", "pycllp_hip_last_error", "pycllp_hip_default_opts",
     "pycllp_hip_dense_max_rows", "pycllp_hip_dense_max_cols", "pycllp_hip_dense_init",
-    "pycllp_hip_dense_solve", "pycllp_hip_dense_newton", "pycllp_hip_dense_launch_info",
+    "pycllp_hip_dense_solve", "pycllp_hip_dense_solve_bounded", "pycllp_hip_dense_newton", "pycllp_hip_dense_launch_info",
     "pycllp_hip_dense_free", "pycllp_hip_ldl", "pycllp_hip_dense_kernel_kind",
     "pycllp_hip_sparse_max_rows", "pycllp_hip_sparse_max_cols", "pycllp_hip_sparse_init", "pycllp_hip_sparse_solve",
     "pycllp_hip_sparse_free", "pycllp_hip_sparse_newton", "pycllp_hip_sparse_launch_info",
@@ -60,6 +60,9 @@ def lib():
     L.pycllp_hip_dense_solve.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, dp, dp, ip, ip,
                                          ctypes.POINTER(Opts), vp]
     L.pycllp_hip_dense_solve.restype = ctypes.c_int
+    L.pycllp_hip_dense_solve_bounded.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip, ip,
+                                                 ctypes.POINTER(Opts), vp]
+    L.pycllp_hip_dense_solve_bounded.restype = ctypes.c_int
     L.pycllp_hip_dense_newton.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, ctypes.c_double, dp, ip,
                                           ctypes.POINTER(Opts), vp]
     L.pycllp_hip_dense_newton.restype = ctypes.c_int

@@ -534,6 +534,7 @@ newton_kernel(int m, int n, long B, const double* __restrict__ pack, const doubl
 
 #include "ipm_group.inc"
 #include "ipm_group_hsd.inc"
+#include "ipm_group_bounded.inc"
 #include "ldl_batched.inc"
 #include "ipm_block.inc"
 
@@ -707,6 +708,42 @@ static hipError_t launch_solve_group(pycllp_hip_dense* h, long B, const double* 
     return e != hipSuccess ? e : e2;
 }
 
+typedef hipError_t (*bounded_launch_fn)(pycllp_hip_dense*, long, const double*, const double*, const double*, double*, double*,
+                                        double*, double*, double*, double*, int*, int*, DevOpts, hipStream_t);
+
+// the bounded slack-aware kernel (ipm_group_bounded.inc): the plan of launch_solve_group with PYCLLP_WPB_BOUNDED waves per workgroup
+template <int MP, int NP>
+static hipError_t launch_solve_bounded(pycllp_hip_dense* h, long B, const double* b, const double* c, const double* u, double* x,
+                                       double* y, double* z, double* s, double* pobj, double* dobj, int* status, int* iters,
+                                       DevOpts o, hipStream_t st) {
+    using G = GeoG<MP, NP, true>;
+    int wpb = PYCLLP_WPB_BOUNDED;
+    while (wpb > 1 && G::lds_bytes(wpb) > (size_t)h->max_lds) wpb--;
+    const long resident = (long)h->num_cu - o.reserve_cus > 0 ? (long)h->num_cu - o.reserve_cus : 1;
+    {
+        const long per_cu = (B + resident - 1) / resident;
+        long want = (per_cu <= 4 * (long)G::G) ? (per_cu < 4 ? per_cu : 4) : (per_cu + G::G - 1) / G::G;
+        if (want < 1) want = 1;
+        if (want < wpb) wpb = (int)want;
+    }
+    long blocks = (B + wpb - 1) / wpb;
+    if (blocks > resident) blocks = resident;
+    if (blocks < 1) blocks = 1;
+    const LaunchPlan p{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP};
+    auto kernel = ipm_bounded_kernel<MP, NP>;
+    hipError_t e = set_dyn_lds((const void*)kernel, p.lds);
+    if (e != hipSuccess) return e;
+    int* qhead = nullptr; unsigned slot = 0;
+    e = h->ring.acquire(st, &qhead, &slot);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, st, h->m, h->n, B,
+                       h->a_rm, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o);
+    e = hipGetLastError();
+    hipError_t e2 = h->ring.release(slot, st);
+    publish(h, p);
+    return e != hipSuccess ? e : e2;
+}
+
 template <int MP, int NP>
 static hipError_t launch_newton(pycllp_hip_dense* h, long B, const double* x, const double* z, const double* y,
                                 const double* b, const double* c, double mu, double* dy, int* nref, DevOpts o,
@@ -747,9 +784,9 @@ static const Variant kVariants[] = {
 static const int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
 // slack-aware group kernels: (MP, NP) with NP - MP padded dense columns + the m identity columns
-struct SlackVariant { int mp, np; solve_launch_fn solve_group, solve_hsd, solve_pc; };
+struct SlackVariant { int mp, np; solve_launch_fn solve_group, solve_hsd, solve_pc; bounded_launch_fn solve_bounded; };
 #define SLACK_VARIANT(MP, NP) { MP, NP, launch_solve_group<MP, NP, true>, launch_solve_group<MP, NP, true, true>, \
-                                launch_solve_group<MP, NP, true, false, true> }
+                                launch_solve_group<MP, NP, true, false, true>, launch_solve_bounded<MP, NP> }
 static const SlackVariant kSlackVariants[] = {
 #ifdef PYCLLP_DEV_ONLY_3296
     SLACK_VARIANT(32, 96),
@@ -955,6 +992,29 @@ int pycllp_hip_dense_solve(pycllp_hip_dense* h, long B, const double* b_dev, con
     hipError_t e = fn(h, B, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, o,
                       (hipStream_t)stream);
     if (e != hipSuccess) return set_err((int)e, "solve kernel launch");
+    return 0;
+}
+
+int pycllp_hip_dense_solve_bounded(pycllp_hip_dense* h, long B, const double* b_dev, const double* c_dev, const double* u_dev,
+                                   double* x_dev, double* y_dev, double* z_dev, double* s_dev, double* pobj_dev, double* dobj_dev,
+                                   int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
+    // every argument check comes before the handle is read and before any HIP call
+    if (!h || B < 0 || !u_dev) return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_bounded: bad argument");
+    const int flags = opts ? opts->flags : 0;
+    const int bad = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL | PYCLLP_FLAG_NO_SLACK_PATH;
+    if (flags & bad)
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH "
+                                        "are not available with upper bounds");
+    if (B > 0 && (!b_dev || !c_dev || !x_dev || !status_dev))
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_bounded: bad argument");
+    if (h->sp || h->variant_sl < 0)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_bounded: A is not [A_dense | I] with m <= 32 and at most 96 "
+                                             "dense columns (48 when m <= 16 on the 16-row kernels)");
+    if (B == 0) return 0;
+    DevOpts o = to_dev(opts);
+    hipError_t e = kSlackVariants[h->variant_sl].solve_bounded(h, B, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev,
+                                                               dobj_dev, status_dev, iters_dev, o, (hipStream_t)stream);
+    if (e != hipSuccess) return set_err((int)e, "bounded solve kernel launch");
     return 0;
 }
 

@@ -215,3 +215,78 @@ class GeneralLP(StandardLP):
         A2 = SparseMatrix(np.concatenate(rows), np.concatenate(cols), np.concatenate(data, axis=1))
         A2._shape = (bb.shape[1], n)
         return StandardLP(A2, bb, c, f)
+
+    def to_bounded_equality_form(self):
+        """(``BoundedEqualityLP``, ``BoundedMap``): the LP  max c^'x^ + f^  s.t.  A^ x^ = b^,  0 <= x^ <= u^  with the same
+        optimum, for the bounded kernel (``HipGeneralPrimalNormalSolver``).  Unlike ``to_standard_form`` it adds no row per upper
+        bound and no second row per ranged or equality row:
+          * x = l + x^:  b^ = b - A l,  a^ = a - A l,  f^ = f + c'l;
+          * one sign per row for the whole batch: b finite for every LP keeps +A (its slack gets the upper bound b^ - a^, +inf
+            where a is not finite, 0 for an equality row); b = +inf and a finite for every LP keeps -A with right-hand side
+            -a^ and an unbounded slack; a row without either bound in every LP is dropped; any other mix raises ``ValueError``;
+          * A^ = [+-A | I]: one +1 slack column per kept row, slacks last;  u^_j = u_j - l_j for the columns, +inf for none.
+        u^ = 0 marks a fixed variable (a column with l == u, the slack of an equality row).  A non-finite ``a`` of either sign
+        means "no lower bound" (the reference stores +inf there, this package -inf)."""
+        if np.isneginf(self.l).any():
+            raise ValueError('Lower bounds (l) contains -inf.')
+        if (self.u < self.l).any():
+            raise ValueError('Upper bounds (u) below lower bounds (l).')
+        afin0 = np.isfinite(self.a)
+        if (afin0 & (self.a > self.b)).any():
+            raise ValueError('Row lower bounds (a) above row upper bounds (b).')
+        m, n, B = self.nrows, self.ncols, self.nproblems
+        rows, cols, data = self.A._rows, self.A._cols, self.A.data
+        l = self.l
+        # A l for every LP in one product: per-problem values (data [B, nnz]) or one shared set (data [1, nnz])
+        S = sp.csr_matrix((np.ones(rows.size), (np.arange(rows.size), rows)), shape=(rows.size, m))
+        Al = np.asarray((S.T @ (data * l[:, cols]).T).T)
+        bh, ah = self.b - Al, self.a - Al
+        f = self.f + (self.c * l).sum(axis=1)
+        bfin, afin = np.isfinite(self.b), afin0
+        plus = bfin.all(axis=0)
+        minus = ~bfin.any(axis=0) & afin.all(axis=0)
+        drop = ~bfin.any(axis=0) & ~afin.any(axis=0)
+        mixed = ~(plus | minus | drop)
+        if mixed.any():
+            raise ValueError("Can not keep row %d in the bounded form: its bounds a, b are finite for some problems of the batch "
+                             "but not all." % int(np.flatnonzero(mixed)[0]))
+        keep = np.flatnonzero(plus | minus)
+        sign = np.where(plus[keep], 1.0, -1.0)
+        mk = keep.size
+        newrow = np.full(m, -1, dtype=np.int64)
+        newrow[keep] = np.arange(mk)
+        sel = newrow[rows] >= 0
+        rsign = sign[newrow[rows[sel]]]
+        A2 = SparseMatrix(np.concatenate([newrow[rows[sel]], np.arange(mk)]), np.concatenate([cols[sel], n + np.arange(mk)]),
+                          np.concatenate([rsign * data[:, sel], np.ones((data.shape[0], mk))], axis=1))
+        A2._shape = (mk, n + mk)
+        b2 = np.where(plus[keep], bh[:, keep], -ah[:, keep])
+        with np.errstate(invalid="ignore"):
+            us = np.where(plus[keep], np.where(np.isfinite(ah[:, keep]), bh[:, keep] - ah[:, keep], np.inf), np.inf)
+        u2 = np.concatenate([np.where(np.isfinite(self.u), self.u - l, np.inf), us], axis=1)
+        c2 = np.concatenate([self.c, np.zeros((B, mk))], axis=1)
+        return BoundedEqualityLP(A2, b2, c2, f, u2), BoundedMap(l.copy(), keep, sign, m)
+
+
+class BoundedEqualityLP(EqualityLP):
+    """maximise c'x + f  subject to  A x = b,  0 <= x <= u   (u [nproblems, ncols]: +inf = no bound, 0 = fixed)."""
+
+    def __init__(self, A=None, b=None, c=None, f=None, u=None):
+        super(BoundedEqualityLP, self).__init__(A=A, b=b, c=c, f=f)
+        self.u = np.full(self.c.shape, np.inf) if u is None else np.array(u, dtype=np.float64).reshape(self.c.shape)
+
+
+class BoundedMap(object):
+    """Maps a solution of ``GeneralLP.to_bounded_equality_form()`` back to the GeneralLP's variables and rows."""
+
+    def __init__(self, l, rows, sign, m):
+        self.l, self.rows, self.sign, self.m = l, rows, sign, m
+
+    def general(self, x, y, z=None, s=None):
+        """(x, y, z, s) of the GeneralLP from x^, y^ (and the duals z^, s^ of x^ >= 0, x^ <= u^): x = l + x^ over the original
+        columns, y per original row (sign restored, 0 for a dropped row), z / s the duals of x >= l / x <= u."""
+        n = self.l.shape[1]
+        x = self.l + np.asarray(x)[:, :n]
+        yo = np.zeros((x.shape[0], self.m))
+        yo[:, self.rows] = self.sign * np.asarray(y)
+        return (x, yo, None if z is None else np.asarray(z)[:, :n].copy(), None if s is None else np.asarray(s)[:, :n].copy())

@@ -1,0 +1,221 @@
+"""HIP solver plugin for ``GeneralLP``:  optimise c'x + f  s.t.  a <= A x <= b,  l <= x <= u.
+
+The LP is brought into the bounded equality form (``GeneralLP.to_bounded_equality_form``: A^ = [+-A | I], 0 <= x^ <= u^) and
+solved on the bounded slack-aware lane-group kernel (``pycllp_hip_dense_solve_bounded``, csrc/ipm_group_bounded.inc): one row
+per kept row of the LP and no row per upper bound.  What that kernel does not serve -- more than 32 kept rows, more than 96
+columns, per-problem values of A -- is solved through the reference's conversion ``to_standard_form().to_equality_form()``
+(``pycllp/lp.py:725-792``) on ``HipDensePrimalNormalSolver`` and mapped back the same way, so the plugin takes every LP the
+library takes.  ``kernel`` tells which path served the last ``solve``: ``'bounded group'`` or ``'expanded'``.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import BaseGeneralSolver
+from .. import _native
+from ..lp import GeneralLP, SparseMatrix
+from .hip import HipDensePrimalNormalSolver, _require_gpu, autoscale_wanted
+
+NATIVE_MAX_ROWS, NATIVE_MAX_COLS = 32, 96      # the slack-aware kernels: m' <= 32 rows, n <= 96 original columns
+_REJECTED = (_native.FLAG_HSD | _native.FLAG_PREDCORR | _native.FLAG_WARM_START | _native.FLAG_WAVE_KERNEL
+             | _native.FLAG_NO_SLACK_PATH)
+RESULTS = ("x", "y", "z", "s", "status", "iters", "primal_obj", "dual_obj")
+
+
+def as_general(lp):
+    """This package's ``GeneralLP`` for ``lp`` (duck-typed on ``A, a, b, c, l, u, f``: a reference GeneralLP works too)."""
+    if isinstance(lp, GeneralLP):
+        return lp
+    A = lp.A if isinstance(lp.A, SparseMatrix) else SparseMatrix(matrix=np.asarray(lp.A.todense(), dtype=np.float64))
+    return GeneralLP(A, lp.b, lp.c, a=getattr(lp, "a", None), l=getattr(lp, "l", None), u=getattr(lp, "u", None),
+                     f=getattr(lp, "f", 0.0))
+
+
+def subset(glp, idx):
+    """The GeneralLP of the problems ``idx`` of ``glp``."""
+    A = glp.A
+    data = A.data[idx] if A.nproblems > 1 else A.data
+    A2 = SparseMatrix(A._rows.copy(), A._cols.copy(), data.copy())
+    A2._shape = (glp.nrows, glp.ncols)
+    return GeneralLP(A2, glp.b[idx], glp.c[idx], a=glp.a[idx], l=glp.l[idx], u=glp.u[idx], f=glp.f[idx])
+
+
+class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
+    """``glp.init(s); glp.solve(s)`` on a ``GeneralLP``; results in the ORIGINAL variables: ``x [B, n]``, ``y [B, m]`` (one
+    per row of the LP, 0 for a row without bounds), ``z`` / ``s [B, n]`` (duals of x >= l / x <= u), ``status``, ``iters``,
+    ``primal_obj``, ``dual_obj`` (f and c'l included)."""
+    name = 'hip_general_primal_normal'
+
+    def __init__(self, device=None, stream=None, autoscale="auto", hsd="auto", predcorr=False, warm_start=False, **options):
+        """``hsd='auto'`` (default): the LPs that do not end optimal on the bounded kernel are solved again through the
+        expansion on ``HipDensePrimalNormalSolver`` (whose own ``hsd='auto'`` gives infeasible / unbounded LPs the certified
+        statuses 2 / 4); ``hsd=False``: the bounded kernel's verdict stands.  ``hsd=True``, ``predcorr=True`` and
+        ``warm_start=True`` are not available with bounds.  ``autoscale``: as ``HipDensePrimalNormalSolver`` (the 'auto' band
+        rule also looks at the finite upper bounds).  Other keyword arguments are fields of ``pycllp_hip_opts``."""
+        if not (hsd is False or (isinstance(hsd, str) and hsd == "auto")):
+            raise ValueError("hsd must be 'auto' or False for %s (the bounded kernel has no embedding)" % self.name)
+        if predcorr:
+            raise ValueError("predcorr is not available with upper bounds")
+        if warm_start:
+            raise ValueError("warm_start is not available with upper bounds")
+        if int(options.get("flags", 0)) & _REJECTED:
+            raise ValueError("flags HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH are not available with upper bounds")
+        if isinstance(autoscale, str):
+            if autoscale != "auto":
+                raise ValueError("autoscale must be True, False or 'auto'")
+        else:
+            autoscale = bool(autoscale)
+        if int(options.get("flags", 0)) & _native.FLAG_AUTOSCALE:
+            autoscale = True
+        self.autoscale, self.hsd = autoscale, hsd
+        self.device, self.stream = device, stream
+        self.options = dict(options)
+        _native.default_opts(**self.options) if options else None   # validate names early
+        self._handle = None
+        self._key = None
+        self.kernel = None
+
+    def _free(self):
+        if self._handle is not None:
+            _native.lib().pycllp_hip_dense_free(self._handle)
+            self._handle = None
+            self._key = None
+
+    def __del__(self):
+        try:
+            self._free()
+        except Exception:
+            pass
+
+    def _stream_ptr(self):
+        st = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
+        return ctypes.c_void_p(st.cuda_stream)
+
+    @staticmethod
+    def native_fits(glp, blp):
+        return glp.A.nproblems == 1 and 1 <= blp.nrows <= NATIVE_MAX_ROWS and glp.ncols <= NATIVE_MAX_COLS
+
+    def _ensure_handle(self, blp):
+        """A handle for A^ (re-made when the kept rows or their signs changed since the last one); False if A^ is not served."""
+        A = np.ascontiguousarray(blp.A.todense(), dtype=np.float64)
+        key = (A.shape, A.tobytes())
+        if self._handle is not None and self._key == key:
+            return True
+        self._free()
+        with torch.cuda.device(self.device):
+            A_dev = torch.as_tensor(A, device=self.device)
+            h = ctypes.c_void_p()
+            rc = _native.lib().pycllp_hip_dense_init(A.shape[0], A.shape[1], ctypes.c_void_p(A_dev.data_ptr()), self._stream_ptr(),
+                                                     ctypes.byref(h))
+            torch.cuda.synchronize(self.device)
+        if rc == -2:
+            return False
+        _native.check(rc, "pycllp_hip_dense_init")
+        self._handle, self._key = h, key
+        return True
+
+    # -- plugin API ------------------------------------------------------------------------------
+    def init(self, lp, verbose=0):
+        self.device = _require_gpu(self.device)
+        glp = as_general(lp)
+        blp, _ = glp.to_bounded_equality_form()
+        if self.native_fits(glp, blp):
+            self._ensure_handle(blp)
+        self.m, self.n = glp.nrows, glp.ncols
+
+    def solve(self, lp, verbose=0):
+        glp = as_general(lp)
+        if glp.nrows != self.m or glp.ncols != self.n:
+            raise ValueError("LP shape changed since init(): (%d,%d) vs (%d,%d)" % (glp.nrows, glp.ncols, self.m, self.n))
+        blp, bmap = glp.to_bounded_equality_form()
+        res = None
+        if self.native_fits(glp, blp) and self._ensure_handle(blp):
+            res = self._solve_bounded(blp, bmap)
+        if res is None:
+            self.kernel = "expanded"
+            res = self.solve_expanded(glp)
+        else:
+            self.kernel = "bounded group"
+            if self.hsd == "auto":
+                idx = np.flatnonzero(res["status"] != 0)
+                if idx.size:
+                    r2 = self.solve_expanded(subset(glp, idx))
+                    for k in RESULTS:
+                        res[k][idx] = r2[k]
+        for k in RESULTS:
+            setattr(self, k, res[k])
+        return self.status
+
+    def _solve_bounded(self, blp, bmap):
+        """One upload, one launch of the bounded kernel, one download; None if the library declines A^ (PYCLLP_E_UNSUPPORTED)."""
+        B, mk, N = blp.nproblems, blp.nrows, blp.ncols
+        opts = dict(self.options)
+        flags = int(opts.get("flags", 0))
+        if self.autoscale is True or (self.autoscale == "auto" and autoscale_wanted(blp.b, blp.c, blp.u)):
+            flags |= _native.FLAG_AUTOSCALE
+        opts["flags"] = flags
+        o = _native.default_opts(**opts)
+        if o.max_iter < 1 or o.max_refine < _native.MAX_REFINE_AUTO or not (o.eps > 0):
+            raise ValueError("max_iter must be >= 1, max_refine >= 0 (or -1 = auto) and eps > 0")
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            b = torch.as_tensor(np.ascontiguousarray(blp.b), **f64)
+            c = torch.as_tensor(np.ascontiguousarray(blp.c), **f64)
+            u = torch.as_tensor(np.ascontiguousarray(blp.u), **f64)
+            x, z, s = (torch.empty((B, N), **f64) for _ in range(3))
+            y = torch.empty((B, mk), **f64)
+            pobj, dobj = torch.empty(B, **f64), torch.empty(B, **f64)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            iters = torch.empty(B, dtype=torch.int32, device=dev)
+            P = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+            rc = _native.lib().pycllp_hip_dense_solve_bounded(
+                self._handle, B, P(b), P(c), P(u), P(x), P(y), P(z), P(s), P(pobj), P(dobj), P(status), P(iters),
+                ctypes.byref(o), self._stream_ptr())
+            if rc == -2:
+                return None
+            _native.check(rc, "pycllp_hip_dense_solve_bounded")
+            torch.cuda.synchronize(dev)
+        xo, yo, zo, so = bmap.general(x.cpu().numpy(), y.cpu().numpy(), z.cpu().numpy(), s.cpu().numpy())
+        f = np.broadcast_to(blp.f, (B,))
+        return dict(x=xo, y=yo, z=zo, s=so, status=status.cpu().numpy(), iters=iters.cpu().numpy(),
+                    primal_obj=pobj.cpu().numpy() + f, dual_obj=dobj.cpu().numpy() + f)
+
+    def solve_expanded(self, glp):
+        """Solve ``glp`` through ``to_standard_form().to_equality_form()`` on ``HipDensePrimalNormalSolver`` and map the results
+        back to the GeneralLP's variables.  The expansion needs every bound finite for all LPs or for none; a batch that mixes
+        them (u = +inf for some LPs only) is solved in groups of equal pattern."""
+        B, m, n = glp.nproblems, glp.nrows, glp.ncols
+        out = dict(x=np.zeros((B, n)), y=np.zeros((B, m)), z=np.zeros((B, n)), s=np.zeros((B, n)),
+                   status=np.zeros(B, dtype=np.int32), iters=np.zeros(B, dtype=np.int32),
+                   primal_obj=np.zeros(B), dual_obj=np.zeros(B))
+        pattern = np.concatenate([np.isfinite(glp.a), np.isfinite(glp.b), np.isfinite(glp.u)], axis=1)
+        _, group = np.unique(pattern, axis=0, return_inverse=True)
+        for gi in np.unique(group):
+            idx = np.flatnonzero(group.reshape(-1) == gi)
+            g = glp if idx.size == B else subset(glp, idx)
+            keep_lo = np.isfinite(g.a).any(axis=0)
+            keep_hi = np.isfinite(g.b).any(axis=0)
+            keep_ub = np.isfinite(g.u).any(axis=0)
+            eq = g.to_standard_form().to_equality_form()
+            solver = HipDensePrimalNormalSolver(device=self.device, stream=self.stream, autoscale=self.autoscale, hsd=self.hsd,
+                                                **self.options)
+            eq.init(solver)
+            eq.solve(solver)
+            nlo, nhi = int(keep_lo.sum()), int(keep_hi.sum())
+            ye = np.asarray(solver.y)
+            y = np.zeros((idx.size, m))
+            y[:, keep_lo] -= ye[:, :nlo]
+            y[:, keep_hi] += ye[:, nlo:nlo + nhi]
+            s = np.zeros((idx.size, n))
+            s[:, keep_ub] = ye[:, nlo + nhi:nlo + nhi + int(keep_ub.sum())]
+            out["x"][idx] = g.l + np.asarray(solver.x)[:, :n]
+            out["y"][idx] = y
+            out["z"][idx] = np.asarray(solver.z)[:, :n]
+            out["s"][idx] = s
+            out["status"][idx] = solver.status
+            out["iters"][idx] = solver.iters
+            out["primal_obj"][idx] = solver.primal_obj
+            out["dual_obj"][idx] = solver.dual_obj
+        return out

@@ -57,11 +57,20 @@ SPARSE_KERNEL_KINDS = {0: ("block", "block"), 1: ("tables", "wave"), 2: ("dense 
 AUTOSCALE_BAND = (0.1, 10.0)
 
 
-def autoscale_wanted(b, c):
+def autoscale_wanted(b, c, u=None):
     """The ``autoscale='auto'`` rule: True when, for any LP of the batch, max|b| or max|c| lies outside [0.1, 10] -- the
     start x = z = y = 1 and the unit floors of the tolerances (eps (1 + |b|)) are tuned to data of order 1 (DESIGN.md section
-    2, scaling caveat: decades away from 1 cost 40-170 iterations and objective accuracy).  numpy arrays or torch tensors."""
+    2, scaling caveat: decades away from 1 cost 40-170 iterations and objective accuracy).  numpy arrays or torch tensors.
+    ``u`` (numpy, optional): upper bounds of a bounded LP; max of the finite positive u of an LP outside the band counts too (an
+    LP without one -- no bounds, or only fixed variables -- is left out of that test)."""
     lo, hi = AUTOSCALE_BAND
+    if u is not None:
+        u = np.asarray(u, dtype=np.float64)
+        fin = np.isfinite(u) & (u > 0)
+        has = fin.any(axis=-1)
+        mx = np.where(fin, np.abs(u), 0.0).max(axis=-1) if u.size else np.zeros(0)
+        if (has & ((mx < lo) | (mx > hi))).any():
+            return True
     for v in (b, c):
         if isinstance(v, torch.Tensor):
             if v.numel() == 0:
