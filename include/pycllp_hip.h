@@ -80,8 +80,8 @@ extern "C" {
 #define PYCLLP_FLAG_BLOCK_KERNEL 64 /* sparse solver: use the workgroup-per-LP kernel (ipm_block_kernel) even where the
                                        register-resident wavefront-per-LP kernel covers the problem (diagnostic / A-B runs;
                                        results agree to rounding)                                                  */
-#define PYCLLP_FLAG_WAVE_KERNEL 2 /* use the first-generation kernel (one LP per wavefront) instead
-                                     of the default one (one LP per 16/32-lane group)          */
+#define PYCLLP_FLAG_WAVE_KERNEL 2 /* the first-generation kernel (one LP per wavefront), since removed:
+                                     pycllp_hip_dense_solve answers it with PYCLLP_E_UNSUPPORTED  */
 
 #define PYCLLP_MAX_REFINE_AUTO (-1)
 #define PYCLLP_MAX_REFINE_PLAIN 5

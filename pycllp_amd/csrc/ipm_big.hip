@@ -25,9 +25,6 @@
 // The Nocedal-Wright guard (ldl.cl:368) is recorded, not applied, by the blocked factorisation; when it would have bitten
 // (rare: collapsing iterates of the embedding) M is re-formed and a column-by-column cold path applies it exactly.
 #include "big.h"
-#ifndef PYCLLP_WINV_FUSED
-#define PYCLLP_WINV_FUSED 1     // see ipm_wreg.hip
-#endif
 
 namespace {
 
@@ -261,7 +258,6 @@ ipm_big_kernel(BigTab T, long B, const double* __restrict__ bg, const double* __
                 for (int r = 0; r < 4; r++) tile[(4 * r + q) * 17 + c16] = blk[r * 64 + lane];
                 wave_lds_sync();
                 double Wd[16], Ws[4];
-                [[maybe_unused]] double Ld[16];
 #pragma unroll
                 for (int k = 0; k < 16; k++) Wd[k] = tile[c16 * 17 + k];
 #pragma unroll
@@ -283,17 +279,11 @@ ipm_big_kernel(BigTab T, long B, const double* __restrict__ bg, const double* __
                         double aDn, rDn;
                         chain_step_pipe_relf<j>(Wd, u, nli, 0.0, myf, aDn, rDn);
                         rD = rDn;
-                        if constexpr (PYCLLP_WINV_FUSED) winv_step<j>(Ws, nli); else Ld[j] = nli;    // see ipm_wreg.hip
+                        winv_step<j>(Ws, nli);      // step j of W = L_KK^-1 rides along with the sweep (see ipm_wreg.hip)
                     }
                 });
                 if (q == 0) rdv[16 * K + c16] = rdiag;
-                // W = L_KK^-1: Ws[s] = W[row c16][column 4s + q] (the A-operand layout of the panel's MFMAs); Ld holds -L
-                if constexpr (!PYCLLP_WINV_FUSED) {
-                    static_for<0, 15>([&](auto jc) {
-                        constexpr int j = decltype(jc)::value;
-                        winv_step<j>(Ws, Ld[j]);
-                    });
-                }
+                // W = L_KK^-1: Ws[s] = W[row c16][column 4s + q] (the A-operand layout of the panel's MFMAs)
 #pragma unroll
                 for (int s = 0; s < 4; s++) { wsA[s * 64 + lane] = Ws[s]; wl[K * 256 + c16 * 16 + 4 * s + q] = Ws[s]; }
             }

@@ -343,142 +343,6 @@ struct Wave {
 };
 
 // ------------------------------------------------------------------------------------------------
-// solve kernel: standard_primal_normal (primal_normal.cl:201-284), one LP per wavefront, persistent.
-// FIRST GENERATION (round 1), superseded by ipm_group_kernel: compiled only with -DPYCLLP_FIRST_GEN (diagnostic A/B
-// builds); the default library answers PYCLLP_FLAG_WAVE_KERNEL with PYCLLP_E_UNSUPPORTED.
-// ------------------------------------------------------------------------------------------------
-#ifdef PYCLLP_FIRST_GEN
-template <int MP, int NP>
-__global__ void __launch_bounds__(512)
-ipm_solve_kernel(int m, int n, long B, const double* __restrict__ pack, const double* __restrict__ bg,
-                 const double* __restrict__ cg, double* __restrict__ xg, double* __restrict__ yg,
-                 double* __restrict__ zg, double* __restrict__ pobj, double* __restrict__ dobj,
-                 int* __restrict__ status, int* __restrict__ iters, DevOpts o) {
-    using G = Geo<MP, NP>;
-    constexpr int NC = G::NC;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int tid = threadIdx.x;
-    const int wpb = blockDim.x / WAVE;
-    // stage both images of A (shared by the workgroup's waves)
-    for (int i = tid; i < G::APACK; i += blockDim.x) lds[i] = pack[i];
-    __syncthreads();
-
-    Wave<MP, NP> w;
-    const int wave = tid / WAVE;
-    w.lane = tid & 63;
-    w.ri = w.lane & (MP - 1);
-    w.m = m; w.n = n;
-    w.Amf = lds;
-    w.Arm = lds + G::AMF;
-    w.slab = lds + G::APACK + wave * G::WSLAB;
-    w.kx = w.slab + MP * G::MS;
-    w.kd = w.kx + NP;
-    w.kdt = w.kd + NP;
-    const int lane = w.lane, ri = w.ri;
-    const bool rowok = ri < m;
-    const bool warm = (o.flags & PYCLLP_FLAG_WARM_START) != 0;
-    STAMP_DECL
-
-    for (long lp = (long)blockIdx.x * wpb + wave; lp < B; lp += (long)gridDim.x * wpb) {
-        double x[NC], z[NC], c[NC], v[NC];
-        bool ok[NC];
-#pragma unroll
-        for (int q = 0; q < NC; q++) {
-            const int j = lane + 64 * q;
-            ok[q] = j < n;
-            c[q] = ok[q] ? cg[lp * n + j] : 0.0;
-            x[q] = (warm && ok[q]) ? xg[lp * n + j] : 1.0;
-            z[q] = (warm && ok[q]) ? zg[lp * n + j] : 1.0;
-        }
-        const double b = rowok ? bg[lp * m + ri] : 0.0;
-        double y = rowok ? ((warm && yg) ? yg[lp * m + ri] : 1.0) : 0.0;
-        w.At_times(y, v);
-
-        double nb2 = wave_sum((lane < MP) ? b * b : 0.0);
-        double nc2 = 0.0;
-#pragma unroll
-        for (int q = 0; q < NC; q++) nc2 += c[q] * c[q];
-        nc2 = wave_sum(nc2);
-        const double tol_r = o.eps * (1.0 + sqrt(nb2));
-        const double tol_s = o.eps * (1.0 + sqrt(nc2));
-        const double etol = o.refine_tol * (1.0 + sqrt(nb2));
-        double normr0 = 1e300, norms0 = 1e300;
-        int stat = PYCLLP_STATUS_ITERATION_LIMIT, it = 0;
-        double po = 0.0, du = 0.0;
-        STAMP(9)
-
-        for (it = 0; it < o.max_iter; it++) {
-            // dual infeasibility, complementarity, objectives (primal_normal.cl:76-94, 245-248)
-            double s2 = 0.0, gam = 0.0, pp = 0.0;
-#pragma unroll
-            for (int q = 0; q < NC; q++) {
-                const double sg = ok[q] ? c[q] - v[q] + z[q] : 0.0;
-                s2 = fma(sg, sg, s2);
-                gam += ok[q] ? x[q] * z[q] : 0.0;
-                pp += c[q] * (ok[q] ? x[q] : 0.0);
-            }
-            s2 = wave_sum(s2); gam = wave_sum(gam); po = wave_sum(pp);
-            du = wave_sum((lane < MP) ? b * y : 0.0);
-            const double norms = sqrt(s2);
-            const double mu = o.delta * gam / (double)(n + m);  // primal_normal.cl:272
-
-            // Newton step (also yields rho = b - Ax for the stop test of THIS point)
-            double dx[NC], wv[NC], rho;
-            int nref;
-            STAMP(0)
-            const double dy = w.newton(x, z, c, v, b, mu, etol, o, dx, wv, rho, nref STAMP_PASS);
-            const double normr = sqrt(wave_sum((lane < MP) ? rho * rho : 0.0));
-
-            if (!(isfinite(normr) && isfinite(norms) && isfinite(gam))) { stat = PYCLLP_STATUS_NUMERICAL; break; }
-            if (normr <= tol_r && norms <= tol_s && gam <= o.eps * (1.0 + fabs(po))) { stat = PYCLLP_STATUS_OPTIMAL; break; }
-            if (normr > 10.0 * normr0 && normr > PYCLLP_GROWTH_FLOOR * tol_r) { stat = PYCLLP_STATUS_PRIMAL_INFEASIBLE; break; }
-            if (norms > 10.0 * norms0 && norms > PYCLLP_GROWTH_FLOOR * tol_s) { stat = PYCLLP_STATUS_DUAL_INFEASIBLE; break; }
-            if (__any(!isfinite(dy))) { stat = PYCLLP_STATUS_NUMERICAL; break; }
-
-            // step (primal_normal.cl:122-156)
-            double dz[NC];
-            double th = 0.0;
-#pragma unroll
-            for (int q = 0; q < NC; q++) {
-                dz[q] = ok[q] ? (mu - z[q] * dx[q]) / x[q] - z[q] : 0.0;
-                if (ok[q]) th = fmax(th, fmax(-dz[q] / z[q], -dx[q] / x[q]));
-            }
-            th = wave_max(th);
-            const double theta = fmin(o.r / th, 1.0);
-            y = fma(theta, dy, y);
-#pragma unroll
-            for (int q = 0; q < NC; q++) {
-                x[q] = fma(theta, dx[q], x[q]);
-                z[q] = fma(theta, dz[q], z[q]);
-                v[q] = fma(theta, wv[q], v[q]);  // A'y carried along: A'(y + theta dy)
-            }
-            normr0 = normr;
-            norms0 = norms;
-            STAMP(8)
-        }
-
-#pragma unroll
-        for (int q = 0; q < NC; q++) {
-            const int j = lane + 64 * q;
-            if (ok[q]) {
-                xg[lp * n + j] = x[q];
-                if (zg) zg[lp * n + j] = z[q];
-            }
-        }
-        if (yg && lane < MP && rowok) yg[lp * m + ri] = y;
-        if (lane == 0) {
-            if (pobj) pobj[lp] = po;
-            if (dobj) dobj[lp] = du;
-            status[lp] = stat;
-            if (iters) iters[lp] = it;
-        }
-        STAMP(9)
-    }
-    STAMP_FLUSH(o, blockIdx.x * wpb + wave)
-}
-#endif  // PYCLLP_FIRST_GEN
-
-// ------------------------------------------------------------------------------------------------
 // stand-alone Newton step kernel: solve_primal_normal (ldl.cl:602-653) as launched by the reference's
 // tests/test_ldl.py:219-273
 // ------------------------------------------------------------------------------------------------
@@ -651,24 +515,6 @@ static hipError_t launch_pack(pycllp_hip_dense* h, const double* A, hipStream_t 
     return hipGetLastError();
 }
 
-#ifdef PYCLLP_FIRST_GEN
-template <int MP, int NP>
-static hipError_t launch_solve(pycllp_hip_dense* h, long B, const double* b, const double* c, double* x, double* y,
-                               double* z, double* pobj, double* dobj, int* status, int* iters, DevOpts o,
-                               hipStream_t st) {
-    const LaunchPlan p = plan<MP, NP>(h, B);
-    hipError_t e = set_dyn_lds((const void*)ipm_solve_kernel<MP, NP>, p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((ipm_solve_kernel<MP, NP>), dim3(p.grid), dim3(p.block), p.lds, st, h->m, h->n, B,
-                       h->pack, b, c, x, y, z, pobj, dobj, status, iters, o);
-    publish(h, p);
-    return hipGetLastError();
-}
-#define FIRST_GEN_SOLVE(MP, NP) launch_solve<MP, NP>
-#else
-#define FIRST_GEN_SOLVE(MP, NP) nullptr
-#endif
-
 template <int MP, int NP, bool SL, bool HSD = false, bool PC = false>
 static hipError_t launch_solve_group(pycllp_hip_dense* h, long B, const double* b, const double* c, double* x, double* y,
                                      double* z, double* pobj, double* dobj, int* status, int* iters, DevOpts o,
@@ -759,7 +605,6 @@ static hipError_t launch_newton(pycllp_hip_dense* h, long B, const double* x, co
 struct Variant {
     int mp, np, apack;
     pack_launch_fn pack;
-    solve_launch_fn solve;        // wave-per-LP kernel (first generation)
     solve_launch_fn solve_group;  // group-per-LP kernel (default)
     solve_launch_fn solve_hsd;    // group-per-LP kernel on the homogeneous self-dual embedding (PYCLLP_FLAG_HSD)
     solve_launch_fn solve_pc;     // group-per-LP kernel with Mehrotra's predictor-corrector (PYCLLP_FLAG_PREDCORR)
@@ -767,7 +612,7 @@ struct Variant {
 };
 
 #define VARIANT(MP, NP) \
-    { MP, NP, Geo<MP, NP>::APACK, launch_pack<MP, NP>, FIRST_GEN_SOLVE(MP, NP), launch_solve_group<MP, NP, false>, \
+    { MP, NP, Geo<MP, NP>::APACK, launch_pack<MP, NP>, launch_solve_group<MP, NP, false>, \
       launch_solve_group<MP, NP, false, true>, launch_solve_group<MP, NP, false, false, true>, launch_newton<MP, NP> }
 
 // ordered by cost: the first variant that covers (m, n) is used
@@ -800,7 +645,7 @@ static const SlackVariant kSlackVariants[] = {
 static const int kNumSlackVariants = sizeof(kSlackVariants) / sizeof(kSlackVariants[0]);
 
 static unsigned long long* g_prof = nullptr;  // diagnostic build only
-#if defined(PYCLLP_PROFILE) || defined(PYCLLP_WREG_DEBUG)
+#ifdef PYCLLP_PROFILE
 extern "C" void pycllp_hip_debug_set_prof(void* p) { g_prof = (unsigned long long*)p; }
 #endif
 
@@ -980,14 +825,12 @@ int pycllp_hip_dense_solve(pycllp_hip_dense* h, long B, const double* b_dev, con
         return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve: PYCLLP_FLAG_HSD is not available with PYCLLP_FLAG_WAVE_KERNEL");
     if ((o.flags & PYCLLP_FLAG_PREDCORR) && (o.flags & (PYCLLP_FLAG_HSD | PYCLLP_FLAG_WAVE_KERNEL)))
         return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve: PYCLLP_FLAG_PREDCORR is an option of the reference's path (not with PYCLLP_FLAG_HSD)");
+    if (o.flags & PYCLLP_FLAG_WAVE_KERNEL)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve: the first-generation kernel (PYCLLP_FLAG_WAVE_KERNEL) has been removed");
     const Variant& v = kVariants[h->variant];
     const bool hsd = (o.flags & PYCLLP_FLAG_HSD) != 0, pc = (o.flags & PYCLLP_FLAG_PREDCORR) != 0;
     solve_launch_fn fn = hsd ? v.solve_hsd : (pc ? v.solve_pc : v.solve_group);
-    if (o.flags & PYCLLP_FLAG_WAVE_KERNEL) {
-        fn = v.solve;
-        if (!fn) return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve: the first-generation kernel (PYCLLP_FLAG_WAVE_KERNEL) is not "
-                                                      "part of this build (diagnostic builds: make EXTRA=-DPYCLLP_FIRST_GEN)");
-    } else if (h->variant_sl >= 0 && !(o.flags & PYCLLP_FLAG_NO_SLACK_PATH))
+    if (h->variant_sl >= 0 && !(o.flags & PYCLLP_FLAG_NO_SLACK_PATH))
         fn = hsd ? kSlackVariants[h->variant_sl].solve_hsd : (pc ? kSlackVariants[h->variant_sl].solve_pc : kSlackVariants[h->variant_sl].solve_group);
     hipError_t e = fn(h, B, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, o,
                       (hipStream_t)stream);

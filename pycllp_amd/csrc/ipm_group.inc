@@ -1,7 +1,7 @@
 // ipm_group.inc -- second-generation solve kernel: one LP per LANE GROUP (MP lanes), G = 64/MP LPs per wavefront.
 //
-// Why: in the wave-per-LP kernel (ipm_dense.hip) the LDL' factorisation and the triangular solves keep one matrix
-// row per lane, so with m <= 32 only half (m <= 16: a quarter) of the 64 lanes work during ~50 % of the run time.
+// Why: in the first-generation wave-per-LP kernel (since removed) the LDL' factorisation and the triangular solves kept one
+// matrix row per lane, so with m <= 32 only half (m <= 16: a quarter) of the 64 lanes worked during ~50 % of the run time.
 // Here the lanes [g*MP, (g+1)*MP) of a wave form a group that owns its own LP for the whole solve:
 //   * m-vectors: lane gl = lane % MP holds element gl of its group's LP (no replication);
 //   * N-vectors: NCG = NP/MP registers per lane, column j = gl + MP*q;
@@ -32,31 +32,11 @@
 #ifndef PYCLLP_AT_RB
 #define PYCLLP_AT_RB 4     // rows of A per batch of the pipelined A'u
 #endif
-#ifndef PYCLLP_AT_PIN_SUMS
-#define PYCLLP_AT_PIN_SUMS 1   // the partial sums of A'u are pinned after every batch: left free, the scheduler may sink every FMA below
-                               // the last batch's loads, and the whole image of A is live at once (the predictor-corrector kernel
-                               // spilled 96-433 registers that way; 6.06 -> 5.45 ms at (32, 96))
-#endif
 #ifndef PYCLLP_A_CB
 #define PYCLLP_A_CB 8      // columns of A per batch of the pipelined A v
 #endif
-#ifndef PYCLLP_EXEC_FACTOR
-#define PYCLLP_EXEC_FACTOR 1   // the LDL' sweep takes "below the pivot" / "the pivot's lane" as EXEC masks (wave_common.h, round 3)
-#endif
-#ifndef PYCLLP_ROWBASE
-#define PYCLLP_ROWBASE 1
-#endif
-#ifndef PYCLLP_COLBASE
-#define PYCLLP_COLBASE 1
-#endif
-#ifndef PYCLLP_BOTTOM_UNMASKED
-#define PYCLLP_BOTTOM_UNMASKED 1
-#endif
 #ifndef PYCLLP_SOLVE_PRIO
 #define PYCLLP_SOLVE_PRIO 2    // s_setprio level inside the substitution (with PYCLLP_FACTOR_PRIO 2: 5.93 -> 5.91 ms; each alone: nothing)
-#endif
-#ifndef PYCLLP_GRAM_PRIO
-#define PYCLLP_GRAM_PRIO 0     // s_setprio level of a wave inside the MFMA loop of the Gram product (0: none)
 #endif
 #ifndef PYCLLP_FACTOR_PRIO
 #define PYCLLP_FACTOR_PRIO 2       // s_setprio level of a wave inside the LDL' sweep, plain / predictor-corrector kernels (0: none)
@@ -64,18 +44,6 @@
 #ifndef PYCLLP_FACTOR_PRIO_HSD
 #define PYCLLP_FACTOR_PRIO_HSD 3   // ... of the HSD kernel (see GWave::factor_dpp)
 #endif
-#ifndef PYCLLP_TOPROW_LDS
-#define PYCLLP_TOPROW_LDS 0    // 1: see GWave::factor_dpp (round 3 experiment: slower, 6.02-6.09 against 5.94 ms)
-#endif
-#ifndef PYCLLP_PIPE_FACTOR
-#define PYCLLP_PIPE_FACTOR 0   // 1: software-pipelined pivot chain in factor_dpp (round 3 experiment, see the comment there: no gain)
-#endif
-#ifndef PYCLLP_KEEP_RCP
-#define PYCLLP_KEEP_RCP 1      // 1/x and 1/z of the point are computed once per iteration and kept (12 VGPRs at (32, 96)) instead of
-#endif                         // being re-derived in each of the three places that need them (round 3: 18 -> 6 fast_rcp per LP-iteration)
-#ifndef PYCLLP_CARRY_RHO
-#define PYCLLP_CARRY_RHO 1     // rho = b - A x is CARRIED from step to step (rho+ = rho - theta A dx, both factors exist anyway) instead of
-#endif                         // being re-formed inside the Gram pass: -32 FMAs, -16 LDS reads, -4 shuffles per LP-iteration (round 3)
 #ifndef PYCLLP_WPB
 #define PYCLLP_WPB 8        // waves per workgroup of the group kernel (LDS at (32,96) slack-aware: 8 x 17.5 KB + 16.8 KB)
 #endif
@@ -155,8 +123,8 @@ struct GWave {
     static constexpr int G = G_::G, NCG = G_::NCG, NCD = G_::NCD, ND = G_::ND, JB = G_::JB, KS = G_::KS, AS = G_::AS, MS = G_::MS;
 
     const double* Aimg;   // LDS: row-major A, row stride AS
-    static constexpr bool COLB = PYCLLP_COLBASE && MP == 32 && NP <= 96;   // (at NP = 128 the sixteen registers are not to spare)
-    static constexpr bool ROWB = PYCLLP_ROWBASE && COLB && SL;     // (the variants without the identity tail carry one more N-vector register each: no room)
+    static constexpr bool COLB = MP == 32 && NP <= 96;   // (at NP = 128 the sixteen registers are not to spare)
+    static constexpr bool ROWB = COLB && SL;     // (the variants without the identity tail carry one more N-vector register each: no room)
     unsigned rb[ROWB ? 16 : 1];   // ... and of the sixteen 16-byte pairs of the lane's own ROW (load_own_row), swizzle included
     unsigned xb[COLB ? 16 : 1];   // MP = 32: LDS byte address of slab entry (row c, column gl), c < 16, swizzle included: entry (k, gl) of the
                           // factor's column layout is at xb[k & 15] + 256 (k & 16).  Kernel-lifetime values (16 registers, which the kernel
@@ -197,7 +165,9 @@ struct GWave {
     // out_q = sum_i A[i][gl + MP q] * u_i   (u: lane = row of own group)  -- A'u
     // Software pipelined by hand: rows are fetched in batches of RB into two register buffers; a batch is pinned
     // (waited for) only after the next batch's loads have been issued.  Left alone, the scheduler sinks every LDS
-    // read next to its FMA and the loop runs at LDS latency.
+    // read next to its FMA and the loop runs at LDS latency.  The partial sums are pinned after every batch too: left free,
+    // the scheduler may sink every FMA below the last batch's loads and keep the whole image of A live at once (the
+    // predictor-corrector kernel spilled 96-433 registers that way; 6.06 -> 5.45 ms at (32, 96)).
     __device__ __forceinline__ void At_times(double u, double (&out)[NCG]) const {
         const int g = ogl();
         stage[grp * MP + g] = u;
@@ -221,7 +191,7 @@ struct GWave {
     asm volatile("" : "+v"(tok));                                                               \
     _Pragma("unroll") for (int ii = 0; ii < RB; ii++)                                           \
         _Pragma("unroll") for (int q = 0; q < NCD; q++) out[q] = fma(A_[ii][q], U_[ii], out[q]); \
-    if (PYCLLP_AT_PIN_SUMS) { _Pragma("unroll") for (int q = 0; q < NCD; q++) asm volatile("" : "+v"(out[q])); }
+    _Pragma("unroll") for (int q = 0; q < NCD; q++) asm volatile("" : "+v"(out[q]));
 #pragma unroll
         for (int q = 0; q < NCG; q++) out[q] = 0.0;
         if (SL) out[NCG - 1] = u;   // slack column i of lane gl = i: (A'u)_slack = u_i (u is 0 in padded rows)
@@ -295,9 +265,6 @@ struct GWave {
 #pragma unroll
             for (int J = 0; J < JB; J++) acc[I][J] = (double4_t){0.0, 0.0, 0.0, 0.0};
         }
-#if PYCLLP_GRAM_PRIO
-        __builtin_amdgcn_s_setprio(PYCLLP_GRAM_PRIO);
-#endif
         const double* px = stage + kg * KS;
         const double* pd = stage + ND + kg * KS;
         const double* pt = stage + 2 * ND + kg * KS;
@@ -324,9 +291,6 @@ struct GWave {
                         acc[I][J] = __builtin_amdgcn_mfma_f64_16x16x4f64(ad[I], a[J], acc[I][J], 0, 0, 0);
             }
         }
-#if PYCLLP_GRAM_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         double* sg = slab0 + g * G_::SLAB;
         int lo_ = lane;                       // opaque copy: see ogl()
         asm volatile("" : "+v"(lo_));
@@ -398,98 +362,28 @@ struct GWave {
         return __hiloint2double(b[0], a[0]);
     }
 
-    // Round 3: the sweep is SOFTWARE-PIPELINED (chain_asm.inc): the pivot of column j+1 -- broadcast, max with the floor,
-    // v_rcp_f64 and two Newton steps, a chain of ~8 dependent DP operations -- is taken as soon as column j's update of its
-    // entry is done and runs between the remaining (independent) trailing updates of column j, instead of standing, fully
-    // exposed, in front of column j+1's updates.  Same operations on the same operands, i.e. the same rounding; only the
-    // order of independent instructions changes.  MEASURED (profiles/r03/dense_factor_pipelined.txt): all parity tests green,
-    // 6.314 ms per 65 536 LPs against 6.26 ms in the round-2 order -- with two waves per SIMD the other wave already fills the
-    // chain's latency; the phase is bound by the FP64 pipe (the 64-bit DPP FMA issues at half rate), not by that latency.
-    // A template parameter (default PYCLLP_PIPE_FACTOR = 0).  hsd_group_kernel<32, ...> used it while it ran ONE wave per SIMD
-    // (9.67 -> 9.51 ms per 65 536 LPs); at two waves per SIMD (round 3, DESIGN 13.5) it is worth nothing there either.
-    template <bool RELF = false, bool PIPE = (PYCLLP_PIPE_FACTOR != 0)>
+    // The sweep takes "below the pivot" / "the pivot's lane" as EXEC masks (wave_common.h, round 3).  Tried and removed:
+    // software-pipelining the next pivot's chain into column j's updates (6.314 against 6.26 ms per 65 536 LPs: with two waves
+    // per SIMD the other wave already hides that latency, profiles/r03/dense_factor_pipelined.txt), and handing the top DPP
+    // row's entries to the bottom row through LDS instead of v_permlane16_swap (6.02-6.09 against 5.94 ms).
+    template <bool RELF = false>
     __device__ __forceinline__ bool factor_dpp(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
                                                const double* fl = nullptr) const {
         rdiag = 1.0;
-        bool viol = false;
         // the sweep is a chain of dependent operations: s_setprio lets it go first when both waves of the SIMD are ready.
         // Measured: 6.82 -> 6.75 ms for the HSD kernel (RELF); for the plain kernel nothing alone (5.93-5.95 ms at levels 0, 2, 3),
         // 5.93 -> 5.91 ms together with the same level inside the substitution (PYCLLP_SOLVE_PRIO); raising the priority of the
         // Gram product's MFMA loop instead costs 0.3-0.6 %.
         constexpr int PRIO_ = RELF ? PYCLLP_FACTOR_PRIO_HSD : PYCLLP_FACTOR_PRIO;
         if constexpr (PRIO_ != 0) __builtin_amdgcn_s_setprio(PRIO_);
-        const int go = ogl();      // the row masks below are derived from an opaque copy: as invariants of the whole solve they
-                                   // are hoisted into 64 SGPRs and spilled to VGPR lanes (v_writelane / v_readlane pairs)
-        if constexpr (PIPE) {
-        double (&Wt)[16] = *reinterpret_cast<double (*)[16]>(&W[0]);
-        double src = (MP == 32) ? top_row_of(W[0]) : W[0];
-        double aD, rD;
-        {
-            const double piv = bcast64<0>(src);
-            aD = fmax(fabs(piv), RELF ? fl[0] : floor_);
-            rD = fast_rcp(aD);
-        }
-        static_for<0, MP>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            const double u = W[j];
-            const bool below = go > j;
-            viol = viol || (live && below && (u * u > beta2 * aD));
-            const double nli = below ? -(u * rD) : 0.0;
-            rdiag = (go == j) ? rD : rdiag;
-            asm volatile("" : "+v"(rdiag));   // select now: deferred, the selects keep every reciprocal + mask alive
-            if constexpr (j + 1 < MP) {
-                const double fn = RELF ? fl[j + 1] : floor_;     // floor of the next pivot
-                double aDn, rDn;
-                if constexpr (MP == 16) {
-                    chain_step_pipe<j>(Wt, u, nli, fn, aDn, rDn);
-                } else {
-                    double (&Wb)[16] = *reinterpret_cast<double (*)[16]>(&W[16]);
-                    if constexpr (j < 15) {
-                        chain_one<j + 1>(Wt[j + 1], src, nli);              // column j+1 first: its entry is final after this
-                        const double srcn = top_row_of(Wt[j + 1]);
-                        chain32_top_pipe<j + 1>(Wb, u, nli, fn, srcn, aDn, rDn);   // bottom-right block + the next pivot's chain
-                        if constexpr (j < 14) chain_rest<j>(Wt, src, nli);
-                        src = srcn;
-                    } else if constexpr (j == 15) {
-                        chain32_mid_pipe(Wb, u, nli, fn, aDn, rDn);
-                    } else {
-                        chain_step_pipe<j - 16>(Wb, u, nli, fn, aDn, rDn);
-                    }
-                }
-                aD = aDn; rD = rDn;
-            }
-            W[j] = -nli;
-        });
-        } else {
-#if PYCLLP_EXEC_FACTOR
+        const int go = ogl();      // unused, but this opaque copy shapes the register allocation of the (32, .) kernels
+        (void)go;
         double ymax = 0.0;         // running max of u^2 / D over the lanes below the pivots: the guard bites iff it exceeds beta^2
-#if PYCLLP_TOPROW_LDS
-        // MP = 32: the top DPP row's column entries reach the bottom row through LDS (a store as soon as the column is final,
-        // load + wait behind the bottom block's sixteen FMAs) instead of two v_permlane16_swap + four moves per column: the
-        // vector issue port is what this kernel is bound by (DESIGN 13.4), the LDS pipe has room -- 96 vector instructions
-        // fewer per sweep.  The slot is the second half of the wave's staging area (the HSD kernel's floors sit in the first).
-        // MEASURED: bit-identical results, but 6.02-6.09 ms against 5.94 ms -- the load's latency in front of every pivot costs
-        // more than the 96 instructions (two waves per SIMD do not hide it all).  Off.
-        unsigned a_own = 0, a_top = 0;
-        double srcn = 0.0;
-        if constexpr (MP == 32) {
-            int lo_ = lane;
-            asm volatile("" : "+v"(lo_));
-            a_own = lds_addr(stage + 64) + 8u * (unsigned)lo_;
-            a_top = lds_addr(stage + 64) + 8u * (unsigned)(lo_ & ~16);
-            lds_put64(a_own, W[0]);
-            srcn = lds_get64(a_top);
-        }
-#endif
         static_for<0, MP>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             const double u = W[j];
             double src = u;        // the u whose lane j % 16 is the pivot row as seen from this lane's DPP row
-#if PYCLLP_TOPROW_LDS
-            if constexpr (MP == 32 && j < 16) src = srcn;
-#else
             if constexpr (MP == 32 && j < 16) src = top_row_of(u);
-#endif
             const double piv = bcast64<j % 16>(src);
             const double aD = RELF ? max_abs<false>(piv, fl[j]) : max_abs<true>(piv, floor_);
             const double rD = fast_rcp(aD);
@@ -504,51 +398,15 @@ struct GWave {
                 chain_step_exec<j, MB_, MB_, 1, ONE_, ONE_>(W, 0.0, rD, l, ymax, rdiag);
             } else if constexpr (j < 16) {
                 chain_step_exec<j, MB_, MB_, 0, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[0]), src, rD, l, ymax, rdiag);
-#if PYCLLP_TOPROW_LDS
-                if constexpr (j + 1 < 16) lds_put64(a_own, W[j + 1]);      // column j + 1 is final
-#endif
-#if PYCLLP_BOTTOM_UNMASKED
                 // the bottom-right block's columns, in ALL lanes: what the top row's lanes hold in W[16..31] is never read (upper
                 // triangle; overwritten with 0 when its column comes), so the EXEC mask of rounds 2-3 only cost its switches
                 chain_all_neg(*reinterpret_cast<double (*)[16]>(&W[16]), W[j], l);
-#else
-                chain_all_exec<0xFFFF0000u, 0xFFFF0000u>(*reinterpret_cast<double (*)[16]>(&W[16]), W[j], l);   // bottom rows only
-#endif
-#if PYCLLP_TOPROW_LDS
-                if constexpr (j + 1 < 16) srcn = lds_get64(a_top);
-#endif
             } else {
                 chain_step_exec<j - 16, MB_, MB_, 1, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[16]), 0.0, rD, l, ymax, rdiag);
             }
             W[j] = l;
         });
-        viol = live && (ymax > beta2);
-#else
-        static_for<0, MP>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            const double u = W[j];
-            double src = u;        // the u whose lane j % 16 is the pivot row as seen from this lane's DPP row
-            if constexpr (MP == 32 && j < 16) src = top_row_of(u);
-            const double piv = bcast64<j % 16>(src);
-            const double aD = fmax(fabs(piv), RELF ? fl[j] : floor_);
-            const bool below = go > j;
-            viol = viol || (live && below && (u * u > beta2 * aD));
-            const double rD = fast_rcp(aD);
-            const double nli = below ? -(u * rD) : 0.0;
-            rdiag = (go == j) ? rD : rdiag;
-            asm volatile("" : "+v"(rdiag));   // select now: deferred, the selects keep every reciprocal + mask alive
-            if constexpr (MP == 16) {
-                if constexpr (j < 15) chain_step<j>(W, src, nli);
-            } else if constexpr (j < 16) {
-                if constexpr (j < 15) chain_step<j>(*reinterpret_cast<double (*)[16]>(&W[0]), src, nli);
-                chain_step<-1>(*reinterpret_cast<double (*)[16]>(&W[16]), u, nli);
-            } else {
-                if constexpr (j < 31) chain_step<j - 16>(*reinterpret_cast<double (*)[16]>(&W[16]), u, nli);
-            }
-            W[j] = -nli;
-        });
-#endif
-        }
+        const bool viol = live && (ymax > beta2);
         if constexpr (PRIO_ != 0) __builtin_amdgcn_s_setprio(0);
         if constexpr (COLB) {
 #pragma unroll
@@ -882,21 +740,16 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
 
         // ---- d = x/z, t = c - A'y + mu/x ----
         double Ax = 0.0, Adt = 0.0;
-#if PYCLLP_KEEP_RCP
+        // 1/x and 1/z are computed once per iteration and kept (12 VGPRs at (32, 96)) instead of being re-derived in each place
+        // that needs them (round 3: 18 -> 6 fast_rcp per LP-iteration)
         double rxk[NCG], rzk[NCG];
 #pragma unroll
         for (int q = 0; q < NCG; q++) { rxk[q] = fast_rcp(x[q]); rzk[q] = fast_rcp(z[q]); }
-#define RCP_X(q) rxk[q]
-#define RCP_Z(q) rzk[q]
-#else
-#define RCP_X(q) fast_rcp(x[q])
-#define RCP_Z(q) fast_rcp(z[q])
-#endif
         auto do_gram = [&](double& Ax_, double& Adt_) {
             double d[NCG], t[NCG];
 #pragma unroll
             for (int q = 0; q < NCG; q++) {
-                const double rx = RCP_X(q), rz = RCP_Z(q);
+                const double rx = rxk[q], rz = rzk[q];
                 d[q] = ok[q] ? x[q] * rz : 0.0;
                 t[q] = ok[q] ? c[q] - v[q] + mu * rx : 0.0;
             }
@@ -904,8 +757,9 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
 #pragma unroll 1
             for (int g = 0; g < G; g++) {
                 if (__shfl((int)live, g * MP, WAVE) == 0) continue;      // an idle lane group (small batch, or the batch's tail)
-                // (a slot that carries rho -- every pass but an LP's first -- needs no A x from the Gram pass)
-                const bool carried = PYCLLP_CARRY_RHO && __shfl((int)have_pred, g * MP, WAVE) != 0;
+                // (a slot that carries rho -- every pass but an LP's first -- needs no A x from the Gram pass: -32 FMAs,
+                // -16 LDS reads, -4 shuffles per LP-iteration, round 3)
+                const bool carried = __shfl((int)have_pred, g * MP, WAVE) != 0;
                 if (grp == g) {
 #pragma unroll
                     for (int q = 0; q < NCD; q++) {
@@ -933,7 +787,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         };
         do_gram(Ax, Adt);
         STAMP(2)
-        const double rho = (PYCLLP_CARRY_RHO && have_pred) ? rho_pred : b - Ax;
+        const double rho = have_pred ? rho_pred : b - Ax;
         const double rhs = Adt - rho;
         double rdiag;
         {
@@ -969,7 +823,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             double tha = 0.0;
 #pragma unroll
             for (int q = 0; q < NCG; q++) {
-                const double rx = RCP_X(q), rz = RCP_Z(q);
+                const double rx = rxk[q], rz = rzk[q];
                 const double dq = ok[q] ? x[q] * rz : 0.0;
                 const double ta = ok[q] ? c[q] - v[q] : 0.0;
                 dxa[q] = (ta - wva[q]) * dq;
@@ -986,7 +840,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             mu = sg * sg * sg * gam / (double)n;
 #pragma unroll
             for (int q = 0; q < NCG; q++) {
-                const double rx = RCP_X(q), rz = RCP_Z(q);
+                const double rx = rxk[q], rz = rzk[q];
                 cor[q] = ok[q] ? mu - dxa[q] * dza[q] : 0.0;
                 const double tq = ok[q] ? c[q] - v[q] + cor[q] * rx : 0.0;
                 dt[q] = (ok[q] ? x[q] * rz : 0.0) * tq;
@@ -1000,7 +854,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         // d and t are recomputed (bit-identical) rather than kept alive across the factorisation: 12 VGPRs
 #pragma unroll
         for (int q = 0; q < NCG; q++) {
-            const double rx = RCP_X(q), rz = RCP_Z(q);
+            const double rx = rxk[q], rz = rzk[q];
             d[q] = ok[q] ? x[q] * rz : 0.0;
             const double tq = ok[q] ? c[q] - v[q] + (PC ? cor[q] : mu) * rx : 0.0;
             dx[q] = (tq - wv[q]) * d[q];
@@ -1049,7 +903,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             double th = 0.0;
 #pragma unroll
             for (int q = 0; q < NCG; q++) {
-                const double rx = RCP_X(q), rz = RCP_Z(q);
+                const double rx = rxk[q], rz = rzk[q];
                 dz[q] = ok[q] ? ((PC ? cor[q] : mu) - z[q] * dx[q]) * rx - z[q] : 0.0;
                 if (ok[q]) th = fmax(th, fmax(-dz[q] * rz, -dx[q] * rx));
             }
@@ -1070,8 +924,6 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         }
         STAMP(8)
         if (fin && live) finalize(stat);
-#undef RCP_X
-#undef RCP_Z
     }
     STAMP_FLUSH(o, blockIdx.x * wpb + wave)
 }

@@ -17,13 +17,6 @@
 #ifndef PYCLLP_HSD_AT_RB
 #define PYCLLP_HSD_AT_RB 4   // rows of A per batch of the pipelined two-vector A'u
 #endif
-#ifndef PYCLLP_HSD_PIPE
-#define PYCLLP_HSD_PIPE 0        // 1: software-pipelined pivot chain in the factorisation (GWave::factor_dpp); paid (1.7 %) only
-                                 //    while this kernel ran one wave per SIMD
-#endif
-#ifndef PYCLLP_HSD_SEQ_SOLVE
-#define PYCLLP_HSD_SEQ_SOLVE 0   // 1: the two right-hand sides are substituted one after the other (fewer live registers)
-#endif
 template <int MP, int NP, bool SL>
 struct GWaveH : GWave<MP, NP, SL> {
     using Base = GWave<MP, NP, SL>;
@@ -409,8 +402,8 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             const double myfloor = pf * pf * fabs(diag);
             fl[go] = myfloor;
             wave_lds_sync();
-            // (PYCLLP_HSD_PIPE: the software-pipelined sweep paid while this kernel ran one wave per SIMD; see GWave::factor_dpp)
-            const bool redo = w.template factor_dpp<true, (PYCLLP_HSD_PIPE != 0)>(W, beta2, 0.0, live, rdiag, fl);
+            // (a software-pipelined sweep paid 1.7 % here only while this kernel ran one wave per SIMD; see GWave::factor_dpp)
+            const bool redo = w.template factor_dpp<true>(W, beta2, 0.0, live, rdiag, fl);
             if (redo || (o.flags & PYCLLP_FLAG_FORCE_GUARD_PATH)) {
                 double t1, t2;
                 do_gram(t1, t2);
@@ -419,12 +412,7 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 rdiag = w.factor_guarded_inplace(rowok, beta2, 0.0, fl);
             }
         }
-#if PYCLLP_HSD_SEQ_SOLVE
-        pv = w.fwd_back(pv, rdiag);
-        qv = w.fwd_back(qv, rdiag);
-#else
         w.fwd_back2(pv, qv, rdiag);
-#endif
         double ap[NCG], aq[NCG], dx[NCG], d[NCG], wv[NCG];
         w.At_times2(pv, qv, ap, aq);
         double dsum = 0.0, nsum = 0.0;

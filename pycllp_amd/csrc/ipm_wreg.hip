@@ -55,29 +55,10 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 // cycles per iteration, 42 % of them in the pivot chains waiting for reloads).  Round 3, with the rest of the kernel no longer
 // under that pressure: the block is simply the MFMA's own result.  It stays where the matrix pipe wrote it, later MFMAs take it
 // as their B operand from the accumulator file directly, and the ~700 v_accvgpr_read / _write per iteration that moved every
-// block out of the accumulators and back are gone (PYCLLP_PARK_ASM = 1 restores the asm form): 378.5 -> 391.5 k LPs/s.
-#ifndef PYCLLP_WINV_FUSED
-#define PYCLLP_WINV_FUSED 1
-#endif
-#ifndef PYCLLP_PARK_ASM
-#define PYCLLP_PARK_ASM 0
-#endif
-#if PYCLLP_PARK_ASM
-struct PBlk { int h[8]; };
-__device__ __forceinline__ void park(PBlk& p, const double4_t& v) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int lo = __double2loint(v[r]), hi = __double2hiint(v[r]);
-        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(p.h[2 * r]) : "v"(lo));
-        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(p.h[2 * r + 1]) : "v"(hi));
-    }
-}
-__device__ __forceinline__ double unpark(const PBlk& p, int r) { return __hiloint2double(p.h[2 * r + 1], p.h[2 * r]); }
-#else
+// block out of the accumulators and back are gone: 378.5 -> 391.5 k LPs/s.
 struct PBlk { double4_t d; };
 __device__ __forceinline__ void park(PBlk& p, const double4_t& v) { p.d = v; }
 __device__ __forceinline__ double unpark(const PBlk& p, int r) { return p.d[r]; }
-#endif
 
 // stage proper: N-vector staging; during factor/solve t, x and z parked at 0, NP, 2 NP and the stride-17 tile of the current
 // diagonal block behind them
@@ -769,7 +750,6 @@ struct WReg {
             wave_lds_sync();
             STAMP(2)
             double Wd[16], Ws[4];
-            [[maybe_unused]] double Ld[16];
 #pragma unroll
             for (int s = 0; s < 4; s++) Ws[s] = (c16 == 4 * s + q) ? 1.0 : 0.0;
             {
@@ -800,22 +780,16 @@ struct WReg {
                     if constexpr (RELF) chain_step_pipe_relf<j>(Wd, u, nli, floor_, myf, aDn, rDn);
                     else chain_step_pipe<j>(Wd, u, nli, floor_, aDn, rDn);
                     rD = rDn;
-                    // PYCLLP_WINV_FUSED: step j of W = L_KK^-1 (A-operand layout: Ws[s] = W[row c16][column 4s + q]; nli = -L[.][j])
-                    // rides along with the sweep instead of running as 15 steps after it: its one to four FMAs fill the tail of the
-                    // reciprocal chain that the late columns' few trailing updates leave exposed (+0.5 %, 389.4 -> 391.5 k LPs/s)
-                    if constexpr (PYCLLP_WINV_FUSED) winv_step<j>(Ws, nli); else Ld[j] = nli;
+                    // step j of W = L_KK^-1 (A-operand layout: Ws[s] = W[row c16][column 4s + q]; nli = -L[.][j]) rides along
+                    // with the sweep instead of running as 15 steps after it: its one to four FMAs fill the tail of the reciprocal
+                    // chain that the late columns' few trailing updates leave exposed (+0.5 %, 389.4 -> 391.5 k LPs/s)
+                    winv_step<j>(Ws, nli);
                 }
             });
             if (q == 0) rdv_()[16 * K + c16] = rdiag;
             STAMP(4)
             pin();
-            // ---- W = L_KK^-1 in the A-operand layout: Ws[s] = W[row c16][column 4s + q]; packed copy to LDS (Ld holds -L) ----
-            if constexpr (!PYCLLP_WINV_FUSED) {
-                static_for<0, 15>([&](auto jc) {
-                    constexpr int j = decltype(jc)::value;
-                    winv_step<j>(Ws, Ld[j]);
-                });
-            }
+            // ---- W = L_KK^-1 in the A-operand layout (Ws[s] = W[row c16][column 4s + q], formed in the sweep): packed copy to LDS ----
             // (entries on and above the diagonal go to spare doubles of the slot: one store each, no branch; [136] and [137]
             // get the constants 1 and 0 that solve() reads for the diagonal and the upper triangle of W)
 #pragma unroll

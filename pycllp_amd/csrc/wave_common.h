@@ -156,35 +156,9 @@ __device__ __forceinline__ double bcast64(double v) {
     asm volatile("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:" DPP_STR(%2) " row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(v), "n"(K));
     return r;
 }
-// Pivot step J of the 16-step chain: Wd[k] += (u of lane k of the row) * nli for k = J+1 .. 15, one fused 64-bit DPP FMA
-// each (J = -1: all sixteen, k = 0 .. 15).  ONE asm statement per step, with a leading s_nop: the compiler may have produced u (or moved it between register
-// files) in the instruction just before, and the hazard recogniser does not look inside inline asm.
-template <int J>
-__device__ __forceinline__ void chain_step(double (&Wd)[16], double u, double nli) {
-    asm volatile("s_nop 1\n\t"
-                 ".if 0 > %18\n\tv_fmac_f64_dpp %0, %16, %17 row_newbcast:0 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 1 > %18\n\tv_fmac_f64_dpp %1, %16, %17 row_newbcast:1 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 2 > %18\n\tv_fmac_f64_dpp %2, %16, %17 row_newbcast:2 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 3 > %18\n\tv_fmac_f64_dpp %3, %16, %17 row_newbcast:3 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 4 > %18\n\tv_fmac_f64_dpp %4, %16, %17 row_newbcast:4 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 5 > %18\n\tv_fmac_f64_dpp %5, %16, %17 row_newbcast:5 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 6 > %18\n\tv_fmac_f64_dpp %6, %16, %17 row_newbcast:6 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 7 > %18\n\tv_fmac_f64_dpp %7, %16, %17 row_newbcast:7 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 8 > %18\n\tv_fmac_f64_dpp %8, %16, %17 row_newbcast:8 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 9 > %18\n\tv_fmac_f64_dpp %9, %16, %17 row_newbcast:9 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 10 > %18\n\tv_fmac_f64_dpp %10, %16, %17 row_newbcast:10 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 11 > %18\n\tv_fmac_f64_dpp %11, %16, %17 row_newbcast:11 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 12 > %18\n\tv_fmac_f64_dpp %12, %16, %17 row_newbcast:12 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 13 > %18\n\tv_fmac_f64_dpp %13, %16, %17 row_newbcast:13 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 14 > %18\n\tv_fmac_f64_dpp %14, %16, %17 row_newbcast:14 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 ".if 15 > %18\n\tv_fmac_f64_dpp %15, %16, %17 row_newbcast:15 row_mask:0xf bank_mask:0xf\n.endif\n\t"
-                 : "+v"(Wd[0]), "+v"(Wd[1]), "+v"(Wd[2]), "+v"(Wd[3]), "+v"(Wd[4]), "+v"(Wd[5]), "+v"(Wd[6]), "+v"(Wd[7]), "+v"(Wd[8]), "+v"(Wd[9]), "+v"(Wd[10]), "+v"(Wd[11]), "+v"(Wd[12]), "+v"(Wd[13]), "+v"(Wd[14]), "+v"(Wd[15])
-                 : "v"(u), "v"(nli), "n"(J));
-}
-
 #include "chain_asm.inc"
 
-// ---- the same steps under an EXEC mask (ipm_group.inc, round 3) ----
+// ---- pivot steps under an EXEC mask (ipm_group.inc, round 3) ----
 // In the lane-group kernel the mask "lanes below the pivot" and the one-hot "the pivot's lane" are compile-time constants per
 // column; taking them as EXEC masks replaces, per column, the compare + two selects that zero the multiplier of the lanes
 // on and above the pivot, the compare + two selects that pick the pivot's reciprocal, and the two multiplies + compare of the
@@ -241,40 +215,6 @@ __device__ __forceinline__ void chain_step_exec(double (&Wd)[16], double src, do
     CHAIN_COL_CASE(0) CHAIN_COL_CASE(1) CHAIN_COL_CASE(2) CHAIN_COL_CASE(3) CHAIN_COL_CASE(4) CHAIN_COL_CASE(5) CHAIN_COL_CASE(6) CHAIN_COL_CASE(7)
     CHAIN_COL_CASE(8) CHAIN_COL_CASE(9) CHAIN_COL_CASE(10) CHAIN_COL_CASE(11) CHAIN_COL_CASE(12) CHAIN_COL_CASE(13) CHAIN_COL_CASE(14) CHAIN_COL_CASE(15)
 #undef CHAIN_COL_CASE
-}
-// Wd[k] -= (src of lane k) * l, k = 0 .. 15, in the lanes of the mask (l is already masked; the mask only saves the work)
-template <unsigned MLO, unsigned MHI>
-__device__ __forceinline__ void chain_all_exec(double (&Wd)[16], double src, double l) {
-    unsigned long long save;
-    asm volatile("s_mov_b64 %16, exec\n\ts_mov_b32 exec_lo, %19\n\ts_mov_b32 exec_hi, %20\n\ts_nop 1\n\t"
-                 "v_fmac_f64_dpp %0, %17, -%18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %1, %17, -%18 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %2, %17, -%18 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %3, %17, -%18 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %4, %17, -%18 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %5, %17, -%18 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %6, %17, -%18 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %7, %17, -%18 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %8, %17, -%18 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %9, %17, -%18 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %10, %17, -%18 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %11, %17, -%18 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %12, %17, -%18 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %13, %17, -%18 row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %14, %17, -%18 row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_fmac_f64_dpp %15, %17, -%18 row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_mov_b64 exec, %16"
-                 : "+v"(Wd[0]), "+v"(Wd[1]), "+v"(Wd[2]), "+v"(Wd[3]), "+v"(Wd[4]), "+v"(Wd[5]), "+v"(Wd[6]), "+v"(Wd[7]), "+v"(Wd[8]), "+v"(Wd[9]), "+v"(Wd[10]), "+v"(Wd[11]), "+v"(Wd[12]), "+v"(Wd[13]), "+v"(Wd[14]), "+v"(Wd[15]),
-                   "=&s"(save)
-                 : "v"(src), "v"(l), "n"(MLO), "n"(MHI));
-}
-// one 64-bit value through LDS, as two statements: the store (no result) and, later, load + wait in ONE statement, so that the
-// compiler never sees a register whose load is still in flight.  DS operations of a wavefront execute in order.
-__device__ __forceinline__ void lds_put64(unsigned a, double v) { asm volatile("ds_write_b64 %0, %1" : : "v"(a), "v"(v) : "memory"); }
-__device__ __forceinline__ double lds_get64(unsigned a) {
-    double r;
-    asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(a) : "memory");
-    return r;
 }
 // Wd[k] -= (src of lane k) * l, k = 0 .. 15, in ALL lanes (no EXEC mask: for callers whose other lanes hold don't-care values)
 __device__ __forceinline__ void chain_all_neg(double (&Wd)[16], double src, double l) {

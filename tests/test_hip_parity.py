@@ -810,9 +810,9 @@ def test_hsd_shapes_up_to_the_maximum(m, n):
         assert rel_err(s.primal_obj[opt], r["pobj"][opt]).max() < 1e-8
 
 
-def test_first_generation_kernel_is_not_in_the_default_build():
-    """the round-1 wave-per-LP kernel is compiled only into diagnostic builds (-DPYCLLP_FIRST_GEN); the
-    shipped library answers its flag with PYCLLP_E_UNSUPPORTED -> NotImplementedError, never with a silent other path."""
+def test_first_generation_kernel_flag_is_refused():
+    """the round-1 wave-per-LP kernel has been removed; the library answers its flag with
+    PYCLLP_E_UNSUPPORTED -> NotImplementedError, never with a silent other path."""
     A, b, c = problems.random_dense_arrays(8, 12, 4, seed=1)
     with pytest.raises(NotImplementedError):
         solve_arrays(A, b, c, hsd=False, flags=2)
