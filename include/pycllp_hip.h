@@ -204,6 +204,23 @@ int pycllp_hip_sparse_solve_batch(pycllp_hip_sparse *handle, long B, const doubl
                                   const double *c_dev, double *x_dev, double *y_dev, double *z_dev, double *pobj_dev,
                                   double *dobj_dev, int *status_dev, int *iters_dev, const pycllp_hip_opts *opts,
                                   void *stream);
+/* Solve B LPs with UPPER BOUNDS, maximise c'x s.t. A x = b, 0 <= x <= u (the bounded equality form of a GeneralLP), on the
+ * register-resident one-LP-per-wavefront kernel (csrc/ipm_wreg_bounded.inc).  Any shared A of the handle with m <= 128 rows
+ * and n <= 512 columns that a variant of that kernel covers; no identity tail is required.  The arguments mean what they
+ * mean for pycllp_hip_dense_solve_bounded:
+ *   u_dev [B,n]      upper bounds: +inf = no bound, 0 = the column is fixed at 0 (it ends at x = 0)
+ *   s_dev [B,n]      (optional) duals of x <= u; z_dev (optional) those of x >= 0: A'y - z + s = c
+ *   dobj_dev [B]     b'y + u's over the finite u
+ * Option: PYCLLP_FLAG_AUTOSCALE (u scales with b).  An LP whose LDL' would need the Nocedal-Wright guard ends
+ * PYCLLP_STATUS_NUMERICAL.  The kernel's plan is built on the first call and kept with the handle.
+ * Returns PYCLLP_E_BADARG for a NULL handle, a NULL u_dev or any of the flags HSD, PREDCORR, WARM_START, WAVE_KERNEL,
+ * BLOCK_KERNEL, NO_SLACK_PATH, FORCE_GUARD_PATH (before the handle is read and before any HIP call), and
+ * PYCLLP_E_UNSUPPORTED when no variant of the bounded kernel or LDS plan covers A (m > 128 or n > 512 among them).
+ * Asynchronous on `stream`. */
+int pycllp_hip_sparse_solve_bounded(pycllp_hip_sparse *handle, long B, const double *b_dev, const double *c_dev,
+                                    const double *u_dev, double *x_dev, double *y_dev, double *z_dev, double *s_dev,
+                                    double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
+                                    const pycllp_hip_opts *opts, void *stream);
 /* One Newton step of the primal normal equations for B independent states with the sparse shared A: the reference's
  * stand-alone kernel sparse_solve_primal_normal (pycllp/cl/ldl.cl:656-712) as launched by its tests/test_ldl.py:276-361.
  * Arguments as pycllp_hip_dense_newton. */

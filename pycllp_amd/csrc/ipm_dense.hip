@@ -678,6 +678,8 @@ struct pycllp_hip_sparse {
     WregPlan* wreg_pa = nullptr;  // its per-problem-A plan (structure tables only), built by the first pycllp_hip_sparse_solve_batch
     WregPlan* last_plan = nullptr;
     bool wreg_pa_tried = false;
+    WregPlan* wreg_bd = nullptr;  // the plan of the bounded wave kernel (t and s behind every wave area), built by the first
+    bool wreg_bd_tried = false;   // pycllp_hip_sparse_solve_bounded (under info_mu)
     int max_lds = 0;
     std::vector<double> host_val; std::vector<int> host_ptr, host_col;   // host CSR copy (what a PA plan is built from)
 };
@@ -1195,6 +1197,53 @@ int pycllp_hip_sparse_solve_batch(pycllp_hip_sparse* h, long B, const double* Ad
     return sparse_solve_impl(h, B, Adata_dev, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, opts, stream);
 }
 
+int pycllp_hip_sparse_solve_bounded(pycllp_hip_sparse* h, long B, const double* b_dev, const double* c_dev, const double* u_dev,
+                                    double* x_dev, double* y_dev, double* z_dev, double* s_dev, double* pobj_dev, double* dobj_dev,
+                                    int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
+    // every argument check comes before the handle is read and before any HIP call
+    if (!h || B < 0 || !u_dev) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_bounded: bad argument");
+    const int flags = opts ? opts->flags : 0;
+    const int bad = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL | PYCLLP_FLAG_BLOCK_KERNEL |
+                    PYCLLP_FLAG_NO_SLACK_PATH | PYCLLP_FLAG_FORCE_GUARD_PATH;
+    if (flags & bad)
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, "
+                                        "NO_SLACK_PATH and FORCE_GUARD_PATH are not available with upper bounds");
+    if (B > 0 && (!b_dev || !c_dev || !x_dev || !status_dev))
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_bounded: bad argument");
+    if (h->big)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_bounded: the bounded wave kernel stops at m = 128, n = 512");
+    hipStream_t st = (hipStream_t)stream;
+    WregPlan* plan = nullptr;
+    {
+        std::lock_guard<std::mutex> g(h->info_mu);
+        if (!h->wreg_bd_tried) {
+            h->wreg_bd_tried = true;
+            WregPlan* wp = nullptr;
+            const int rc = wreg_plan_create_bounded(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(),
+                                                    h->host_col.data(), h->max_lds, st, &wp);
+            if (rc >= 1000) return set_err(rc - 1000, "wreg_plan_create_bounded");
+            h->wreg_bd = (rc == 0) ? wp : nullptr;
+        }
+        plan = h->wreg_bd;
+    }
+    if (!plan)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_bounded: no variant of the bounded wave kernel covers this A "
+                                             "(rows, columns, or its tables in LDS)");
+    if (B == 0) return 0;
+    DevOpts o = to_dev(opts);
+    int* qw = nullptr; unsigned sw = 0; int grid = 0;
+    hipError_t e = h->ring.acquire(st, &qw, &sw);
+    if (e == hipSuccess) {
+        e = wreg_launch_solve_bounded(plan, B, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev, status_dev,
+                                      iters_dev, qw, o, h->num_cu, st, &grid);
+        hipError_t er = h->ring.release(sw, st);
+        if (e == hipSuccess) e = er;
+    }
+    { std::lock_guard<std::mutex> g(h->info_mu); h->last_wreg = 1; h->last_plan = plan; h->grid = grid; }
+    if (e != hipSuccess) return set_err((int)e, "ipm_wreg_bounded_kernel launch");
+    return 0;
+}
+
 int pycllp_hip_sparse_newton(pycllp_hip_sparse* h, long B, const double* x_dev, const double* z_dev, const double* y_dev,
                              const double* b_dev, const double* c_dev, double mu, double* dy_dev, int* nrefine_dev,
                              const pycllp_hip_opts* opts, void* stream) {
@@ -1304,6 +1353,7 @@ void pycllp_hip_sparse_free(pycllp_hip_sparse* h) {
     h->ring.destroy();
     wreg_plan_free(h->wreg);
     wreg_plan_free(h->wreg_pa);
+    wreg_plan_free(h->wreg_bd);
     big_plan_free(h->big);
     delete h;
 }

@@ -1958,6 +1958,10 @@ __global__ void wreg_selftest_kernel(double* out) {
     out[512 + lane] = wmax(v);               // expect 64
 }
 
+#if WREG_PART == 6
+#include "ipm_wreg_bounded.inc"     // the kernel for LPs with upper bounds (seventh translation unit)
+#endif
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1970,6 +1974,7 @@ struct WregPlan {
     WregTab tab;
     int mb, nq;
     bool da = false, pa = false;
+    bool bd = false;      // the plan of the bounded kernel (wreg_plan_create_bounded): 2 NP more doubles per wave
     void* dev_blob;
 };
 
@@ -2096,18 +2101,51 @@ extern const WVariant kWVariantsPCPA[] = WVARIANTS_PCPA;
 extern const int kNumWVariantsPCPA = sizeof(kWVariantsPCPA) / sizeof(kWVariantsPCPA[0]);
 #endif
 #endif
+#if WREG_PART == 6
+// the bounded kernel (ipm_wreg_bounded.inc) on the table and dense-image geometries (seventh translation unit); the plan of
+// wreg_plan_create_bounded picks the first variant of the wanted kind that covers (m, n), as for the other kernels
+template <int MB, int NQ, bool DA>
+hipError_t do_solve_bounded(const WregTab& T, long B, const double* b, const double* c, const double* u, double* x, double* y,
+                            double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead, DevOpts o,
+                            int grid, hipStream_t st) {
+    hipError_t e = set_dyn_lds((const void*)ipm_wreg_bounded_kernel<MB, NQ, DA>, T.lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ipm_wreg_bounded_kernel<MB, NQ, DA>), dim3(grid), dim3(64 * T.wpb), T.lds_bytes, st, T, B, b, c, u, x, y, z,
+                       s, pobj, dobj, status, iters, qhead, o);
+    return hipGetLastError();
+}
+#define WVARIANT_BD(MB, NQ, DA) { MB, NQ, DA, do_solve_bounded<MB, NQ, DA> }
+#define WVARIANTS_BD { WVARIANT_BD(1, 4, false), WVARIANT_BD(2, 4, false), WVARIANT_BD(3, 4, false), WVARIANT_BD(4, 2, false), \
+                       WVARIANT_BD(4, 4, false), WVARIANT_BD(5, 6, false), WVARIANT_BD(6, 6, false), WVARIANT_BD(7, 6, false), \
+                       WVARIANT_BD(8, 4, false), WVARIANT_BD(8, 6, false), WVARIANT_BD(8, 8, false), \
+                       WVARIANT_BD(1, 4, true), WVARIANT_BD(2, 4, true), WVARIANT_BD(3, 4, true), WVARIANT_BD(4, 2, true), \
+                       WVARIANT_BD(4, 4, true), WVARIANT_BD(5, 4, true), WVARIANT_BD(6, 4, true), WVARIANT_BD(7, 4, true), \
+                       WVARIANT_BD(8, 4, true), WVARIANT_BD(8, 6, true) }
+#ifdef __HIP_DEVICE_COMPILE__
+namespace { [[maybe_unused]] const WBVariant kWVariantsBD_instantiate[] = WVARIANTS_BD; }
+#else
+extern const WBVariant kWVariantsBD[] = WVARIANTS_BD;
+extern const int kNumWVariantsBD = sizeof(kWVariantsBD) / sizeof(kWVariantsBD[0]);
+#endif
+#endif
 #if WREG_PART == 0
 
 // Plan with A as a dense image in LDS (no tables): for matrices whose Gram term list does not fit -- dense A's, e.g. the LPs
 // hip_dense_primal_normal hands over beyond m = 32.  The last m columns are kept out of the image when they are the
 // identity (equality form of a StandardLP).  Fewer than four waves per workgroup when that is what lets the image fit.
+// bd: the plan of the bounded kernel (its variants; t and s behind every wave area)
 static int wreg_plan_create_dense(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
-                                  hipStream_t st, WregPlan** out) {
-    int vi = -1;
-    for (int i = 0; i < kNumWVariants; i++)
-        if (kWVariants[i].da && !kWVariants[i].pa && m <= 16 * kWVariants[i].mb && n <= 64 * kWVariants[i].nq) { vi = i; break; }
-    if (vi < 0) return 1;
-    const int MB = kWVariants[vi].mb, NQ = kWVariants[vi].nq, MP = 16 * MB;
+                                  bool bd, hipStream_t st, WregPlan** out) {
+    int MB = 0, NQ = 0;
+    if (bd) {
+        for (int i = 0; i < kNumWVariantsBD; i++)
+            if (kWVariantsBD[i].da && m <= 16 * kWVariantsBD[i].mb && n <= 64 * kWVariantsBD[i].nq) { MB = kWVariantsBD[i].mb; NQ = kWVariantsBD[i].nq; break; }
+    } else {
+        for (int i = 0; i < kNumWVariants; i++)
+            if (kWVariants[i].da && !kWVariants[i].pa && m <= 16 * kWVariants[i].mb && n <= 64 * kWVariants[i].nq) { MB = kWVariants[i].mb; NQ = kWVariants[i].nq; break; }
+    }
+    if (!MB) return 1;
+    const int MP = 16 * MB;
     // identity tail?
     bool sl = n > m;
     std::vector<int> tail_cnt(sl ? m : 0, 0);
@@ -2120,7 +2158,7 @@ static int wreg_plan_create_dense(int m, int n, int nnz, const double* val, cons
     WregTab& T = P->tab;
     memset(&T, 0, sizeof(T));
     T.m = m; T.n = n; T.nnz = nnz; T.nd = nd; T.as = AS; T.img_rows = R;
-    T.wave_doubles = stage_d(NQ) + 64 * NQ + 5 * MP + MB * WL;
+    T.wave_doubles = stage_d(NQ) + 64 * NQ + 5 * MP + MB * WL + (bd ? 2 * 64 * NQ : 0);
     const size_t img_bytes = sizeof(double) * (size_t)R * AS;
     int wpb = 0;
     for (int w = 4; w >= 1; w--)
@@ -2137,31 +2175,43 @@ static int wreg_plan_create_dense(int m, int n, int nnz, const double* val, cons
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { if (P->dev_blob) (void)hipFree(P->dev_blob); delete P; return 1000 + (int)e; }
     T.img = (const double*)P->dev_blob;
-    P->mb = MB; P->nq = NQ; P->da = true;
+    P->mb = MB; P->nq = NQ; P->da = true; P->bd = bd;
     *out = P;
     return 0;
 }
 
 static int wreg_plan_create_tables(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
-                                   bool pa, hipStream_t st, WregPlan** out);
+                                   bool pa, bool bd, hipStream_t st, WregPlan** out);
 
 int wreg_plan_create(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds, int pa,
                      hipStream_t st, WregPlan** out) {
-    if (pa) return wreg_plan_create_tables(m, n, nnz, val, ptr, col, max_lds, true, st, out);
-    const int rc = wreg_plan_create_tables(m, n, nnz, val, ptr, col, max_lds, false, st, out);
+    if (pa) return wreg_plan_create_tables(m, n, nnz, val, ptr, col, max_lds, true, false, st, out);
+    const int rc = wreg_plan_create_tables(m, n, nnz, val, ptr, col, max_lds, false, false, st, out);
     if (rc != 1) return rc;
-    return wreg_plan_create_dense(m, n, nnz, val, ptr, col, max_lds, st, out);
+    return wreg_plan_create_dense(m, n, nnz, val, ptr, col, max_lds, false, st, out);
+}
+
+int wreg_plan_create_bounded(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
+                             hipStream_t st, WregPlan** out) {
+    const int rc = wreg_plan_create_tables(m, n, nnz, val, ptr, col, max_lds, false, true, st, out);
+    if (rc != 1) return rc;
+    return wreg_plan_create_dense(m, n, nnz, val, ptr, col, max_lds, true, st, out);
 }
 
 // pa: the structure-only tables of the per-problem-A variants (the values `val` only stand in where a table still wants
-// one; no kernel of those variants reads them)
+// one; no kernel of those variants reads them).  bd: the plan of the bounded kernel (its variants; t and s behind every wave
+// area, fewer waves per workgroup where that is what lets the tables fit)
 static int wreg_plan_create_tables(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
-                                   bool pa, hipStream_t st, WregPlan** out) {
-    int vi = -1;
-    for (int i = 0; i < kNumWVariants; i++)
-        if (!kWVariants[i].da && kWVariants[i].pa == pa && m <= 16 * kWVariants[i].mb && n <= 64 * kWVariants[i].nq) { vi = i; break; }
-    if (vi < 0 || nnz >= 65535) return 1;
-    const int MB = kWVariants[vi].mb, NQ = kWVariants[vi].nq;
+                                   bool pa, bool bd, hipStream_t st, WregPlan** out) {
+    int MB = 0, NQ = 0;
+    if (bd) {
+        for (int i = 0; i < kNumWVariantsBD; i++)
+            if (!kWVariantsBD[i].da && m <= 16 * kWVariantsBD[i].mb && n <= 64 * kWVariantsBD[i].nq) { MB = kWVariantsBD[i].mb; NQ = kWVariantsBD[i].nq; break; }
+    } else {
+        for (int i = 0; i < kNumWVariants; i++)
+            if (!kWVariants[i].da && kWVariants[i].pa == pa && m <= 16 * kWVariants[i].mb && n <= 64 * kWVariants[i].nq) { MB = kWVariants[i].mb; NQ = kWVariants[i].nq; break; }
+    }
+    if (!MB || nnz >= 65535) return 1;
     const int MP = 16 * MB, MPL = 64 * ((MP + 63) / 64), NP = 64 * NQ;
     WregPlan* P = new WregPlan();
     WregTab& T = P->tab;
@@ -2292,7 +2342,7 @@ static int wreg_plan_create_tables(int m, int n, int nnz, const double* val, con
     // workgroup as the LDS takes (three at config 5's structure: 3 x 37.6 KB + 22 KB of structure tables)
     T.pa = pa ? 1 : 0;
     T.nnzp = pa ? ((nnz + 1 + 1) & ~1) : 0;
-    T.wave_doubles = stage_d(NQ) + 64 * NQ + 5 * MP + MB * WL + T.nnzp;
+    T.wave_doubles = stage_d(NQ) + 64 * NQ + 5 * MP + MB * WL + T.nnzp + (bd ? 2 * NP : 0);
     int wpb = 4;
     for (;;) {
         size_t off = 0;
@@ -2315,7 +2365,7 @@ static int wreg_plan_create_tables(int m, int n, int nnz, const double* val, con
         if (pa) T.o_ec_src = take(sizeof(unsigned short) * ec_src.size());
         T.lds_bytes = (int)((off + 15) & ~(size_t)15);
         if (T.lds_bytes <= max_lds) break;
-        if (!pa || wpb == 1) { delete P; return 1; }
+        if (!(pa || bd) || wpb == 1) { delete P; return 1; }
         wpb--;
     }
     // ---- device copies ----
@@ -2335,7 +2385,7 @@ static int wreg_plan_create_tables(int m, int n, int nnz, const double* val, con
     T.colmap = (const unsigned*)(db + a9);
     T.t_cd = (const unsigned*)(db + a11);
     T.ec_src = (const unsigned short*)(db + a12); T.t_ab = (const unsigned*)(db + a13);
-    P->mb = MB; P->nq = NQ; P->pa = pa; T.wpb = wpb;
+    P->mb = MB; P->nq = NQ; P->pa = pa; P->bd = bd; T.wpb = wpb;
     *out = P;
     return 0;
 }
@@ -2352,6 +2402,7 @@ int wreg_variant(const WregPlan* p) { return p ? (p->da ? 2 : 1) : 0; }
 int wreg_has_predcorr(const WregPlan* p) { return p ? 1 : 0; }
 
 static const WVariant* find_variant(const WregPlan* p) {
+    if (p->bd) return nullptr;
     for (int i = 0; i < kNumWVariants; i++)
         if (kWVariants[i].mb == p->mb && kWVariants[i].nq == p->nq && kWVariants[i].da == p->da && kWVariants[i].pa == p->pa) return &kWVariants[i];
     return nullptr;
@@ -2381,6 +2432,21 @@ hipError_t wreg_launch_solve(WregPlan* p, long B, const double* a_batch, const d
         if (!fn) return hipErrorNotSupported;
     }
     return fn(p->tab, B, a_batch, b, c, x, y, z, pobj, dobj, status, iters, qhead, defer, o, (int)grid, st);
+}
+
+hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* b, const double* c, const double* u, double* x, double* y,
+                                     double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead,
+                                     DevOpts o, int num_cu, hipStream_t st, int* grid_out) {
+    wbsolve_fn fn = nullptr;
+    for (int i = 0; p && p->bd && i < kNumWVariantsBD; i++)
+        if (kWVariantsBD[i].mb == p->mb && kWVariantsBD[i].nq == p->nq && kWVariantsBD[i].da == p->da) fn = kWVariantsBD[i].solve;
+    if (!fn) return hipErrorInvalidValue;
+    long cus = (long)num_cu - o.reserve_cus > 0 ? (long)num_cu - o.reserve_cus : 1;
+    if (p->mb <= 4 && 2 * (long)p->tab.lds_bytes <= 160 * 1024 && p->tab.wpb == 4) cus *= 2;     // as wreg_launch_solve
+    long grid = std::min(cus, (B + p->tab.wpb - 1) / p->tab.wpb);
+    if (grid < 1) grid = 1;
+    if (grid_out) *grid_out = (int)grid;
+    return fn(p->tab, B, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o, (int)grid, st);
 }
 
 hipError_t wreg_launch_newton(WregPlan* p, long B, const double* x, const double* z, const double* y, const double* b,

@@ -1,0 +1,279 @@
+// ipm_wreg_bounded.inc -- the register-resident one-LP-per-wavefront kernel (ipm_wreg_kernel) for LPs with UPPER BOUNDS:
+//   maximise c'x  subject to  A x = b,  0 <= x <= u        (u_j = +inf: no bound;  u_j = 0: the column is fixed at 0)
+// the bounded equality form of a GeneralLP (pycllp_amd/lp.py, GeneralLP.to_bounded_equality_form), any shared A.  Included by
+// ipm_wreg.hip in its seventh translation unit (WREG_PART = 6).  The step is the one of ipm_group_bounded.inc (DESIGN.md
+// sections 14 and 15; tests/bounded_twin.py restates it):
+//   d = 1 / (z/x + s/t),  t~ = c - A'y + mu/x - mu/t + (s/t) tau,  tau = u - x - t,  mu = delta gamma / (n + m + N_b)
+//   M dy = A (d t~) - rho,  dx = d (t~ - A'dy),  dz = (mu - z dx)/x - z,  dt = tau - dx,  ds = (mu - s dt)/t - s
+// A column without a bound carries no t, s: every formula is then the one of ipm_wreg_kernel.  A fixed column takes no part in
+// the iteration: it ends at x = 0 with the duals z = max(A'y - c, 0), s = max(c - A'y, 0).
+// Only the per-column phases are new: gram(), factor<false>(), newton_solve<false> (block substitution + x-space refinement),
+// At() and Arow() are the WReg<MB, NQ, DA> members, unchanged.  Differences from ipm_wreg_kernel:
+//   * no carried residuals: cv = c - A'y and rho = b - A x are recomputed from the point at the top of every iteration (one
+//     A'y and one A x more per iteration), so every verdict is taken on fresh residuals and the path is the twin's;
+//   * t and s cross the factorisation and the loop's back edge in 2 NP more doubles per wave BEHIND the wave area
+//     (G::WAVE_D(NQ)): the stage, the tile and every other offset of the wave area are those of ipm_wreg_kernel; the bounded
+//     plan (wreg_plan_create_bounded) reserves the extra doubles.  x and z wait where ipm_wreg_kernel parks them, t~ where the
+//     Newton kernel parks its t (stage_()[0, NP)), d in vd_(), rho in flr_().  u and c are read from global memory;
+//   * an LP whose LDL' the Nocedal-Wright guard would have changed has no guarded kernel to go to: it ends NUMERICAL;
+//   * a verdict reached inside an iteration (NUMERICAL, ITERATION_LIMIT) is stored at the top of the next pass, where the
+//     point's A'y is at hand for the duals of the fixed columns; the point itself is the one the verdict was reached on.
+// No warm start, no predictor-corrector, no HSD.
+
+template <int MB, int NQ, bool DA>
+__global__ void __launch_bounds__(256, 1)
+ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const double* __restrict__ cg,
+                        const double* __restrict__ ug, double* __restrict__ xg, double* __restrict__ yg, double* __restrict__ zg,
+                        double* __restrict__ sg, double* __restrict__ pobj, double* __restrict__ dobj, int* __restrict__ status,
+                        int* __restrict__ iters, int* __restrict__ queue, DevOpts o) {
+    using G = WGeo<MB>;
+    constexpr int MR = G::MR, MP = G::MP, NP = 64 * NQ, TS = G::WAVE_D(NQ);   // t at W0[TS, TS + NP), s behind it
+    extern __shared__ __attribute__((aligned(16))) unsigned char lraw[];
+    WReg<MB, NQ, DA> w;
+    USE_AGPR_FORM();
+    wreg_setup(w, T, lraw, threadIdx.x);
+    const int& lane = w.lane;
+    const int m = w.m, n = w.n;
+    const bool autoscale = (o.flags & PYCLLP_FLAG_AUTOSCALE) != 0;
+    double* vx = w.stage_();
+    bool okc[NQ], okr[MR];
+#pragma unroll
+    for (int qq = 0; qq < NQ; qq++) okc[qq] = lane + 64 * qq < n;
+#pragma unroll
+    for (int r2 = 0; r2 < MR; r2++) okr[r2] = lane + 64 * r2 < m;
+
+    long lp;
+    {
+        int nxt = 0;
+        if (lane == 0) nxt = atomicAdd(queue, 1);
+        lp = __builtin_amdgcn_readfirstlane(nxt);
+    }
+    while (lp < B) {
+        // padded positions read u = 0 (buffer offset past the row): they take no part, like a fixed column
+        const __amdgpu_buffer_rsrc_t rc = row_rsrc(cg + lp * n, n), ru = row_rsrc(ug + lp * n, n);
+        // PYCLLP_FLAG_AUTOSCALE: b, u / max|b| and c / max|c| over the columns that take part (as the lane-group kernel)
+        double sb = 1.0, sc = 1.0;
+        if (autoscale) {
+            double cm = 0.0, bm = 0.0;
+#pragma unroll
+            for (int qq = 0; qq < NQ; qq++) {
+                const unsigned jo = w.coff(qq);
+                const double uj = buf_ld(ru, jo), cj = buf_ld(rc, jo);
+                cm = fmax(cm, uj > 0.0 ? fabs(cj) : 0.0);
+            }
+#pragma unroll
+            for (int r2 = 0; r2 < MR; r2++) bm = fmax(bm, okr[r2] ? fabs(bg[lp * m + lane + 64 * r2]) : 0.0);
+            sb = wmax(bm); sc = wmax(cm);
+            sb = uni((sb > 0.0) ? sb : 1.0); sc = uni((sc > 0.0) ? sc : 1.0);
+        }
+        // ---- start: z = s = y = 1, x = min(1, u/2), t = u - x (tau = 0); norms for the tolerances ----
+        double c2 = 0.0, u2 = 0.0, nbc = 0.0;
+#pragma unroll
+        for (int qq = 0; qq < NQ; qq++) {
+            const unsigned jo = w.coff(qq);
+            double cj = buf_ld(rc, jo), uj = buf_ld(ru, jo);
+            if (autoscale) { cj = cj / sc; uj = uj / sb; }
+            const bool a = uj > 0.0, bq = a && uj < HUGE_VAL;
+            c2 += a ? cj * cj : 0.0;
+            u2 += bq ? uj * uj : 0.0;
+            nbc += bq ? 1.0 : 0.0;
+            const double xq = bq ? fmin(1.0, 0.5 * uj) : 1.0;
+            w.stage_()[NP + lane + 64 * qq] = xq;
+            w.stage_()[2 * NP + lane + 64 * qq] = 1.0;
+            w.W0[TS + lane + 64 * qq] = bq ? uj - xq : 1.0;
+            w.W0[TS + NP + lane + 64 * qq] = 1.0;
+        }
+        double b2 = 0.0;
+#pragma unroll
+        for (int r2 = 0; r2 < MR; r2++) {
+            const int i = lane + 64 * r2;
+            double bi = okr[r2] ? bg[lp * m + i] : 0.0;
+            if (autoscale) bi = bi / sb;
+            b2 = fma(bi, bi, b2);
+            if (i < MP) { w.bs_()[i] = bi; w.ys_()[i] = okr[r2] ? 1.0 : 0.0; }
+        }
+        wave_lds_sync();
+        const double nb2 = wsum(b2), nc2 = wsum(c2), nu2 = wsum(u2);
+        const double tol_r = uni(o.eps * (1.0 + sqrt(nb2))), tol_s = uni(o.eps * (1.0 + sqrt(nc2)));
+        const double tol_u = uni(o.eps * (1.0 + sqrt(nu2))), etol = uni(o.refine_tol * (1.0 + sqrt(nb2)));
+        const double ncomp = uni((double)(n + m) + wsum(nbc));
+        double normr0 = 1e300, norms0 = 1e300;
+        int it = 0, forced = -1;      // forced >= 0: the verdict reached inside the last pass, stored by this one
+        bool running = true;
+
+        while (running) {
+            double x[NQ], z[NQ], cq[NQ], uq[NQ], v[NQ], rho[MR];
+#pragma unroll
+            for (int qq = 0; qq < NQ; qq++) { const unsigned jo = w.coff(qq); cq[qq] = buf_ld(rc, jo); uq[qq] = buf_ld(ru, jo); }
+            w.At(w.ys_(), v);          // (c and u in flight meanwhile)
+#pragma unroll
+            for (int qq = 0; qq < NQ; qq++) {
+                if (autoscale) { cq[qq] = cq[qq] / sc; uq[qq] = uq[qq] / sb; }
+                x[qq] = w.stage_()[NP + lane + 64 * qq];
+                z[qq] = w.stage_()[2 * NP + lane + 64 * qq];
+                vx[lane + 64 * qq] = (uq[qq] > 0.0) ? x[qq] : 0.0;
+            }
+            wave_lds_sync();
+            {
+                double Ax[MR], dm[MR];
+                w.template Arow<false>(vx, Ax, dm);
+#pragma unroll
+                for (int r2 = 0; r2 < MR; r2++) rho[r2] = okr[r2] ? w.bs_()[lane + 64 * r2] - Ax[r2] : 0.0;
+            }
+            // ---- dual infeasibility, complementarity, bound residual, objectives of THIS point ----
+            double s2 = 0.0, gam = 0.0, tau2 = 0.0, pp = 0.0, dd = 0.0, r2s = 0.0;
+#pragma unroll
+            for (int qq = 0; qq < NQ; qq++) {
+                const bool a = uq[qq] > 0.0, bq = a && uq[qq] < HUGE_VAL;
+                const double tq = w.W0[TS + lane + 64 * qq], sq = w.W0[TS + NP + lane + 64 * qq];
+                const double sgq = a ? (cq[qq] - v[qq]) + z[qq] - (bq ? sq : 0.0) : 0.0;
+                const double tau = bq ? (uq[qq] - x[qq]) - tq : 0.0;
+                s2 = fma(sgq, sgq, s2);
+                tau2 = fma(tau, tau, tau2);
+                gam += a ? x[qq] * z[qq] : 0.0;
+                gam += bq ? sq * tq : 0.0;
+                pp += a ? cq[qq] * x[qq] : 0.0;
+                dd += bq ? uq[qq] * sq : 0.0;
+            }
+#pragma unroll
+            for (int r2 = 0; r2 < MR; r2++) {
+                const int i = lane + 64 * r2;
+                dd = fma((i < MP) ? w.bs_()[i] : 0.0, (i < MP) ? w.ys_()[i] : 0.0, dd);
+                r2s = fma(rho[r2], rho[r2], r2s);
+            }
+            s2 = wsum(s2); gam = wsum(gam); tau2 = wsum(tau2);
+            const double po = wsum(pp), du = wsum(dd);
+            const double norms = uni(sqrt(s2)), normr = uni(sqrt(wsum(r2s))), ntau = uni(sqrt(tau2));
+            const double mu = uni(o.delta * gam / ncomp);
+            // ---- stop tests ----
+            int stat = PYCLLP_STATUS_ITERATION_LIMIT;
+            if (forced >= 0) { stat = forced; running = false; }
+            else if (!(isfinite(normr) && isfinite(norms) && isfinite(gam) && isfinite(ntau))) { stat = PYCLLP_STATUS_NUMERICAL; running = false; }
+            else if (normr <= tol_r && norms <= tol_s && gam <= o.eps * (1.0 + fabs(po)) && ntau <= tol_u) { stat = PYCLLP_STATUS_OPTIMAL; running = false; }
+            else if (normr > 10.0 * normr0 && normr > PYCLLP_GROWTH_FLOOR * tol_r) { stat = PYCLLP_STATUS_PRIMAL_INFEASIBLE; running = false; }
+            else if (norms > 10.0 * norms0 && norms > PYCLLP_GROWTH_FLOOR * tol_s) { stat = PYCLLP_STATUS_DUAL_INFEASIBLE; running = false; }
+            if (!running) {
+                // ---- store the LP (padded positions and null z / s: dropped by the buffer descriptors) ----
+                const __amdgpu_buffer_rsrc_t rx = row_rsrc(xg + lp * n, n), rz = row_rsrc(zg ? zg + lp * n : nullptr, n),
+                                             rs = row_rsrc(sg ? sg + lp * n : nullptr, n);
+#pragma unroll
+                for (int qq = 0; qq < NQ; qq++) {
+                    const unsigned jo = w.coff(qq);
+                    const bool a = uq[qq] > 0.0, bq = a && uq[qq] < HUGE_VAL;
+                    const double r = cq[qq] - v[qq];          // reduced cost of a fixed column
+                    const double sq = w.W0[TS + NP + lane + 64 * qq];
+                    buf_st(rx, jo, a ? x[qq] * sb : 0.0);
+                    buf_st(rz, jo, (a ? z[qq] : fmax(-r, 0.0)) * sc);
+                    buf_st(rs, jo, (bq ? sq : (a ? 0.0 : fmax(r, 0.0))) * sc);
+                }
+#pragma unroll
+                for (int r2 = 0; r2 < MR; r2++) {
+                    const int i = lane + 64 * r2;
+                    if (yg && okr[r2]) yg[lp * m + i] = w.ys_()[i] * sc;
+                }
+                if (lane == 0) {
+                    if (pobj) pobj[lp] = po * (sb * sc);
+                    if (dobj) dobj[lp] = du * (sb * sc);
+                    status[lp] = stat;
+                    if (iters) iters[lp] = it;
+                }
+                break;
+            }
+            // ---- d = 1 / (z/x + s/t), t~ = c - A'y + mu/x - mu/t + (s/t) tau; rhs = A (d t~) - rho, diag(M) ----
+            double tt[NQ];
+#pragma unroll
+            for (int qq = 0; qq < NQ; qq++) {
+                const bool a = uq[qq] > 0.0, bq = a && uq[qq] < HUGE_VAL;
+                const double tq = w.W0[TS + lane + 64 * qq], sq = w.W0[TS + NP + lane + 64 * qq];
+                const double rx = fast_rcp(x[qq]), rt = fast_rcp(tq);
+                const double tau = (uq[qq] - x[qq]) - tq;
+                double dq, tn;
+                if (bq) {
+                    dq = fast_rcp(fma(z[qq], rx, sq * rt));
+                    tn = (cq[qq] - v[qq]) + mu * rx - mu * rt + (sq * rt) * tau;
+                } else {
+                    dq = x[qq] * fast_rcp(z[qq]);
+                    tn = (cq[qq] - v[qq]) + mu * rx;
+                }
+                dq = a ? dq : 0.0;
+                tt[qq] = a ? tn : 0.0;
+                vx[lane + 64 * qq] = dq * tt[qq];
+                w.vd_()[lane + 64 * qq] = dq;
+            }
+            wave_lds_sync();
+            double beta2;
+            {
+                double Adt[MR], Md[MR], bmax = 0.0;
+                w.template Arow<true>(vx, Adt, Md);
+#pragma unroll
+                for (int r2 = 0; r2 < MR; r2++) {
+                    const int i = lane + 64 * r2;
+                    if (i < MP) { w.um_()[i] = okr[r2] ? Adt[r2] - rho[r2] : 0.0; w.flr_()[i] = rho[r2]; }
+                    bmax = fmax(bmax, okr[r2] ? fabs(Md[r2]) : 0.0);
+                }
+                beta2 = wmax(bmax);
+                wave_lds_sync();
+                // ---- M = A diag(d) A' into registers; factor ----
+                w.gram(Md);
+            }
+            // t~, x and z wait in the stage while factor and solve have the registers
+#pragma unroll
+            for (int qq = 0; qq < NQ; qq++) {
+                w.stage_()[lane + 64 * qq] = tt[qq];
+                w.stage_()[NP + lane + 64 * qq] = x[qq];
+                w.stage_()[2 * NP + lane + 64 * qq] = z[qq];
+            }
+            const bool viol = w.template factor<false>(beta2, o.pivot_floor);
+            if (viol) { forced = PYCLLP_STATUS_NUMERICAL; continue; }   // the guard would have bitten: no guarded kernel here
+            double dy[MR], wv[NQ], dx[NQ], e[MR], rhn[MR];
+            bool bad;
+#pragma unroll
+            for (int r2 = 0; r2 < MR; r2++) rhn[r2] = (lane + 64 * r2 < MP) ? w.flr_()[lane + 64 * r2] : 0.0;
+            (void)newton_solve<false>(w, okc, okr, rhn, etol, o.max_refine, mu, dy, dx, wv, e, bad, nullptr);
+            if (bad) { forced = PYCLLP_STATUS_NUMERICAL; continue; }
+            // ---- step: theta = min(r / max(0, -dx/x, -dz/z, -dt/t, -ds/s), 1) ----
+            double th = 0.0;
+            double dz[NQ], dt[NQ], ds[NQ];
+#pragma unroll
+            for (int qq = 0; qq < NQ; qq++) {
+                const unsigned jo = w.coff(qq);
+                double uj = buf_ld(ru, jo);
+                if (autoscale) uj = uj / sb;
+                const bool a = uj > 0.0, bq = a && uj < HUGE_VAL;
+                const double xq = w.stage_()[NP + lane + 64 * qq], zq = w.stage_()[2 * NP + lane + 64 * qq];
+                const double tq = w.W0[TS + lane + 64 * qq], sq = w.W0[TS + NP + lane + 64 * qq];
+                const double rx = fast_rcp(xq), rz = fast_rcp(zq), rt = fast_rcp(tq);
+                const double tau = (uj - xq) - tq;
+                dz[qq] = a ? (mu - zq * dx[qq]) * rx - zq : 0.0;
+                dt[qq] = bq ? tau - dx[qq] : 0.0;
+                ds[qq] = bq ? (mu - sq * dt[qq]) * rt - sq : 0.0;
+                if (a) th = fmax(th, fmax(-dz[qq] * rz, -dx[qq] * rx));
+                if (bq) th = fmax(th, fmax(-dt[qq] * rt, -ds[qq] * fast_rcp(sq)));
+            }
+            th = wmax(th);
+            const double theta = uni(fmin(o.r / th, 1.0));
+            wave_lds_sync();
+#pragma unroll
+            for (int r2 = 0; r2 < MR; r2++) {
+                const int i = lane + 64 * r2;
+                if (i < MP) w.ys_()[i] = fma(theta, dy[r2], w.ys_()[i]);
+            }
+#pragma unroll
+            for (int qq = 0; qq < NQ; qq++) {
+                // (dx, dz are 0 where the column takes no part, dt, ds where it has no bound: those values stay)
+                w.stage_()[NP + lane + 64 * qq] = fma(theta, dx[qq], w.stage_()[NP + lane + 64 * qq]);
+                w.stage_()[2 * NP + lane + 64 * qq] = fma(theta, dz[qq], w.stage_()[2 * NP + lane + 64 * qq]);
+                w.W0[TS + lane + 64 * qq] = fma(theta, dt[qq], w.W0[TS + lane + 64 * qq]);
+                w.W0[TS + NP + lane + 64 * qq] = fma(theta, ds[qq], w.W0[TS + NP + lane + 64 * qq]);
+            }
+            normr0 = normr; norms0 = norms;
+            wave_lds_sync();
+            it++;
+            if (it >= o.max_iter) forced = PYCLLP_STATUS_ITERATION_LIMIT;
+        }
+        wave_lds_sync();
+        int nxt = 0;
+        if (lane == 0) nxt = atomicAdd(queue, 1);
+        lp = __builtin_amdgcn_readfirstlane(nxt);
+    }
+}

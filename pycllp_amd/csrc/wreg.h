@@ -63,6 +63,13 @@ extern const int kNumWVariantsPCDA;
 extern const WVariant kWVariantsPCPA[];    // ... and of the per-problem-A variants (-DWREG_PART=5)
 extern const int kNumWVariantsPCPA;
 
+// the kernel for LPs with upper bounds (ipm_wreg_bounded.inc, -DWREG_PART=6): argument meaning of pycllp_hip_sparse_solve_bounded
+typedef hipError_t (*wbsolve_fn)(const WregTab&, long, const double*, const double*, const double*, double*, double*, double*,
+                                 double*, double*, double*, int*, int*, int*, DevOpts, int, hipStream_t);
+struct WBVariant { int mb, nq; bool da; wbsolve_fn solve; };
+extern const WBVariant kWVariantsBD[];
+extern const int kNumWVariantsBD;
+
 struct WregPlan;   // host tables + device copies for one shared constraint matrix
 
 // Builds the plan from a host CSR copy of A (m rows, n columns, equality form).  Returns 0 and *out on success,
@@ -71,6 +78,11 @@ struct WregPlan;   // host tables + device copies for one shared constraint matr
 // pa != 0: the plan of the per-problem-A variants (structure tables only; `val` is not read).
 int wreg_plan_create(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds, int pa,
                      hipStream_t st, WregPlan** out);
+// The plan of the bounded kernel for the same A: the tables or dense image of wreg_plan_create with 2 NP more doubles per
+// wave (t and s), as many waves per workgroup (4 at most) as the LDS then takes.  Returns 1 when no bounded variant or LDS plan
+// covers A.
+int wreg_plan_create_bounded(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
+                             hipStream_t st, WregPlan** out);
 void wreg_plan_free(WregPlan* p);
 
 // Solve B LPs (same argument meaning as pycllp_hip_sparse_solve).  LPs whose factorisation would have needed the
@@ -80,6 +92,12 @@ void wreg_plan_free(WregPlan* p);
 hipError_t wreg_launch_solve(WregPlan* p, long B, const double* a_batch, const double* b, const double* c, double* x, double* y, double* z,
                              double* pobj, double* dobj, int* status, int* iters, int* qhead, int* defer, DevOpts o,
                              int num_cu, hipStream_t st, int* grid_out);
+
+// Solve B LPs with upper bounds on a plan of wreg_plan_create_bounded (argument meaning of pycllp_hip_sparse_solve_bounded).
+// An LP whose factorisation would have needed the Nocedal-Wright guard ends PYCLLP_STATUS_NUMERICAL.
+hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* b, const double* c, const double* u, double* x, double* y,
+                                     double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead,
+                                     DevOpts o, int num_cu, hipStream_t st, int* grid_out);
 
 // One Newton step for B states (semantics of pycllp_hip_dense_newton).  guard_hit[0] is set to 1 if any state would
 // have needed the guard (the stand-alone step then simply ran without it).

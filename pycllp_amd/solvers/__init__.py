@@ -63,4 +63,4 @@ def register_with_pycllp():
 
 
 from .hip import HipDensePrimalNormalSolver, HipSparsePrimalNormalSolver  # noqa: E402,F401
-from .general import HipGeneralPrimalNormalSolver  # noqa: E402,F401
+from .general import HipGeneralPrimalNormalSolver, HipSparseGeneralPrimalNormalSolver  # noqa: E402,F401

@@ -1,4 +1,4 @@
-"""HIP solver plugin for ``GeneralLP``:  optimise c'x + f  s.t.  a <= A x <= b,  l <= x <= u.
+"""HIP solver plugins for ``GeneralLP``:  optimise c'x + f  s.t.  a <= A x <= b,  l <= x <= u.
 
 The LP is brought into the bounded equality form (``GeneralLP.to_bounded_equality_form``: A^ = [+-A | I], 0 <= x^ <= u^) and
 solved on the bounded slack-aware lane-group kernel (``pycllp_hip_dense_solve_bounded``, csrc/ipm_group_bounded.inc): one row
@@ -6,6 +6,10 @@ per kept row of the LP and no row per upper bound.  What that kernel does not se
 columns, per-problem values of A -- is solved through the reference's conversion ``to_standard_form().to_equality_form()``
 (``pycllp/lp.py:725-792``) on ``HipDensePrimalNormalSolver`` and mapped back the same way, so the plugin takes every LP the
 library takes.  ``kernel`` tells which path served the last ``solve``: ``'bounded group'`` or ``'expanded'``.
+
+``hip_sparse_general_primal_normal`` is the same plugin on the bounded one-LP-per-wavefront kernel
+(``pycllp_hip_sparse_solve_bounded``, csrc/ipm_wreg_bounded.inc): any shared A^ with m' <= 128 kept rows and N <= 512 columns
+that a variant of that kernel covers (``kernel == 'bounded wave'``), sparse or dense, the expansion for the rest.
 """
 import ctypes
 
@@ -18,6 +22,7 @@ from ..lp import GeneralLP, SparseMatrix
 from .hip import HipDensePrimalNormalSolver, _require_gpu, autoscale_wanted
 
 NATIVE_MAX_ROWS, NATIVE_MAX_COLS = 32, 96      # the slack-aware kernels: m' <= 32 rows, n <= 96 original columns
+WAVE_MAX_ROWS, WAVE_MAX_COLS = 128, 512        # the bounded wave kernel: m' <= 128 rows, N <= 512 columns of A^
 _REJECTED = (_native.FLAG_HSD | _native.FLAG_PREDCORR | _native.FLAG_WARM_START | _native.FLAG_WAVE_KERNEL
              | _native.FLAG_NO_SLACK_PATH)
 RESULTS = ("x", "y", "z", "s", "status", "iters", "primal_obj", "dual_obj")
@@ -46,6 +51,10 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
     per row of the LP, 0 for a row without bounds), ``z`` / ``s [B, n]`` (duals of x >= l / x <= u), ``status``, ``iters``,
     ``primal_obj``, ``dual_obj`` (f and c'l included)."""
     name = 'hip_general_primal_normal'
+    _rejected = _REJECTED
+    _rejected_names = "HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH"
+    _native_kernel = "bounded group"
+    _bounded_entry = "pycllp_hip_dense_solve_bounded"
 
     def __init__(self, device=None, stream=None, autoscale="auto", hsd="auto", predcorr=False, warm_start=False, **options):
         """``hsd='auto'`` (default): the LPs that do not end optimal on the bounded kernel are solved again through the
@@ -59,8 +68,8 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
             raise ValueError("predcorr is not available with upper bounds")
         if warm_start:
             raise ValueError("warm_start is not available with upper bounds")
-        if int(options.get("flags", 0)) & _REJECTED:
-            raise ValueError("flags HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH are not available with upper bounds")
+        if int(options.get("flags", 0)) & self._rejected:
+            raise ValueError("flags %s are not available with upper bounds" % self._rejected_names)
         if isinstance(autoscale, str):
             if autoscale != "auto":
                 raise ValueError("autoscale must be True, False or 'auto'")
@@ -136,9 +145,9 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
             self.kernel = "expanded"
             res = self.solve_expanded(glp)
         else:
-            self.kernel = "bounded group"
+            self.kernel = self._native_kernel
             if self.hsd == "auto":
-                idx = np.flatnonzero(res["status"] != 0)
+                idx = self._redo(glp, np.flatnonzero(res["status"] != 0))
                 if idx.size:
                     r2 = self.solve_expanded(subset(glp, idx))
                     for k in RESULTS:
@@ -146,6 +155,10 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
         for k in RESULTS:
             setattr(self, k, res[k])
         return self.status
+
+    def _redo(self, glp, idx):
+        """The LPs among ``idx`` (not optimal on the native kernel) that ``hsd='auto'`` solves again through the expansion."""
+        return idx
 
     def _solve_bounded(self, blp, bmap):
         """One upload, one launch of the bounded kernel, one download; None if the library declines A^ (PYCLLP_E_UNSUPPORTED)."""
@@ -170,12 +183,12 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
             status = torch.empty(B, dtype=torch.int32, device=dev)
             iters = torch.empty(B, dtype=torch.int32, device=dev)
             P = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
-            rc = _native.lib().pycllp_hip_dense_solve_bounded(
+            rc = getattr(_native.lib(), self._bounded_entry)(
                 self._handle, B, P(b), P(c), P(u), P(x), P(y), P(z), P(s), P(pobj), P(dobj), P(status), P(iters),
                 ctypes.byref(o), self._stream_ptr())
             if rc == -2:
                 return None
-            _native.check(rc, "pycllp_hip_dense_solve_bounded")
+            _native.check(rc, self._bounded_entry)
             torch.cuda.synchronize(dev)
         xo, yo, zo, so = bmap.general(x.cpu().numpy(), y.cpu().numpy(), z.cpu().numpy(), s.cpu().numpy())
         f = np.broadcast_to(blp.f, (B,))
@@ -219,3 +232,63 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
             out["primal_obj"][idx] = solver.primal_obj
             out["dual_obj"][idx] = solver.dual_obj
         return out
+
+
+def expansion_rows(glp):
+    """Rows of ``glp.to_standard_form().to_equality_form()`` for the batch: one per finite lower and upper row bound and per
+    finite upper column bound in any of its LPs (what ``solve_expanded`` hands to ``HipDensePrimalNormalSolver``)."""
+    return int(np.isfinite(glp.a).any(axis=0).sum() + np.isfinite(glp.b).any(axis=0).sum()
+               + np.isfinite(glp.u).any(axis=0).sum())
+
+
+class HipSparseGeneralPrimalNormalSolver(HipGeneralPrimalNormalSolver):
+    """``hip_general_primal_normal`` on the bounded one-LP-per-wavefront kernel (``pycllp_hip_sparse_solve_bounded``): the same
+    contract, options and results, for bounded forms of up to 128 kept rows and 512 columns, sparse or dense.  ``kernel`` is
+    ``'bounded wave'`` or ``'expanded'`` (per-problem values of A, a bounded form no variant of the kernel covers).  With
+    ``hsd='auto'`` the LPs that do not end optimal -- NUMERICAL included -- are solved again through the expansion where it
+    fits the library (``pycllp_hip_dense_max_rows()`` / ``_max_cols()``); elsewhere the wave kernel's status stands."""
+    name = 'hip_sparse_general_primal_normal'
+    _rejected = _REJECTED | _native.FLAG_BLOCK_KERNEL | _native.FLAG_FORCE_GUARD_PATH
+    _rejected_names = "HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and FORCE_GUARD_PATH"
+    _native_kernel = "bounded wave"
+    _bounded_entry = "pycllp_hip_sparse_solve_bounded"
+
+    def _free(self):
+        if self._handle is not None:
+            _native.lib().pycllp_hip_sparse_free(self._handle)
+            self._handle = None
+            self._key = None
+
+    @staticmethod
+    def native_fits(glp, blp):
+        return glp.A.nproblems == 1 and 1 <= blp.nrows <= WAVE_MAX_ROWS and blp.ncols <= WAVE_MAX_COLS
+
+    def _ensure_handle(self, blp):
+        """A handle for the CSR of A^ (re-made when A^ changed since the last one); False if the library declines it."""
+        A = blp.A.tocsr()
+        A.sum_duplicates(); A.eliminate_zeros(); A.sort_indices()
+        data = np.ascontiguousarray(A.data, dtype=np.float64)
+        indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
+        indices = np.ascontiguousarray(A.indices, dtype=np.int32)
+        key = (A.shape, data.tobytes(), indptr.tobytes(), indices.tobytes())
+        if self._handle is not None and self._key == key:
+            return True
+        self._free()
+        with torch.cuda.device(self.device):
+            t = [torch.as_tensor(v, device=self.device) for v in (data, indptr, indices)]
+            h = ctypes.c_void_p()
+            rc = _native.lib().pycllp_hip_sparse_init(A.shape[0], A.shape[1], int(A.nnz), *(ctypes.c_void_p(v.data_ptr()) for v in t),
+                                                      self._stream_ptr(), ctypes.byref(h))
+            torch.cuda.synchronize(self.device)
+        if rc == -2:
+            return False
+        _native.check(rc, "pycllp_hip_sparse_init")
+        self._handle, self._key = h, key
+        return True
+
+    def _redo(self, glp, idx):
+        if idx.size:
+            L, rows = _native.lib(), expansion_rows(subset(glp, idx))
+            if rows > L.pycllp_hip_dense_max_rows() or glp.ncols + rows > L.pycllp_hip_dense_max_cols():
+                return idx[:0]
+        return idx
