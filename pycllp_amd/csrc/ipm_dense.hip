@@ -460,7 +460,32 @@ struct QueueRing {
         mu[s].unlock();
         return e;
     }
+    // launch(head) on a slot of its own: acquire, launch, release on every path once acquired; the launch's error comes first
+    template <typename Launch>
+    hipError_t run(hipStream_t st, Launch&& launch) {
+        int* head = nullptr; unsigned slot = 0;
+        hipError_t e = acquire(st, &head, &slot);
+        if (e != hipSuccess) return e;
+        e = launch(head);
+        const hipError_t er = release(slot, st);
+        return e != hipSuccess ? e : er;
+    }
 };
+
+// What the launch plans need to know of the current device: its CU count and the LDS one workgroup may take.  The LDS cap
+// is 160 KB, also where a device reports none: every code object of this library is built for gfx950, which has 160 KB.
+struct DeviceLimits { int num_cu = 0, max_lds = 0; };
+static hipError_t device_limits(DeviceLimits* d) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+    if (e != hipSuccess) return e;
+    d->num_cu = prop.multiProcessorCount;
+    d->max_lds = (int)prop.maxSharedMemoryPerMultiProcessor;
+    if (d->max_lds > 160 * 1024 || d->max_lds <= 0) d->max_lds = 160 * 1024;
+    return hipSuccess;
+}
 
 struct pycllp_hip_dense {
     int m = 0, n = 0, mp = 0, np = 0, variant = -1;
@@ -515,12 +540,11 @@ static hipError_t launch_pack(pycllp_hip_dense* h, const double* A, hipStream_t 
     return hipGetLastError();
 }
 
-template <int MP, int NP, bool SL, bool HSD = false, bool PC = false>
-static hipError_t launch_solve_group(pycllp_hip_dense* h, long B, const double* b, const double* c, double* x, double* y,
-                                     double* z, double* pobj, double* dobj, int* status, int* iters, DevOpts o,
-                                     hipStream_t st) {
+// Launch plan of a lane-group kernel on GeoG<MP, NP, SL>, starting from wpb waves per workgroup (as many as its launch bounds
+// allow) and stepping down until the LDS takes them
+template <int MP, int NP, bool SL>
+static LaunchPlan plan_group(const pycllp_hip_dense* h, long B, int wpb, const DevOpts& o) {
     using G = GeoG<MP, NP, SL>;
-    int wpb = HSD ? hsd_wpb<MP>() : PYCLLP_WPB;
     while (wpb > 1 && G::lds_bytes(wpb) > (size_t)h->max_lds) wpb--;
     // one persistent workgroup per CU: its 8 waves already use the whole register file, so a second workgroup could not
     // become resident whatever the LDS says
@@ -539,19 +563,32 @@ static hipError_t launch_solve_group(pycllp_hip_dense* h, long B, const double* 
     long blocks = (B + wpb - 1) / wpb;
     if (blocks > resident) blocks = resident;
     if (blocks < 1) blocks = 1;
-    const LaunchPlan p{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP};
+    return LaunchPlan{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP};
+}
+
+// Sets the kernel's LDS, runs launch(qhead) on a queue-ring slot and publishes the plan for launch_info
+template <typename Launch>
+static hipError_t run_group(pycllp_hip_dense* h, const void* kernel, const LaunchPlan& p, hipStream_t st, Launch&& launch) {
+    hipError_t e = set_dyn_lds(kernel, p.lds);
+    if (e != hipSuccess) return e;
+    return h->ring.run(st, [&](int* qhead) {
+        launch(qhead);
+        const hipError_t el = hipGetLastError();
+        publish(h, p);
+        return el;
+    });
+}
+
+template <int MP, int NP, bool SL, bool HSD = false, bool PC = false>
+static hipError_t launch_solve_group(pycllp_hip_dense* h, long B, const double* b, const double* c, double* x, double* y,
+                                     double* z, double* pobj, double* dobj, int* status, int* iters, DevOpts o,
+                                     hipStream_t st) {
+    const LaunchPlan p = plan_group<MP, NP, SL>(h, B, HSD ? hsd_wpb<MP>() : PYCLLP_WPB, o);
     auto kernel = HSD ? hsd_group_kernel<MP, NP, SL> : ipm_group_kernel<MP, NP, SL, PC>;
-    hipError_t e = set_dyn_lds((const void*)kernel, p.lds);
-    if (e != hipSuccess) return e;
-    int* qhead = nullptr; unsigned slot = 0;
-    e = h->ring.acquire(st, &qhead, &slot);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, st, h->m, h->n, B,
-                       h->a_rm, b, c, x, y, z, pobj, dobj, status, iters, qhead, o);
-    e = hipGetLastError();
-    hipError_t e2 = h->ring.release(slot, st);
-    publish(h, p);
-    return e != hipSuccess ? e : e2;
+    return run_group(h, (const void*)kernel, p, st, [&](int* qhead) {
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, st, h->m, h->n, B,
+                           h->a_rm, b, c, x, y, z, pobj, dobj, status, iters, qhead, o);
+    });
 }
 
 typedef hipError_t (*bounded_launch_fn)(pycllp_hip_dense*, long, const double*, const double*, const double*, double*, double*,
@@ -562,32 +599,12 @@ template <int MP, int NP>
 static hipError_t launch_solve_bounded(pycllp_hip_dense* h, long B, const double* b, const double* c, const double* u, double* x,
                                        double* y, double* z, double* s, double* pobj, double* dobj, int* status, int* iters,
                                        DevOpts o, hipStream_t st) {
-    using G = GeoG<MP, NP, true>;
-    int wpb = PYCLLP_WPB_BOUNDED;
-    while (wpb > 1 && G::lds_bytes(wpb) > (size_t)h->max_lds) wpb--;
-    const long resident = (long)h->num_cu - o.reserve_cus > 0 ? (long)h->num_cu - o.reserve_cus : 1;
-    {
-        const long per_cu = (B + resident - 1) / resident;
-        long want = (per_cu <= 4 * (long)G::G) ? (per_cu < 4 ? per_cu : 4) : (per_cu + G::G - 1) / G::G;
-        if (want < 1) want = 1;
-        if (want < wpb) wpb = (int)want;
-    }
-    long blocks = (B + wpb - 1) / wpb;
-    if (blocks > resident) blocks = resident;
-    if (blocks < 1) blocks = 1;
-    const LaunchPlan p{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP};
+    const LaunchPlan p = plan_group<MP, NP, true>(h, B, PYCLLP_WPB_BOUNDED, o);
     auto kernel = ipm_bounded_kernel<MP, NP>;
-    hipError_t e = set_dyn_lds((const void*)kernel, p.lds);
-    if (e != hipSuccess) return e;
-    int* qhead = nullptr; unsigned slot = 0;
-    e = h->ring.acquire(st, &qhead, &slot);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, st, h->m, h->n, B,
-                       h->a_rm, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o);
-    e = hipGetLastError();
-    hipError_t e2 = h->ring.release(slot, st);
-    publish(h, p);
-    return e != hipSuccess ? e : e2;
+    return run_group(h, (const void*)kernel, p, st, [&](int* qhead) {
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, st, h->m, h->n, B,
+                           h->a_rm, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o);
+    });
 }
 
 template <int MP, int NP>
@@ -613,35 +630,24 @@ struct Variant {
 
 #define VARIANT(MP, NP) \
     { MP, NP, Geo<MP, NP>::APACK, launch_pack<MP, NP>, launch_solve_group<MP, NP, false>, \
-      launch_solve_group<MP, NP, false, true>, launch_solve_group<MP, NP, false, false, true>, launch_newton<MP, NP> }
-
-// ordered by cost: the first variant that covers (m, n) is used
-static const Variant kVariants[] = {
-#ifdef PYCLLP_DEV_ONLY_3296   // development builds (tools/ab_*.sh): only the headline shape, compiles in a fraction of the time
-    VARIANT(32, 96),
-#elif defined(PYCLLP_DEV_ONLY_1648)
-    VARIANT(16, 48),
-#else
-    VARIANT(16, 32), VARIANT(16, 48), VARIANT(16, 64), VARIANT(32, 64),
-    VARIANT(32, 96), VARIANT(32, 128),
-#endif
-};
-static const int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+      launch_solve_group<MP, NP, false, true>, launch_solve_group<MP, NP, false, false, true>, launch_newton<MP, NP> },
 
 // slack-aware group kernels: (MP, NP) with NP - MP padded dense columns + the m identity columns
 struct SlackVariant { int mp, np; solve_launch_fn solve_group, solve_hsd, solve_pc; bounded_launch_fn solve_bounded; };
 #define SLACK_VARIANT(MP, NP) { MP, NP, launch_solve_group<MP, NP, true>, launch_solve_group<MP, NP, true, true>, \
-                                launch_solve_group<MP, NP, true, false, true>, launch_solve_bounded<MP, NP> }
-static const SlackVariant kSlackVariants[] = {
-#ifdef PYCLLP_DEV_ONLY_3296
-    SLACK_VARIANT(32, 96),
+                                launch_solve_group<MP, NP, true, false, true>, launch_solve_bounded<MP, NP> },
+
+// the lane-group shapes (MP, NP), ordered by cost: the first that covers (m, n) is used, in both tables
+#if defined(PYCLLP_DEV_ONLY_3296)   // development builds (tools/ab_*.sh): only the headline shape, compiles in a fraction of the time
+#define GROUP_SHAPES(X) X(32, 96)
 #elif defined(PYCLLP_DEV_ONLY_1648)
-    SLACK_VARIANT(16, 48),
+#define GROUP_SHAPES(X) X(16, 48)
 #else
-    SLACK_VARIANT(16, 32), SLACK_VARIANT(16, 48), SLACK_VARIANT(16, 64), SLACK_VARIANT(32, 64),
-    SLACK_VARIANT(32, 96), SLACK_VARIANT(32, 128),
+#define GROUP_SHAPES(X) X(16, 32) X(16, 48) X(16, 64) X(32, 64) X(32, 96) X(32, 128)
 #endif
-};
+static const Variant kVariants[] = { GROUP_SHAPES(VARIANT) };
+static const int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+static const SlackVariant kSlackVariants[] = { GROUP_SHAPES(SLACK_VARIANT) };
 static const int kNumSlackVariants = sizeof(kSlackVariants) / sizeof(kSlackVariants[0]);
 
 static unsigned long long* g_prof = nullptr;  // diagnostic build only
@@ -672,17 +678,36 @@ struct pycllp_hip_sparse {
     mutable std::mutex info_mu;
     int lds = 0, num_cu = 0, grid = 0;
     int lds_with_a = 0;     // LDS bytes with A's arrays in LDS (what per-problem values need), 0 when that does not fit
-    int last_wreg = 0;      // 1 when the last solve ran on the wave kernel
     WregPlan* wreg = nullptr;     // tables of the register-resident wave kernel (ipm_wreg.hip), or nullptr when it does not cover A
     BigPlan* big = nullptr;       // LPs beyond m = 128 / n = 512: the workgroup-per-LP kernel of ipm_big.hip serves the handle alone
     WregPlan* wreg_pa = nullptr;  // its per-problem-A plan (structure tables only), built by the first pycllp_hip_sparse_solve_batch
-    WregPlan* last_plan = nullptr;
+    WregPlan* last_plan = nullptr;   // the wave kernel's plan when the last solve ran on it, else null
     bool wreg_pa_tried = false;
     WregPlan* wreg_bd = nullptr;  // the plan of the bounded wave kernel (t and s behind every wave area), built by the first
     bool wreg_bd_tried = false;   // pycllp_hip_sparse_solve_bounded (under info_mu)
     int max_lds = 0;
     std::vector<double> host_val; std::vector<int> host_ptr, host_col;   // host CSR copy (what a PA plan is built from)
 };
+
+// what launch_info reports: the last solve ran on the wave kernel with `plan` (null: on the block or large-LP kernel)
+static void record_launch(pycllp_hip_sparse* h, WregPlan* plan, int grid) {
+    std::lock_guard<std::mutex> g(h->info_mu);
+    h->last_plan = plan; h->grid = grid;
+}
+
+// A wave-kernel plan built by its first user (under info_mu; once any call has returned, *plan no longer changes), null when
+// no variant covers A.  Returns 0, or the set_err code of a HIP error of the build.
+template <typename Create>
+static int lazy_plan(pycllp_hip_sparse* h, WregPlan** plan, bool* tried, const char* what, Create create) {
+    std::lock_guard<std::mutex> g(h->info_mu);
+    if (*tried) return 0;
+    *tried = true;
+    WregPlan* wp = nullptr;
+    const int rc = create(&wp);
+    if (rc >= 1000) return set_err(rc - 1000, what);
+    *plan = (rc == 0) ? wp : nullptr;
+    return 0;
+}
 
 template <typename T>
 static T* blob_put(char* host, size_t& off, const std::vector<T>& v, char* dev_base) {
@@ -762,21 +787,17 @@ int pycllp_hip_dense_init(int m, int n, const double* A_dev, void* stream, pycll
     pycllp_hip_dense* h = new (std::nothrow) pycllp_hip_dense();
     if (!h) return set_err(PYCLLP_E_NOMEM, "pycllp_hip_dense_init: out of host memory");
     h->m = m; h->n = n; h->variant = vi; h->mp = kVariants[vi].mp; h->np = kVariants[vi].np;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
-    if (e != hipSuccess) { delete h; return set_err((int)e, "hipGetDeviceProperties"); }
-    h->num_cu = prop.multiProcessorCount;
-    h->max_lds = (int)prop.maxSharedMemoryPerMultiProcessor;
-    if (h->max_lds > 160 * 1024) h->max_lds = 160 * 1024;
-    if (h->max_lds <= 0) h->max_lds = 64 * 1024;
+    // on failure the partly built handle goes through pycllp_hip_dense_free, which skips what was not made
+    DeviceLimits lim;
+    hipError_t e = device_limits(&lim);
+    if (e != hipSuccess) { pycllp_hip_dense_free(h); return set_err((int)e, "hipGetDeviceProperties"); }
+    h->num_cu = lim.num_cu; h->max_lds = lim.max_lds;
     e = hipMalloc((void**)&h->pack, sizeof(double) * kVariants[vi].apack);
-    if (e != hipSuccess) { delete h; return set_err((int)e, "hipMalloc(pack)"); }
+    if (e != hipSuccess) { pycllp_hip_dense_free(h); return set_err((int)e, "hipMalloc(pack)"); }
     e = hipMalloc((void**)&h->a_rm, sizeof(double) * (size_t)m * n);
-    if (e != hipSuccess) { (void)hipFree(h->pack); delete h; return set_err((int)e, "hipMalloc(A)"); }
+    if (e != hipSuccess) { pycllp_hip_dense_free(h); return set_err((int)e, "hipMalloc(A)"); }
     e = h->ring.create();
-    if (e != hipSuccess) { h->ring.destroy(); (void)hipFree(h->pack); (void)hipFree(h->a_rm); delete h; return set_err((int)e, "hipMalloc(queue)"); }
+    if (e != hipSuccess) { pycllp_hip_dense_free(h); return set_err((int)e, "hipMalloc(queue)"); }
     hipStream_t st = (hipStream_t)stream;
     e = hipMemcpyAsync(h->a_rm, A_dev, sizeof(double) * (size_t)m * n, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = kVariants[vi].pack(h, A_dev, st);
@@ -797,7 +818,7 @@ int pycllp_hip_dense_init(int m, int n, const double* A_dev, void* stream, pycll
         }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(h->pack); (void)hipFree(h->a_rm); h->ring.destroy(); delete h; return set_err((int)e, "pack_A_kernel"); }
+    if (e != hipSuccess) { pycllp_hip_dense_free(h); return set_err((int)e, "pack_A_kernel"); }
     *handle = h;
     return 0;
 }
@@ -951,20 +972,15 @@ int pycllp_hip_sparse_init(int m, int n, int nnz, const double* Adata_dev, const
         // LDS or an L2-resident workspace)
         pycllp_hip_sparse* hb = new (std::nothrow) pycllp_hip_sparse();
         if (!hb) return set_err(PYCLLP_E_NOMEM, "pycllp_hip_sparse_init: out of host memory");
-        int devb = 0;
-        hipDeviceProp_t propb;
-        hipError_t eb = hipGetDevice(&devb);
-        if (eb == hipSuccess) eb = hipGetDeviceProperties(&propb, devb);
+        DeviceLimits lim;
+        hipError_t eb = device_limits(&lim);
         if (eb == hipSuccess) eb = hb->ring.create();
-        if (eb != hipSuccess) { hb->ring.destroy(); delete hb; return set_err((int)eb, "pycllp_hip_sparse_init (large LP)"); }
-        hb->num_cu = propb.multiProcessorCount;
-        int max_lds_b = (int)propb.maxSharedMemoryPerMultiProcessor;
-        if (max_lds_b > 160 * 1024 || max_lds_b <= 0) max_lds_b = 160 * 1024;
-        hb->max_lds = max_lds_b;
+        if (eb != hipSuccess) { pycllp_hip_sparse_free(hb); return set_err((int)eb, "pycllp_hip_sparse_init (large LP)"); }
+        hb->num_cu = lim.num_cu; hb->max_lds = lim.max_lds;
         hb->desc.m = m; hb->desc.n = n; hb->desc.nnz = nnz;
-        const int rc = big_plan_create(m, n, nnz, val.data(), ptr.data(), col.data(), max_lds_b, st, &hb->big);
+        const int rc = big_plan_create(m, n, nnz, val.data(), ptr.data(), col.data(), lim.max_lds, st, &hb->big);
         if (rc != 0) {
-            hb->ring.destroy(); delete hb;
+            pycllp_hip_sparse_free(hb);
             if (rc >= 1000) return set_err(rc - 1000, "big_plan_create");
             return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_init: the LP does not fit the large-LP kernel");
         }
@@ -1007,21 +1023,19 @@ int pycllp_hip_sparse_init(int m, int n, int nnz, const double* Adata_dev, const
 
     pycllp_hip_sparse* h = new (std::nothrow) pycllp_hip_sparse();
     if (!h) return set_err(PYCLLP_E_NOMEM, "pycllp_hip_sparse_init: out of host memory");
-    int dev = 0;
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
-    if (e != hipSuccess) { delete h; return set_err((int)e, "hipGetDeviceProperties"); }
-    h->num_cu = prop.multiProcessorCount;
-    int max_lds = (int)prop.maxSharedMemoryPerMultiProcessor;
-    if (max_lds > 160 * 1024 || max_lds <= 0) max_lds = 160 * 1024;
+    // on failure the partly built handle goes through pycllp_hip_sparse_free, which skips what was not made
+    DeviceLimits lim;
+    hipError_t e = device_limits(&lim);
+    if (e != hipSuccess) { pycllp_hip_sparse_free(h); return set_err((int)e, "hipGetDeviceProperties"); }
+    h->num_cu = lim.num_cu;
+    const int max_lds = lim.max_lds;
     const size_t total = 64 + sizeof(double) * (val.size() + cval.size() + term_w.size()) +
                          sizeof(int) * (ptr.size() + col.size() + cptr.size() + crow.size() + ent_tri.size() + ent_ptr.size() +
                                         term_col.size() + csrc.size() + term_ia.size() + term_ib.size()) + 16 * 16;
     std::vector<char> host(total);
     e = hipMalloc(&h->dev_blob, total);
     if (e == hipSuccess) e = h->ring.create();
-    if (e != hipSuccess) { h->ring.destroy(); if (h->dev_blob) (void)hipFree(h->dev_blob); delete h; return set_err((int)e, "hipMalloc(sparse A)"); }
+    if (e != hipSuccess) { pycllp_hip_sparse_free(h); return set_err((int)e, "hipMalloc(sparse A)"); }
     size_t off = 0;
     char* db = (char*)h->dev_blob;
     BlockA& d = h->desc;
@@ -1036,7 +1050,7 @@ int pycllp_hip_sparse_init(int m, int n, int nnz, const double* Adata_dev, const
     d.n_entries = (int)ent_tri.size(); d.n_terms = (int)terms.size();
     e = hipMemcpyAsync(h->dev_blob, host.data(), off, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(h->dev_blob); h->ring.destroy(); delete h; return set_err((int)e, "upload sparse A"); }
+    if (e != hipSuccess) { pycllp_hip_sparse_free(h); return set_err((int)e, "upload sparse A"); }
     // LDS plan: two workgroups per CU hide each other's LDS latency, so the CSR/CSC copy goes into LDS only when the
     // workgroup still fits in half a CU (or when it cannot be paired anyway)
     const size_t mp8 = ((size_t)m + 7) & ~(size_t)7;
@@ -1049,17 +1063,14 @@ int pycllp_hip_sparse_init(int m, int n, int nnz, const double* Adata_dev, const
     h->lds = (int)(d.a_in_lds ? with_a : base);
     h->lds_with_a = with_a <= (size_t)max_lds ? (int)with_a : 0;
     if ((size_t)h->lds > (size_t)max_lds) {
-        (void)hipFree(h->dev_blob); h->ring.destroy(); delete h;
+        pycllp_hip_sparse_free(h);
         return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_init: problem does not fit in LDS");
     }
     // the register-resident one-LP-per-wavefront kernel takes over whenever its tables fit (ipm_wreg.hip)
     {
         WregPlan* wp = nullptr;
         const int rc = wreg_plan_create(m, n, nnz, val.data(), ptr.data(), col.data(), max_lds, 0, st, &wp);
-        if (rc >= 1000) {
-            (void)hipFree(h->dev_blob); h->ring.destroy(); delete h;
-            return set_err(rc - 1000, "wreg_plan_create");
-        }
+        if (rc >= 1000) { pycllp_hip_sparse_free(h); return set_err(rc - 1000, "wreg_plan_create"); }
         h->wreg = (rc == 0) ? wp : nullptr;
     }
     h->max_lds = max_lds;
@@ -1098,15 +1109,12 @@ static int sparse_solve_impl(pycllp_hip_sparse* h, long B, const double* a_batch
         return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve: PYCLLP_FLAG_PREDCORR is not available on the kernel that serves this LP");
     if (h->big) {
         if (a_batch) return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_batch: per-problem values of A stop at m = 128, n = 512");
-        int* qb = nullptr; unsigned sb_ = 0; int grid_b = 0;
-        hipError_t eb = h->ring.acquire(st, &qb, &sb_);
-        if (eb == hipSuccess) {
-            eb = big_launch_solve(h->big, B, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, qb, o,
-                                  h->num_cu, st, &grid_b);
-            hipError_t er = h->ring.release(sb_, st);
-            if (eb == hipSuccess) eb = er;
-        }
-        { std::lock_guard<std::mutex> g(h->info_mu); h->last_wreg = 0; h->last_plan = nullptr; h->grid = grid_b; }
+        int grid_b = 0;
+        const hipError_t eb = h->ring.run(st, [&](int* qb) {
+            return big_launch_solve(h->big, B, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, qb, o,
+                                    h->num_cu, st, &grid_b);
+        });
+        record_launch(h, nullptr, grid_b);
         if (eb != hipSuccess) return set_err((int)eb, "ipm_big_kernel launch");
         return 0;
     }
@@ -1117,15 +1125,11 @@ static int sparse_solve_impl(pycllp_hip_sparse* h, long B, const double* a_batch
     if (a_batch && h->lds_with_a) { desc.a_in_lds = 1; lds = h->lds_with_a; }
     // per-problem values: the PA plan of the wave kernel (structure tables; built on first use), else the shared-A plan
     if (a_batch && !(o.flags & PYCLLP_FLAG_BLOCK_KERNEL)) {
-        std::lock_guard<std::mutex> g(h->info_mu);
-        if (!h->wreg_pa_tried) {
-            h->wreg_pa_tried = true;
-            WregPlan* wp = nullptr;
-            const int rc = wreg_plan_create(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(), h->host_col.data(),
-                                            h->max_lds, 1, st, &wp);
-            if (rc >= 1000) return set_err(rc - 1000, "wreg_plan_create (per-problem A)");
-            h->wreg_pa = (rc == 0) ? wp : nullptr;
-        }
+        const int rc = lazy_plan(h, &h->wreg_pa, &h->wreg_pa_tried, "wreg_plan_create (per-problem A)", [&](WregPlan** wp) {
+            return wreg_plan_create(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(), h->host_col.data(),
+                                    h->max_lds, 1, st, wp);
+        });
+        if (rc != 0) return rc;
     }
     WregPlan* wplan = a_batch ? h->wreg_pa : h->wreg;
     const bool use_wreg = wplan && !(o.flags & PYCLLP_FLAG_BLOCK_KERNEL);
@@ -1139,14 +1143,10 @@ static int sparse_solve_impl(pycllp_hip_sparse* h, long B, const double* a_batch
     if (use_wreg) {
         // wave kernel first; whatever it defers (guard would have bitten) goes through the block kernel's guarded path
         HIP_TRY(hipMallocAsync((void**)&worklist, sizeof(int) * (size_t)(B + 1), st));
-        int* qw = nullptr; unsigned sw = 0;
-        hipError_t ew = h->ring.acquire(st, &qw, &sw);
-        if (ew == hipSuccess) {
-            ew = wreg_launch_solve(wplan, B, a_batch, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, qw,
-                                   worklist, o, h->num_cu, st, &grid_w);
-            hipError_t er = h->ring.release(sw, st);
-            if (ew == hipSuccess) ew = er;
-        }
+        const hipError_t ew = h->ring.run(st, [&](int* qw) {
+            return wreg_launch_solve(wplan, B, a_batch, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev,
+                                     qw, worklist, o, h->num_cu, st, &grid_w);
+        });
         if (ew != hipSuccess) { (void)hipFreeAsync(worklist, st); return set_err((int)ew, "ipm_wreg_kernel launch"); }
     }
     long blocks = 0;
@@ -1155,7 +1155,7 @@ static int sparse_solve_impl(pycllp_hip_sparse* h, long B, const double* a_batch
         hipLaunchKernelGGL(deferred_to_numerical_kernel, dim3(64), dim3(256), 0, st, worklist, status_dev);
         e = hipGetLastError();
         hipError_t e2 = hipFreeAsync(worklist, st); if (e == hipSuccess) e = e2;
-        { std::lock_guard<std::mutex> g(h->info_mu); h->last_wreg = 1; h->last_plan = wplan; h->grid = grid_w; }
+        record_launch(h, wplan, grid_w);
         if (e != hipSuccess) return set_err((int)e, "deferred_to_numerical_kernel launch");
         return 0;
     }
@@ -1164,22 +1164,13 @@ static int sparse_solve_impl(pycllp_hip_sparse* h, long B, const double* a_batch
     const long free_cus = (long)h->num_cu - o.reserve_cus > 0 ? (long)h->num_cu - o.reserve_cus : 1;
     blocks = free_cus * per_cu;
     if (blocks > B) blocks = B;
-    int* qhead = nullptr; unsigned slot = 0;
-    e = h->ring.acquire(st, &qhead, &slot);
-    if (e == hipSuccess) {
+    e = h->ring.run(st, [&](int* qhead) {
         hipLaunchKernelGGL(ipm_block_kernel, dim3((unsigned)blocks), dim3(BLK_T), lds, st, desc, B, b_dev, c_dev, x_dev,
                            y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, qhead, worklist, 0.0, nullptr, nullptr, a_batch, o);
-        e = hipGetLastError();
-        hipError_t er = h->ring.release(slot, st);
-        if (e == hipSuccess) e = er;
-    }
+        return hipGetLastError();
+    });
     if (worklist) { hipError_t e2 = hipFreeAsync(worklist, st); if (e == hipSuccess) e = e2; }
-    {
-        std::lock_guard<std::mutex> g(h->info_mu);
-        h->last_wreg = use_wreg ? 1 : 0;
-        h->last_plan = use_wreg ? wplan : nullptr;
-        h->grid = use_wreg ? grid_w : (int)blocks;
-    }
+    record_launch(h, use_wreg ? wplan : nullptr, use_wreg ? grid_w : (int)blocks);
     if (e != hipSuccess) return set_err((int)e, "ipm_block_kernel launch");
     return 0;
 }
@@ -1213,33 +1204,23 @@ int pycllp_hip_sparse_solve_bounded(pycllp_hip_sparse* h, long B, const double* 
     if (h->big)
         return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_bounded: the bounded wave kernel stops at m = 128, n = 512");
     hipStream_t st = (hipStream_t)stream;
-    WregPlan* plan = nullptr;
-    {
-        std::lock_guard<std::mutex> g(h->info_mu);
-        if (!h->wreg_bd_tried) {
-            h->wreg_bd_tried = true;
-            WregPlan* wp = nullptr;
-            const int rc = wreg_plan_create_bounded(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(),
-                                                    h->host_col.data(), h->max_lds, st, &wp);
-            if (rc >= 1000) return set_err(rc - 1000, "wreg_plan_create_bounded");
-            h->wreg_bd = (rc == 0) ? wp : nullptr;
-        }
-        plan = h->wreg_bd;
-    }
+    const int rc = lazy_plan(h, &h->wreg_bd, &h->wreg_bd_tried, "wreg_plan_create_bounded", [&](WregPlan** wp) {
+        return wreg_plan_create_bounded(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(), h->host_col.data(),
+                                        h->max_lds, st, wp);
+    });
+    if (rc != 0) return rc;
+    WregPlan* plan = h->wreg_bd;
     if (!plan)
         return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_bounded: no variant of the bounded wave kernel covers this A "
                                              "(rows, columns, or its tables in LDS)");
     if (B == 0) return 0;
     DevOpts o = to_dev(opts);
-    int* qw = nullptr; unsigned sw = 0; int grid = 0;
-    hipError_t e = h->ring.acquire(st, &qw, &sw);
-    if (e == hipSuccess) {
-        e = wreg_launch_solve_bounded(plan, B, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev, status_dev,
-                                      iters_dev, qw, o, h->num_cu, st, &grid);
-        hipError_t er = h->ring.release(sw, st);
-        if (e == hipSuccess) e = er;
-    }
-    { std::lock_guard<std::mutex> g(h->info_mu); h->last_wreg = 1; h->last_plan = plan; h->grid = grid; }
+    int grid = 0;
+    const hipError_t e = h->ring.run(st, [&](int* qw) {
+        return wreg_launch_solve_bounded(plan, B, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev, status_dev,
+                                         iters_dev, qw, o, h->num_cu, st, &grid);
+    });
+    record_launch(h, plan, grid);
     if (e != hipSuccess) return set_err((int)e, "ipm_wreg_bounded_kernel launch");
     return 0;
 }
@@ -1254,13 +1235,9 @@ int pycllp_hip_sparse_newton(pycllp_hip_sparse* h, long B, const double* x_dev, 
     DevOpts o = to_dev(opts);
     hipStream_t st = (hipStream_t)stream;
     if (h->big) {
-        int* qb = nullptr; unsigned sb_ = 0;
-        hipError_t eb = h->ring.acquire(st, &qb, &sb_);
-        if (eb == hipSuccess) {
-            eb = big_launch_newton(h->big, B, x_dev, z_dev, y_dev, b_dev, c_dev, mu, dy_dev, nrefine_dev, qb, o, h->num_cu, st);
-            hipError_t er = h->ring.release(sb_, st);
-            if (eb == hipSuccess) eb = er;
-        }
+        const hipError_t eb = h->ring.run(st, [&](int* qb) {
+            return big_launch_newton(h->big, B, x_dev, z_dev, y_dev, b_dev, c_dev, mu, dy_dev, nrefine_dev, qb, o, h->num_cu, st);
+        });
         if (eb != hipSuccess) return set_err((int)eb, "ipm_big_kernel (Newton mode) launch");
         return 0;
     }
@@ -1274,16 +1251,12 @@ int pycllp_hip_sparse_newton(pycllp_hip_sparse* h, long B, const double* x_dev, 
     const long per_cu = (160 * 1024) / h->lds >= 4 ? 4 : ((160 * 1024) / h->lds >= 2 ? 2 : 1);
     long blocks = (long)h->num_cu * per_cu;
     if (blocks > B) blocks = B;
-    int* qhead = nullptr; unsigned slot = 0;
-    hipError_t e = h->ring.acquire(st, &qhead, &slot);
-    if (e == hipSuccess) {
+    const hipError_t e = h->ring.run(st, [&](int* qhead) {
         hipLaunchKernelGGL(ipm_block_kernel, dim3((unsigned)blocks), dim3(BLK_T), h->lds, st, h->desc, B, b_dev, c_dev,
                            (double*)x_dev, (double*)y_dev, (double*)z_dev, (double*)nullptr, (double*)nullptr, (int*)nullptr,
                            (int*)nullptr, qhead, (const int*)nullptr, mu, dy_dev, nrefine_dev, (const double*)nullptr, o);
-        e = hipGetLastError();
-        hipError_t er = h->ring.release(slot, st);
-        if (e == hipSuccess) e = er;
-    }
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return set_err((int)e, "ipm_block_kernel (Newton mode) launch");
     return 0;
 }
@@ -1292,9 +1265,9 @@ int pycllp_hip_sparse_launch_info(const pycllp_hip_sparse* h, int* grid, int* bl
     if (!h) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_launch_info: bad argument");
     std::lock_guard<std::mutex> g(h->info_mu);
     if (grid) *grid = h->grid;
-    if (block) *block = h->last_wreg ? wreg_block_threads(h->last_plan) : BLK_T;
-    if (lds_bytes) *lds_bytes = h->last_wreg ? wreg_lds_bytes(h->last_plan) : h->lds;
-    if (kernel) *kernel = h->big ? (big_dense_mode(h->big) ? 4 : 3) : (h->last_wreg ? wreg_variant(h->last_plan) : 0);
+    if (block) *block = h->last_plan ? wreg_block_threads(h->last_plan) : BLK_T;
+    if (lds_bytes) *lds_bytes = h->last_plan ? wreg_lds_bytes(h->last_plan) : h->lds;
+    if (kernel) *kernel = h->big ? (big_dense_mode(h->big) ? 4 : 3) : (h->last_plan ? wreg_variant(h->last_plan) : 0);
     return 0;
 }
 

@@ -31,13 +31,14 @@
 //     three pinned values where it is used (WReg::pin): no scratch traffic inside the iteration loop;
 //   * the triangular solves are 16-row block steps: 4 FMAs per off-diagonal block, quad/row reductions by
 //     v_permlane swaps and DPP.
-// Variants (MB 16-row blocks, NQ 64-column N-vector registers; term tables or dense image): see kWVariantsTab / kWVariantsDA.
+// Variants (MB 16-row blocks, NQ 64-column N-vector registers; term tables or dense image): see WREG_TAB_SHAPES / WREG_DA_SHAPES
+// in wreg.h.
 // The Nocedal-Wright guard (ldl.cl:487) is not applied here: the sweep records whether it WOULD have bitten and such an
 // LP (never seen on a positive definite M) is deferred to ipm_block_kernel, which applies it exactly.
 // Semantics = oracle/ipm_dense_ref.c (ipm_one_path / hsd_one_raw), like every other kernel of this library.
 // tools/wreg_sim.py is a lane-level numpy model of the layouts used below.
 #ifndef WREG_PART
-#define WREG_PART 0     // 0: table variants + host code; 1: the dense-image variants only (second translation unit)
+#define WREG_PART 0     // which kernels this translation unit compiles (Makefile: 0 = term tables + all host code, 1..6 = the other kinds)
 #endif
 #include "wreg.h"
 
@@ -1967,9 +1968,6 @@ __global__ void wreg_selftest_kernel(double* out) {
 // ------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------
-#ifndef WREG_PART
-#error "WREG_PART must be defined before this point"
-#endif
 struct WregPlan {
     WregTab tab;
     int mb, nq;
@@ -2018,92 +2016,7 @@ hipError_t do_newton(const WregTab& T, long B, const double* x, const double* z,
     return hipGetLastError();
 }
 
-#define WVARIANT(MB, NQ, DA) { MB, NQ, DA, false, do_solve<MB, NQ, DA, false>, do_solve_hsd<MB, NQ, DA, false>, do_newton<MB, NQ, DA> }
-#define WVARIANT_PA(MB, NQ) { MB, NQ, false, true, do_solve<MB, NQ, false, true>, do_solve_hsd<MB, NQ, false, true>, nullptr }
-// predictor-corrector kernels of the table variants (fourth translation unit): only `solve` is meaningful
-#define WVARIANT_PC(MB, NQ, DA) { MB, NQ, DA, false, do_solve<MB, NQ, DA, false, true>, nullptr, nullptr }
-#define WVARIANT_PCPA(MB, NQ) { MB, NQ, false, true, do_solve<MB, NQ, false, true, true>, nullptr, nullptr }
-// ordered by cost; the first variant of the wanted kind (tables / dense image) with 16 mb >= m and 64 nq >= n is used
-#if WREG_PART == 0
-#ifdef PYCLLP_DEV_ONLY_W86   // development builds: only the (8, 6) table variant (BASELINE config 5), compiles in a fraction of the time
-const WVariant kWVariantsTab[] = { WVARIANT(8, 6, false) };
-#else
-const WVariant kWVariantsTab[] = { WVARIANT(1, 4, false), WVARIANT(2, 4, false), WVARIANT(3, 4, false), WVARIANT(4, 2, false), WVARIANT(4, 4, false), WVARIANT(5, 6, false), WVARIANT(6, 6, false),
-                                   WVARIANT(7, 6, false), WVARIANT(8, 4, false), WVARIANT(8, 6, false), WVARIANT(8, 8, false) };
-#endif
-const int kNumWVariantsTab = sizeof(kWVariantsTab) / sizeof(kWVariantsTab[0]);
-const int kNumWVariants = kNumWVariantsTab + kNumWVariantsDA + kNumWVariantsPA;
-struct VariantList {
-    const WVariant& operator[](int i) const {
-        return i < kNumWVariantsTab ? kWVariantsTab[i]
-             : (i < kNumWVariantsTab + kNumWVariantsDA ? kWVariantsDA[i - kNumWVariantsTab] : kWVariantsPA[i - kNumWVariantsTab - kNumWVariantsDA]);
-    }
-};
-const VariantList kWVariants{};
-#endif
-
-}  // namespace
-
-#if WREG_PART == 1
-#define WVARIANTS_DA { WVARIANT(1, 4, true), WVARIANT(2, 4, true), WVARIANT(3, 4, true), WVARIANT(4, 2, true), WVARIANT(4, 4, true), WVARIANT(5, 4, true), WVARIANT(6, 4, true), \
-                       WVARIANT(7, 4, true), WVARIANT(8, 4, true), WVARIANT(8, 6, true) }
-#ifdef __HIP_DEVICE_COMPILE__
-// device pass: a file-local copy of the table -- it is never emitted, but referencing the launchers is what makes the kernels
-// they launch get instantiated (an external table of host function pointers would be emitted into the device object and
-// fail to link there)
-namespace { [[maybe_unused]] const WVariant kWVariantsDA_instantiate[] = WVARIANTS_DA; }
-#else
-extern const WVariant kWVariantsDA[] = WVARIANTS_DA;
-extern const int kNumWVariantsDA = sizeof(kWVariantsDA) / sizeof(kWVariantsDA[0]);
-#endif
-#endif
-#if WREG_PART == 2
-// per-problem values of A: every (MB, NQ) of the table variants, solve + HSD kernels (third translation unit)
-#define WVARIANTS_PA { WVARIANT_PA(1, 4), WVARIANT_PA(2, 4), WVARIANT_PA(3, 4), WVARIANT_PA(4, 2), WVARIANT_PA(4, 4), WVARIANT_PA(5, 6), \
-                       WVARIANT_PA(6, 6), WVARIANT_PA(7, 6), WVARIANT_PA(8, 4), WVARIANT_PA(8, 6), WVARIANT_PA(8, 8) }
-#ifdef __HIP_DEVICE_COMPILE__
-namespace { [[maybe_unused]] const WVariant kWVariantsPA_instantiate[] = WVARIANTS_PA; }
-#else
-extern const WVariant kWVariantsPA[] = WVARIANTS_PA;
-extern const int kNumWVariantsPA = sizeof(kWVariantsPA) / sizeof(kWVariantsPA[0]);
-#endif
-#endif
-#if WREG_PART == 3
-#define WVARIANTS_PC { WVARIANT_PC(1, 4, false), WVARIANT_PC(2, 4, false), WVARIANT_PC(3, 4, false), WVARIANT_PC(4, 2, false), WVARIANT_PC(4, 4, false), \
-                       WVARIANT_PC(5, 6, false), WVARIANT_PC(6, 6, false), WVARIANT_PC(7, 6, false), WVARIANT_PC(8, 4, false), WVARIANT_PC(8, 6, false), \
-                       WVARIANT_PC(8, 8, false) }
-#ifdef __HIP_DEVICE_COMPILE__
-namespace { [[maybe_unused]] const WVariant kWVariantsPC_instantiate[] = WVARIANTS_PC; }
-#else
-extern const WVariant kWVariantsPC[] = WVARIANTS_PC;
-extern const int kNumWVariantsPC = sizeof(kWVariantsPC) / sizeof(kWVariantsPC[0]);
-#endif
-#endif
-#if WREG_PART == 4
-// predictor-corrector kernels of the dense-image variants (fifth translation unit)
-#define WVARIANTS_PCDA { WVARIANT_PC(1, 4, true), WVARIANT_PC(2, 4, true), WVARIANT_PC(3, 4, true), WVARIANT_PC(4, 2, true), WVARIANT_PC(4, 4, true), \
-                         WVARIANT_PC(5, 4, true), WVARIANT_PC(6, 4, true), WVARIANT_PC(7, 4, true), WVARIANT_PC(8, 4, true), WVARIANT_PC(8, 6, true) }
-#ifdef __HIP_DEVICE_COMPILE__
-namespace { [[maybe_unused]] const WVariant kWVariantsPCDA_instantiate[] = WVARIANTS_PCDA; }
-#else
-extern const WVariant kWVariantsPCDA[] = WVARIANTS_PCDA;
-extern const int kNumWVariantsPCDA = sizeof(kWVariantsPCDA) / sizeof(kWVariantsPCDA[0]);
-#endif
-#endif
-#if WREG_PART == 5
-// predictor-corrector kernels of the per-problem-A variants (sixth translation unit)
-#define WVARIANTS_PCPA { WVARIANT_PCPA(1, 4), WVARIANT_PCPA(2, 4), WVARIANT_PCPA(3, 4), WVARIANT_PCPA(4, 2), WVARIANT_PCPA(4, 4), WVARIANT_PCPA(5, 6), \
-                         WVARIANT_PCPA(6, 6), WVARIANT_PCPA(7, 6), WVARIANT_PCPA(8, 4), WVARIANT_PCPA(8, 6), WVARIANT_PCPA(8, 8) }
-#ifdef __HIP_DEVICE_COMPILE__
-namespace { [[maybe_unused]] const WVariant kWVariantsPCPA_instantiate[] = WVARIANTS_PCPA; }
-#else
-extern const WVariant kWVariantsPCPA[] = WVARIANTS_PCPA;
-extern const int kNumWVariantsPCPA = sizeof(kWVariantsPCPA) / sizeof(kWVariantsPCPA[0]);
-#endif
-#endif
 #if WREG_PART == 6
-// the bounded kernel (ipm_wreg_bounded.inc) on the table and dense-image geometries (seventh translation unit); the plan of
-// wreg_plan_create_bounded picks the first variant of the wanted kind that covers (m, n), as for the other kernels
 template <int MB, int NQ, bool DA>
 hipError_t do_solve_bounded(const WregTab& T, long B, const double* b, const double* c, const double* u, double* x, double* y,
                             double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead, DevOpts o,
@@ -2114,21 +2027,67 @@ hipError_t do_solve_bounded(const WregTab& T, long B, const double* b, const dou
                        s, pobj, dobj, status, iters, qhead, o);
     return hipGetLastError();
 }
-#define WVARIANT_BD(MB, NQ, DA) { MB, NQ, DA, do_solve_bounded<MB, NQ, DA> }
-#define WVARIANTS_BD { WVARIANT_BD(1, 4, false), WVARIANT_BD(2, 4, false), WVARIANT_BD(3, 4, false), WVARIANT_BD(4, 2, false), \
-                       WVARIANT_BD(4, 4, false), WVARIANT_BD(5, 6, false), WVARIANT_BD(6, 6, false), WVARIANT_BD(7, 6, false), \
-                       WVARIANT_BD(8, 4, false), WVARIANT_BD(8, 6, false), WVARIANT_BD(8, 8, false), \
-                       WVARIANT_BD(1, 4, true), WVARIANT_BD(2, 4, true), WVARIANT_BD(3, 4, true), WVARIANT_BD(4, 2, true), \
-                       WVARIANT_BD(4, 4, true), WVARIANT_BD(5, 4, true), WVARIANT_BD(6, 4, true), WVARIANT_BD(7, 4, true), \
-                       WVARIANT_BD(8, 4, true), WVARIANT_BD(8, 6, true) }
+#endif
+
+}  // namespace
+
+// The launcher table of one kernel kind, over one of the shape lists of wreg.h.  The device pass gets a file-local copy: it
+// is never emitted, but referencing the launchers is what makes the kernels they launch get instantiated (an external table
+// of host function pointers would be emitted into the device object and fail to link there).
 #ifdef __HIP_DEVICE_COMPILE__
-namespace { [[maybe_unused]] const WBVariant kWVariantsBD_instantiate[] = WVARIANTS_BD; }
+#define WREG_TABLE(NAME, SHAPES, ENTRY) namespace { [[maybe_unused]] const WVariant NAME##_instantiate[] = { SHAPES(ENTRY) }; }
 #else
-extern const WBVariant kWVariantsBD[] = WVARIANTS_BD;
-extern const int kNumWVariantsBD = sizeof(kWVariantsBD) / sizeof(kWVariantsBD[0]);
+#define WREG_TABLE(NAME, SHAPES, ENTRY)                                                                                      \
+    namespace { const WVariant NAME##_v[] = { SHAPES(ENTRY) }; }                                                            \
+    extern const WVariants NAME = { NAME##_v, (int)(sizeof(NAME##_v) / sizeof(NAME##_v[0])) };
 #endif
-#endif
+#define WV_PLAIN(MB, NQ, DA) { MB, NQ, do_solve<MB, NQ, DA, false>, do_solve_hsd<MB, NQ, DA, false>, do_newton<MB, NQ, DA>, nullptr },
 #if WREG_PART == 0
+#define WV_TAB(MB, NQ) WV_PLAIN(MB, NQ, false)
+#ifdef PYCLLP_DEV_ONLY_W86   // development builds: only the (8, 6) table variant (BASELINE config 5), compiles in a fraction of the time
+#define WREG_W86_SHAPES(X) X(8, 6)
+WREG_TABLE(kWTab, WREG_W86_SHAPES, WV_TAB)
+#else
+WREG_TABLE(kWTab, WREG_TAB_SHAPES, WV_TAB)
+#endif
+#elif WREG_PART == 1
+#define WV_DA(MB, NQ) WV_PLAIN(MB, NQ, true)
+WREG_TABLE(kWDA, WREG_DA_SHAPES, WV_DA)
+#elif WREG_PART == 2
+// per-problem values of A: every (MB, NQ) of the table variants, solve + HSD kernels
+#define WV_PA(MB, NQ) { MB, NQ, do_solve<MB, NQ, false, true>, do_solve_hsd<MB, NQ, false, true>, nullptr, nullptr },
+WREG_TABLE(kWPA, WREG_TAB_SHAPES, WV_PA)
+#elif WREG_PART == 3
+#define WV_PC(MB, NQ) { MB, NQ, do_solve<MB, NQ, false, false, true>, nullptr, nullptr, nullptr },
+WREG_TABLE(kWPC, WREG_TAB_SHAPES, WV_PC)
+#elif WREG_PART == 4
+#define WV_PCDA(MB, NQ) { MB, NQ, do_solve<MB, NQ, true, false, true>, nullptr, nullptr, nullptr },
+WREG_TABLE(kWPCDA, WREG_DA_SHAPES, WV_PCDA)
+#elif WREG_PART == 5
+#define WV_PCPA(MB, NQ) { MB, NQ, do_solve<MB, NQ, false, true, true>, nullptr, nullptr, nullptr },
+WREG_TABLE(kWPCPA, WREG_TAB_SHAPES, WV_PCPA)
+#elif WREG_PART == 6
+#define WV_BD(MB, NQ) { MB, NQ, nullptr, nullptr, nullptr, do_solve_bounded<MB, NQ, false> },
+#define WV_BDDA(MB, NQ) { MB, NQ, nullptr, nullptr, nullptr, do_solve_bounded<MB, NQ, true> },
+WREG_TABLE(kWBD, WREG_TAB_SHAPES, WV_BD)
+WREG_TABLE(kWBDDA, WREG_DA_SHAPES, WV_BDDA)
+#endif
+
+#if WREG_PART == 0
+
+// the launcher table of a plan's kind; pc: its predictor-corrector kernels (plans of the bounded kernel have none)
+static const WVariants& table_of(bool da, bool pa, bool bd, bool pc = false) {
+    if (bd) return da ? kWBDDA : kWBD;
+    if (pc) return pa ? kWPCPA : (da ? kWPCDA : kWPC);
+    return pa ? kWPA : (da ? kWDA : kWTab);
+}
+
+// the first variant of a table (ordered by cost) that covers (m, n), or null
+static const WVariant* first_covering(const WVariants& t, int m, int n) {
+    for (int i = 0; i < t.n; i++)
+        if (m <= 16 * t.v[i].mb && n <= 64 * t.v[i].nq) return &t.v[i];
+    return nullptr;
+}
 
 // Plan with A as a dense image in LDS (no tables): for matrices whose Gram term list does not fit -- dense A's, e.g. the LPs
 // hip_dense_primal_normal hands over beyond m = 32.  The last m columns are kept out of the image when they are the
@@ -2136,15 +2095,9 @@ extern const int kNumWVariantsBD = sizeof(kWVariantsBD) / sizeof(kWVariantsBD[0]
 // bd: the plan of the bounded kernel (its variants; t and s behind every wave area)
 static int wreg_plan_create_dense(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
                                   bool bd, hipStream_t st, WregPlan** out) {
-    int MB = 0, NQ = 0;
-    if (bd) {
-        for (int i = 0; i < kNumWVariantsBD; i++)
-            if (kWVariantsBD[i].da && m <= 16 * kWVariantsBD[i].mb && n <= 64 * kWVariantsBD[i].nq) { MB = kWVariantsBD[i].mb; NQ = kWVariantsBD[i].nq; break; }
-    } else {
-        for (int i = 0; i < kNumWVariants; i++)
-            if (kWVariants[i].da && !kWVariants[i].pa && m <= 16 * kWVariants[i].mb && n <= 64 * kWVariants[i].nq) { MB = kWVariants[i].mb; NQ = kWVariants[i].nq; break; }
-    }
-    if (!MB) return 1;
+    const WVariant* v = first_covering(table_of(true, false, bd), m, n);
+    if (!v) return 1;
+    const int MB = v->mb, NQ = v->nq;
     const int MP = 16 * MB;
     // identity tail?
     bool sl = n > m;
@@ -2203,15 +2156,9 @@ int wreg_plan_create_bounded(int m, int n, int nnz, const double* val, const int
 // area, fewer waves per workgroup where that is what lets the tables fit)
 static int wreg_plan_create_tables(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
                                    bool pa, bool bd, hipStream_t st, WregPlan** out) {
-    int MB = 0, NQ = 0;
-    if (bd) {
-        for (int i = 0; i < kNumWVariantsBD; i++)
-            if (!kWVariantsBD[i].da && m <= 16 * kWVariantsBD[i].mb && n <= 64 * kWVariantsBD[i].nq) { MB = kWVariantsBD[i].mb; NQ = kWVariantsBD[i].nq; break; }
-    } else {
-        for (int i = 0; i < kNumWVariants; i++)
-            if (!kWVariants[i].da && kWVariants[i].pa == pa && m <= 16 * kWVariants[i].mb && n <= 64 * kWVariants[i].nq) { MB = kWVariants[i].mb; NQ = kWVariants[i].nq; break; }
-    }
-    if (!MB || nnz >= 65535) return 1;
+    const WVariant* v = first_covering(table_of(false, pa, bd), m, n);
+    if (!v || nnz >= 65535) return 1;
+    const int MB = v->mb, NQ = v->nq;
     const int MP = 16 * MB, MPL = 64 * ((MP + 63) / 64), NP = 64 * NQ;
     WregPlan* P = new WregPlan();
     WregTab& T = P->tab;
@@ -2401,57 +2348,55 @@ int wreg_block_threads(const WregPlan* p) { return p ? 64 * p->tab.wpb : 0; }
 int wreg_variant(const WregPlan* p) { return p ? (p->da ? 2 : 1) : 0; }
 int wreg_has_predcorr(const WregPlan* p) { return p ? 1 : 0; }
 
-static const WVariant* find_variant(const WregPlan* p) {
-    if (p->bd) return nullptr;
-    for (int i = 0; i < kNumWVariants; i++)
-        if (kWVariants[i].mb == p->mb && kWVariants[i].nq == p->nq && kWVariants[i].da == p->da && kWVariants[i].pa == p->pa) return &kWVariants[i];
+// the launchers of the plan's (MB, NQ) among the plain (pc: predictor-corrector, bd: bounded) kernels of its kind, or null
+static const WVariant* plan_launchers(const WregPlan* p, bool bd, bool pc = false) {
+    if (!p || p->bd != bd) return nullptr;
+    const WVariants& t = table_of(p->da, p->pa, p->bd, pc);
+    for (int i = 0; i < t.n; i++)
+        if (t.v[i].mb == p->mb && t.v[i].nq == p->nq) return &t.v[i];
     return nullptr;
+}
+
+// persistent grid of the solve kernels: one workgroup per CU left to the solve; the m <= 64 variants need fewer than half the
+// registers (234 of 512 per lane): two workgroups per CU -- two waves per SIMD -- where the LDS allows it
+static int solve_grid(const WregPlan* p, long B, const DevOpts& o, int num_cu) {
+    long cus = (long)num_cu - o.reserve_cus > 0 ? (long)num_cu - o.reserve_cus : 1;
+    if (p->mb <= 4 && 2 * (long)p->tab.lds_bytes <= 160 * 1024 && p->tab.wpb == 4) cus *= 2;
+    const long grid = std::min(cus, (B + p->tab.wpb - 1) / p->tab.wpb);
+    return grid < 1 ? 1 : (int)grid;
 }
 
 hipError_t wreg_launch_solve(WregPlan* p, long B, const double* a_batch, const double* b, const double* c, double* x, double* y, double* z,
                              double* pobj, double* dobj, int* status, int* iters, int* qhead, int* defer, DevOpts o,
                              int num_cu, hipStream_t st, int* grid_out) {
-    const WVariant* v = find_variant(p);
+    const WVariant* v = plan_launchers(p, false);
     if (!v || (p->pa != (a_batch != nullptr))) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(defer, 0, sizeof(int), st);
     if (e != hipSuccess) return e;
-    long cus = (long)num_cu - o.reserve_cus > 0 ? (long)num_cu - o.reserve_cus : 1;
-    // the m <= 64 variants need fewer than half the registers (234 of 512 per lane): two workgroups per CU -- two waves per
-    // SIMD -- where the LDS allows it
-    if (p->mb <= 4 && 2 * (long)p->tab.lds_bytes <= 160 * 1024 && p->tab.wpb == 4) cus *= 2;
-    long grid = std::min(cus, (B + p->tab.wpb - 1) / p->tab.wpb);
-    if (grid < 1) grid = 1;
-    if (grid_out) *grid_out = (int)grid;
+    const int grid = solve_grid(p, B, o, num_cu);
+    if (grid_out) *grid_out = grid;
     wsolve_fn fn = (o.flags & PYCLLP_FLAG_HSD) ? v->solve_hsd : v->solve;
     if ((o.flags & PYCLLP_FLAG_PREDCORR) && !(o.flags & PYCLLP_FLAG_HSD)) {
-        fn = nullptr;
-        const WVariant* list = p->pa ? kWVariantsPCPA : (p->da ? kWVariantsPCDA : kWVariantsPC);
-        const int nlist = p->pa ? kNumWVariantsPCPA : (p->da ? kNumWVariantsPCDA : kNumWVariantsPC);
-        for (int i = 0; i < nlist; i++)
-            if (list[i].mb == p->mb && list[i].nq == p->nq) fn = list[i].solve;
-        if (!fn) return hipErrorNotSupported;
+        const WVariant* pc = plan_launchers(p, false, true);
+        if (!pc) return hipErrorNotSupported;
+        fn = pc->solve;
     }
-    return fn(p->tab, B, a_batch, b, c, x, y, z, pobj, dobj, status, iters, qhead, defer, o, (int)grid, st);
+    return fn(p->tab, B, a_batch, b, c, x, y, z, pobj, dobj, status, iters, qhead, defer, o, grid, st);
 }
 
 hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* b, const double* c, const double* u, double* x, double* y,
                                      double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead,
                                      DevOpts o, int num_cu, hipStream_t st, int* grid_out) {
-    wbsolve_fn fn = nullptr;
-    for (int i = 0; p && p->bd && i < kNumWVariantsBD; i++)
-        if (kWVariantsBD[i].mb == p->mb && kWVariantsBD[i].nq == p->nq && kWVariantsBD[i].da == p->da) fn = kWVariantsBD[i].solve;
-    if (!fn) return hipErrorInvalidValue;
-    long cus = (long)num_cu - o.reserve_cus > 0 ? (long)num_cu - o.reserve_cus : 1;
-    if (p->mb <= 4 && 2 * (long)p->tab.lds_bytes <= 160 * 1024 && p->tab.wpb == 4) cus *= 2;     // as wreg_launch_solve
-    long grid = std::min(cus, (B + p->tab.wpb - 1) / p->tab.wpb);
-    if (grid < 1) grid = 1;
-    if (grid_out) *grid_out = (int)grid;
-    return fn(p->tab, B, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o, (int)grid, st);
+    const WVariant* v = plan_launchers(p, true);
+    if (!v) return hipErrorInvalidValue;
+    const int grid = solve_grid(p, B, o, num_cu);
+    if (grid_out) *grid_out = grid;
+    return v->solve_bounded(p->tab, B, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o, grid, st);
 }
 
 hipError_t wreg_launch_newton(WregPlan* p, long B, const double* x, const double* z, const double* y, const double* b,
                               const double* c, double mu, double* dy, int* nref, DevOpts o, int num_cu, hipStream_t st) {
-    const WVariant* v = find_variant(p);
+    const WVariant* v = plan_launchers(p, false);
     if (!v || !v->newton) return hipErrorInvalidValue;
     int* qhead = nullptr;
     hipError_t e = hipMallocAsync((void**)&qhead, sizeof(int), st);

@@ -4,7 +4,7 @@
 #define PYCLLP_WREG_H
 #include "wave_common.h"
 
-// ---- shared between the translation units the wave kernels are compiled in (ipm_wreg.hip, twice: WREG_PART 0 / 1) ----
+// ---- shared between the translation units the wave kernels are compiled in (ipm_wreg.hip, seven times: WREG_PART 0..6) ----
 constexpr int MAX_NQ = 8;
 constexpr int META_COFF = MAX_NQ, META_SEG = 2 * MAX_NQ, META_N = META_SEG + 16;
 
@@ -48,27 +48,29 @@ typedef hipError_t (*wsolve_fn)(const WregTab&, long, const double*, const doubl
                                 double*, double*, int*, int*, int*, int*, DevOpts, int, hipStream_t);
 typedef hipError_t (*wnewton_fn)(const WregTab&, long, const double*, const double*, const double*, const double*,
                                  const double*, double, double*, int*, int*, DevOpts, int, hipStream_t);
-
-struct WVariant { int mb, nq; bool da, pa; wsolve_fn solve, solve_hsd; wnewton_fn newton; };
-// the dense-image variants live in the second translation unit (same source, -DWREG_PART=1), the per-problem-A variants
-// in the third (-DWREG_PART=2), compiled in parallel
-extern const WVariant kWVariantsDA[];
-extern const int kNumWVariantsDA;
-extern const WVariant kWVariantsPA[];
-extern const int kNumWVariantsPA;
-extern const WVariant kWVariantsPC[];      // predictor-corrector kernels of the table variants (-DWREG_PART=3)
-extern const int kNumWVariantsPC;
-extern const WVariant kWVariantsPCDA[];    // ... and of the dense-image variants (-DWREG_PART=4)
-extern const int kNumWVariantsPCDA;
-extern const WVariant kWVariantsPCPA[];    // ... and of the per-problem-A variants (-DWREG_PART=5)
-extern const int kNumWVariantsPCPA;
-
-// the kernel for LPs with upper bounds (ipm_wreg_bounded.inc, -DWREG_PART=6): argument meaning of pycllp_hip_sparse_solve_bounded
+// the kernel for LPs with upper bounds (ipm_wreg_bounded.inc): argument meaning of pycllp_hip_sparse_solve_bounded
 typedef hipError_t (*wbsolve_fn)(const WregTab&, long, const double*, const double*, const double*, double*, double*, double*,
                                  double*, double*, double*, int*, int*, int*, DevOpts, int, hipStream_t);
-struct WBVariant { int mb, nq; bool da; wbsolve_fn solve; };
-extern const WBVariant kWVariantsBD[];
-extern const int kNumWVariantsBD;
+
+// The (MB, NQ) geometries of the wave kernels (MB 16-row blocks, NQ 64-column N-vector registers), ordered by cost: a plan
+// takes the first of its kind with 16 MB >= m and 64 NQ >= n.  One list for the kernels on term tables, one for those on a
+// dense image; every table below is derived from one of them.
+#define WREG_TAB_SHAPES(X) X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 6) X(6, 6) X(7, 6) X(8, 4) X(8, 6) X(8, 8)
+#define WREG_DA_SHAPES(X)  X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4) X(8, 6)
+
+// The launchers of one (MB, NQ) of one kernel kind; a launcher the kind does not have is null.
+struct WVariant { int mb, nq; wsolve_fn solve, solve_hsd; wnewton_fn newton; wbsolve_fn solve_bounded; };
+struct WVariants { const WVariant* v; int n; };
+// One table per kind, each defined by the translation unit (ipm_wreg.hip, -DWREG_PART=k) that compiles its kernels;
+// launchers are matched across tables by (MB, NQ), never by position.
+extern const WVariants kWTab;      // 0: term tables (plain, HSD, Newton)
+extern const WVariants kWDA;       // 1: dense image (plain, HSD, Newton)
+extern const WVariants kWPA;       // 2: per-problem A on structure tables (plain, HSD)
+extern const WVariants kWPC;       // 3: predictor-corrector kernels of kWTab's kind
+extern const WVariants kWPCDA;     // 4: ... of kWDA's kind
+extern const WVariants kWPCPA;     // 5: ... of kWPA's kind
+extern const WVariants kWBD;       // 6: upper bounds, term tables
+extern const WVariants kWBDDA;     // 6: upper bounds, dense image
 
 struct WregPlan;   // host tables + device copies for one shared constraint matrix
 

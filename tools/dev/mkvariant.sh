@@ -7,7 +7,9 @@ cd "$(dirname "$0")/../.."
 name=$1; shift
 mkdir -p proflib
 C=pycllp_amd/csrc
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -DPYCLLP_DEV_ONLY_3296 "$@" -c -o /tmp/dense_$name.o $C/ipm_dense.hip
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o proflib/$name.so /tmp/dense_$name.o $C/ipm_wreg.o $C/ipm_wreg_da.o $C/ipm_wreg_pa.o \
-    $C/ipm_wreg_pc.o $C/ipm_wreg_pcda.o $C/ipm_wreg_pcpa.o $C/ipm_big.o
+T=$(mktemp -d); trap 'rm -rf "$T"' EXIT
+/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -DPYCLLP_DEV_ONLY_3296 "$@" -c -o $T/ipm_dense.o $C/ipm_dense.hip
+# the product's object list (the Makefile's), with the object rebuilt above in place of its own
+objs=$(for o in $(make -s --no-print-directory -C $C print-objs); do [ -f $T/${o##*/} ] && echo $T/${o##*/} || echo $o; done)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o proflib/$name.so $objs
 echo built proflib/$name.so
