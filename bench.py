@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- LPs solved/sec on BASELINE.json's headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,13 +11,18 @@ rank 0 (RCCL).  Workload per GPU: 65 536 random dense LPs, StandardLP (m=32, n=6
 (BASELINE.json configs[2]; with 8 GPUs this is configs[3], 524 288 LPs).  Weak scaling: per-GPU work is fixed.
 
 Rank 0 prints ONE JSON line.  `roofline` prices the solve kernel against the FP64 FMA/MFMA peak (the path is
-compute bound: ~1500 flop per compulsory HBM byte, SURVEY section 8d) and also reports the algorithmic HBM rate;
-`cpu_baseline` is the reference's own CPU solver (pycllp/ipo.py -> ipo/hsd.c, built from the reference sources
-into oracle/_ref) timed on one host core on a bounded sample of the same workload.
+compute bound: ~1500 flop per compulsory HBM byte) and also reports the algorithmic HBM rate.
 
-With one GPU and the default workload the line also carries `secondary`: the other single-GPU configurations of this
-path (configs[1] 4 096 x (16, 32); configs[4]'s per-GPU share on the reference's algorithm and on the homogeneous
-self-dual variant; per-problem values of A on that structure; a dense LP beyond the lane-group kernels, m = 100) --
+A plain run does only what the headline needs: set up, warm up, time the steps, dump the outputs if asked, print the line.
+Everything else runs with --full only, and is null in a plain run's line: `parity`, the objectives of the solver on the
+committed golden vectors of the reference solver; `cpu_baseline`, the reference's own CPU solver (pycllp/ipo.py ->
+ipo/hsd.c, built from the reference sources into oracle/_ref) timed on one host core on a bounded sample of the same
+workload, and `cpu_port`, the oracle restatement on the host (both left out with --no-cpu-baseline).
+
+With --full, one GPU and the default workload the line also carries `secondary` (left out with --no-secondary): the other
+single-GPU configurations of this path (configs[1] 4 096 x (16, 32); configs[4]'s per-GPU share on the reference's
+algorithm and on the homogeneous self-dual variant; per-problem values of A on that structure; a dense LP beyond the
+lane-group kernels, m = 100) --
 each measured the same way (the same --steps and --warmup, resident inputs, HIP events around the launches,
 barrier-free wall clock with a device synchronise either side), each with its own roofline figures, its parity against
 the committed golden vectors of the reference solver and the reference solver's own time on a bounded sample of THAT
@@ -392,8 +397,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="LPs per GPU (default: the BASELINE workload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline record only (no `secondary` list)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: golden parity, the CPU legs and (one GPU, default workload) the `secondary` "
+                         "records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU legs")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no `secondary` list")
     ap.add_argument("--hsd", action="store_true", help="time the homogeneous self-dual variant (PYCLLP_FLAG_HSD) of --workload")
     ap.add_argument("--predcorr", action="store_true", help="time the predictor-corrector option (PYCLLP_FLAG_PREDCORR) of --workload")
     ap.add_argument("--workload", choices=("dense3", "sparse5", "perA", "dense2", "dense100", "dense200"), default="dense3",
@@ -460,7 +468,7 @@ def main():
     sparse, per_a, m_, n_ = wl.sparse, wl.per_a, wl.m, wl.n
 
     cpu = cpu_all = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if args.workload == "dense3":
             cpu = cpu_baseline()
             cpu_all = cpu_port(cpu["value"] if cpu["kind"] == "reference" else None)
@@ -538,7 +546,7 @@ def main():
         ok_total, iters_mean = ok_local, float(iters.mean())
 
     if rank == 0:
-        parity = wl.parity()     # on the committed golden LPs (outside the timed region)
+        parity = wl.parity() if args.full else None     # on the committed golden LPs (outside the timed region)
         total = B * world * args.steps
         value = total / elapsed
         out = {
@@ -556,8 +564,8 @@ def main():
             "cpu_baseline": cpu,
             "cpu_port": cpu_all,
         }
-        if (world == 1 and not multi and args.workload == "dense3" and not args.hsd and not args.predcorr and not args.no_secondary
-                and B == B_PER_GPU):
+        if (args.full and world == 1 and not multi and args.workload == "dense3" and not args.hsd and not args.predcorr
+                and not args.no_secondary and B == B_PER_GPU):
             # the other single-GPU configurations under the same clock (records; `value` above stays the headline's)
             del wl
             sec, cpu5 = [], None
