@@ -10,18 +10,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PYCLLP_HIP_LIB lets a developer point at a diagnostic build of the SAME library (tools/phase_profile.py)
 LIB_PATH = os.environ.get("PYCLLP_HIP_LIB") or os.path.join(_HERE, "csrc", "libpycllp_hip.so")
 
-# every symbol include/pycllp_hip.h declares (tests/test_abi.py checks the two stay in sync)
-EXPORTS = (
-    "pycllp_hip_abi_version", "pycllp_hip_last_error", "pycllp_hip_default_opts",
-    "pycllp_hip_dense_max_rows", "pycllp_hip_dense_max_cols", "pycllp_hip_dense_init",
-    "pycllp_hip_dense_solve", "pycllp_hip_dense_solve_bounded", "pycllp_hip_dense_newton", "pycllp_hip_dense_launch_info",
-    "pycllp_hip_dense_free", "pycllp_hip_ldl", "pycllp_hip_dense_kernel_kind",
-    "pycllp_hip_sparse_max_rows", "pycllp_hip_sparse_max_cols", "pycllp_hip_sparse_init", "pycllp_hip_sparse_solve",
-    "pycllp_hip_sparse_free", "pycllp_hip_sparse_newton", "pycllp_hip_sparse_launch_info",
-    "pycllp_hip_ldl_solve", "pycllp_hip_forward_backward_ldl", "pycllp_hip_sparse_solve_batch",
-    "pycllp_hip_sparse_solve_bounded",
-)
-
 STATUS_OPTIMAL, STATUS_PRIMAL_INFEASIBLE, STATUS_NUMERICAL, STATUS_DUAL_INFEASIBLE, STATUS_ITERATION_LIMIT = 0, 2, 3, 4, 5
 FLAG_WARM_START, FLAG_WAVE_KERNEL, FLAG_FORCE_GUARD_PATH, FLAG_AUTOSCALE, FLAG_NO_SLACK_PATH = 1, 2, 4, 8, 16
 FLAG_HSD = 32
@@ -37,6 +25,40 @@ class Opts(ctypes.Structure):
                 ("reserve_cus", ctypes.c_int)]
 
 
+_i, _l, _d, _p = ctypes.c_int, ctypes.c_long, ctypes.c_double, ctypes.c_void_p     # _p: a device array, a handle, a stream
+_O, _ip, _pp = ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)
+
+
+def _solve(arrays):
+    """handle, B, the device arrays, opts, stream: the solve entries."""
+    return [_p, _l] + [_p] * arrays + [_O, _p]
+
+
+# (symbol, argument types, result type) of every symbol include/pycllp_hip.h declares (tests/test_abi.py checks the two
+# stay in sync)
+SIGNATURES = (
+    ("pycllp_hip_abi_version", [], _i), ("pycllp_hip_last_error", [], ctypes.c_char_p),
+    ("pycllp_hip_default_opts", [_O], None),
+    ("pycllp_hip_dense_max_rows", [], _i), ("pycllp_hip_dense_max_cols", [], _i),
+    ("pycllp_hip_dense_init", [_i, _i, _p, _p, _pp], _i),
+    ("pycllp_hip_dense_solve", _solve(9), _i),                  # b, c, x, y, z, pobj, dobj, status, iters
+    ("pycllp_hip_dense_solve_bounded", _solve(11), _i),         # b, c, u, x, y, z, s, pobj, dobj, status, iters
+    ("pycllp_hip_dense_newton", [_p, _l, _p, _p, _p, _p, _p, _d, _p, _p, _O, _p], _i),
+    ("pycllp_hip_dense_launch_info", [_p] + [_ip] * 5, _i), ("pycllp_hip_dense_kernel_kind", [_p], _i),
+    ("pycllp_hip_dense_free", [_p], None),
+    ("pycllp_hip_ldl", [_i, _l, _p, _p, _p, _i, _d, _d, _p], _i),
+    ("pycllp_hip_ldl_solve", [_i, _l, _p, _p, _p, _i, _d, _d, _p], _i),
+    ("pycllp_hip_forward_backward_ldl", [_i, _l, _p, _p, _p, _p, _p], _i),
+    ("pycllp_hip_sparse_max_rows", [], _i), ("pycllp_hip_sparse_max_cols", [], _i),
+    ("pycllp_hip_sparse_init", [_i, _i, _i, _p, _p, _p, _p, _pp], _i),
+    ("pycllp_hip_sparse_solve", _solve(9), _i),
+    ("pycllp_hip_sparse_solve_batch", _solve(10), _i),          # A's values first
+    ("pycllp_hip_sparse_solve_bounded", _solve(11), _i),
+    ("pycllp_hip_sparse_newton", [_p, _l, _p, _p, _p, _p, _p, _d, _p, _p, _O, _p], _i),
+    ("pycllp_hip_sparse_launch_info", [_p] + [_ip] * 4, _i), ("pycllp_hip_sparse_free", [_p], None),
+)
+EXPORTS = tuple(name for name, _, _ in SIGNATURES)
+
 _lib = None
 
 
@@ -49,54 +71,9 @@ def lib():
             "pycllp_amd: HIP library %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C pycllp_amd/csrc` (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    vp, dp, ip = ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p
-    L.pycllp_hip_abi_version.restype = ctypes.c_int
-    L.pycllp_hip_last_error.restype = ctypes.c_char_p
-    L.pycllp_hip_default_opts.argtypes = [ctypes.POINTER(Opts)]
-    L.pycllp_hip_default_opts.restype = None
-    L.pycllp_hip_dense_max_rows.restype = ctypes.c_int
-    L.pycllp_hip_dense_max_cols.restype = ctypes.c_int
-    L.pycllp_hip_dense_init.argtypes = [ctypes.c_int, ctypes.c_int, dp, vp, ctypes.POINTER(vp)]
-    L.pycllp_hip_dense_init.restype = ctypes.c_int
-    L.pycllp_hip_dense_solve.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, dp, dp, ip, ip,
-                                         ctypes.POINTER(Opts), vp]
-    L.pycllp_hip_dense_solve.restype = ctypes.c_int
-    L.pycllp_hip_dense_solve_bounded.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip, ip,
-                                                 ctypes.POINTER(Opts), vp]
-    L.pycllp_hip_dense_solve_bounded.restype = ctypes.c_int
-    L.pycllp_hip_dense_newton.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, ctypes.c_double, dp, ip,
-                                          ctypes.POINTER(Opts), vp]
-    L.pycllp_hip_dense_newton.restype = ctypes.c_int
-    L.pycllp_hip_dense_launch_info.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int)] * 5
-    L.pycllp_hip_dense_launch_info.restype = ctypes.c_int
-    L.pycllp_hip_dense_kernel_kind.argtypes = [vp]
-    L.pycllp_hip_dense_kernel_kind.restype = ctypes.c_int
-    L.pycllp_hip_ldl.argtypes = [ctypes.c_int, ctypes.c_long, dp, dp, dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp]
-    L.pycllp_hip_ldl.restype = ctypes.c_int
-    L.pycllp_hip_sparse_max_rows.restype = ctypes.c_int
-    L.pycllp_hip_sparse_max_cols.restype = ctypes.c_int
-    L.pycllp_hip_sparse_init.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, ip, ip, vp, ctypes.POINTER(vp)]
-    L.pycllp_hip_sparse_init.restype = ctypes.c_int
-    L.pycllp_hip_sparse_solve.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, dp, dp, ip, ip, ctypes.POINTER(Opts), vp]
-    L.pycllp_hip_sparse_solve.restype = ctypes.c_int
-    L.pycllp_hip_sparse_newton.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, ctypes.c_double, dp, ip,
-                                           ctypes.POINTER(Opts), vp]
-    L.pycllp_hip_sparse_newton.restype = ctypes.c_int
-    L.pycllp_hip_sparse_launch_info.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int)] * 4
-    L.pycllp_hip_sparse_launch_info.restype = ctypes.c_int
-    L.pycllp_hip_ldl_solve.argtypes = [ctypes.c_int, ctypes.c_long, dp, dp, dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp]
-    L.pycllp_hip_ldl_solve.restype = ctypes.c_int
-    L.pycllp_hip_forward_backward_ldl.argtypes = [ctypes.c_int, ctypes.c_long, dp, dp, dp, dp, vp]
-    L.pycllp_hip_forward_backward_ldl.restype = ctypes.c_int
-    L.pycllp_hip_sparse_solve_batch.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, dp, dp, dp, ip, ip, ctypes.POINTER(Opts), vp]
-    L.pycllp_hip_sparse_solve_batch.restype = ctypes.c_int
-    L.pycllp_hip_sparse_solve_bounded.argtypes = [vp, ctypes.c_long, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip, ip,
-                                                  ctypes.POINTER(Opts), vp]
-    L.pycllp_hip_sparse_solve_bounded.restype = ctypes.c_int
-    L.pycllp_hip_sparse_free.argtypes = [vp]
-    L.pycllp_hip_sparse_free.restype = None
-    L.pycllp_hip_dense_free.argtypes = [vp]
-    L.pycllp_hip_dense_free.restype = None
+    for name, args, res in SIGNATURES:
+        f = getattr(L, name)
+        f.argtypes, f.restype = args, res
     if L.pycllp_hip_abi_version() != 1:
         raise RuntimeError("pycllp_amd: ABI version mismatch in %s" % LIB_PATH)
     _lib = L

@@ -11,15 +11,13 @@ library takes.  ``kernel`` tells which path served the last ``solve``: ``'bounde
 (``pycllp_hip_sparse_solve_bounded``, csrc/ipm_wreg_bounded.inc): any shared A^ with m' <= 128 kept rows and N <= 512 columns
 that a variant of that kernel covers (``kernel == 'bounded wave'``), sparse or dense, the expansion for the rest.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import BaseGeneralSolver
 from .. import _native
 from ..lp import GeneralLP, SparseMatrix
-from .hip import HipDensePrimalNormalSolver, _require_gpu, autoscale_wanted
+from .hip import Handle, HipDensePrimalNormalSolver, _require_gpu, autoscale_wanted, plugin_options, solve_opts
 
 NATIVE_MAX_ROWS, NATIVE_MAX_COLS = 32, 96      # the slack-aware kernels: m' <= 32 rows, n <= 96 original columns
 WAVE_MAX_ROWS, WAVE_MAX_COLS = 128, 512        # the bounded wave kernel: m' <= 128 rows, N <= 512 columns of A^
@@ -54,7 +52,6 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
     _rejected = _REJECTED
     _rejected_names = "HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH"
     _native_kernel = "bounded group"
-    _bounded_entry = "pycllp_hip_dense_solve_bounded"
 
     def __init__(self, device=None, stream=None, autoscale="auto", hsd="auto", predcorr=False, warm_start=False, **options):
         """``hsd='auto'`` (default): the LPs that do not end optimal on the bounded kernel are solved again through the
@@ -62,7 +59,7 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
         statuses 2 / 4); ``hsd=False``: the bounded kernel's verdict stands.  ``hsd=True``, ``predcorr=True`` and
         ``warm_start=True`` are not available with bounds.  ``autoscale``: as ``HipDensePrimalNormalSolver`` (the 'auto' band
         rule also looks at the finite upper bounds).  Other keyword arguments are fields of ``pycllp_hip_opts``."""
-        if not (hsd is False or (isinstance(hsd, str) and hsd == "auto")):
+        if not isinstance(hsd, str) and hsd:
             raise ValueError("hsd must be 'auto' or False for %s (the bounded kernel has no embedding)" % self.name)
         if predcorr:
             raise ValueError("predcorr is not available with upper bounds")
@@ -70,58 +67,33 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
             raise ValueError("warm_start is not available with upper bounds")
         if int(options.get("flags", 0)) & self._rejected:
             raise ValueError("flags %s are not available with upper bounds" % self._rejected_names)
-        if isinstance(autoscale, str):
-            if autoscale != "auto":
-                raise ValueError("autoscale must be True, False or 'auto'")
-        else:
-            autoscale = bool(autoscale)
-        if int(options.get("flags", 0)) & _native.FLAG_AUTOSCALE:
-            autoscale = True
-        self.autoscale, self.hsd = autoscale, hsd
+        self.hsd, self.autoscale, _, _, self.options = plugin_options(options, hsd, autoscale)
         self.device, self.stream = device, stream
-        self.options = dict(options)
-        _native.default_opts(**self.options) if options else None   # validate names early
         self._handle = None
         self._key = None
         self.kernel = None
-
-    def _free(self):
-        if self._handle is not None:
-            _native.lib().pycllp_hip_dense_free(self._handle)
-            self._handle = None
-            self._key = None
-
-    def __del__(self):
-        try:
-            self._free()
-        except Exception:
-            pass
-
-    def _stream_ptr(self):
-        st = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
-        return ctypes.c_void_p(st.cuda_stream)
 
     @staticmethod
     def native_fits(glp, blp):
         return glp.A.nproblems == 1 and 1 <= blp.nrows <= NATIVE_MAX_ROWS and glp.ncols <= NATIVE_MAX_COLS
 
-    def _ensure_handle(self, blp):
-        """A handle for A^ (re-made when the kept rows or their signs changed since the last one); False if A^ is not served."""
+    @staticmethod
+    def _bounded_matrix(blp):
+        """(A^ as the handle of the native kernel takes it -- dense --, a key that tells whether A^ changed)."""
         A = np.ascontiguousarray(blp.A.todense(), dtype=np.float64)
-        key = (A.shape, A.tobytes())
+        return A, (A.shape, A.tobytes())
+
+    def _ensure_handle(self, blp):
+        """A handle for A^ (re-made when A^ changed since the last one); False if the library declines it."""
+        A, key = self._bounded_matrix(blp)
         if self._handle is not None and self._key == key:
             return True
-        self._free()
-        with torch.cuda.device(self.device):
-            A_dev = torch.as_tensor(A, device=self.device)
-            h = ctypes.c_void_p()
-            rc = _native.lib().pycllp_hip_dense_init(A.shape[0], A.shape[1], ctypes.c_void_p(A_dev.data_ptr()), self._stream_ptr(),
-                                                     ctypes.byref(h))
-            torch.cuda.synchronize(self.device)
-        if rc == -2:
+        self._handle = self._key = None
+        try:
+            self._handle = Handle(A, self.device, self.stream)
+        except NotImplementedError:
             return False
-        _native.check(rc, "pycllp_hip_dense_init")
-        self._handle, self._key = h, key
+        self._key = key
         return True
 
     # -- plugin API ------------------------------------------------------------------------------
@@ -163,37 +135,23 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
     def _solve_bounded(self, blp, bmap):
         """One upload, one launch of the bounded kernel, one download; None if the library declines A^ (PYCLLP_E_UNSUPPORTED)."""
         B, mk, N = blp.nproblems, blp.nrows, blp.ncols
-        opts = dict(self.options)
-        flags = int(opts.get("flags", 0))
-        if self.autoscale is True or (self.autoscale == "auto" and autoscale_wanted(blp.b, blp.c, blp.u)):
-            flags |= _native.FLAG_AUTOSCALE
-        opts["flags"] = flags
-        o = _native.default_opts(**opts)
-        if o.max_iter < 1 or o.max_refine < _native.MAX_REFINE_AUTO or not (o.eps > 0):
-            raise ValueError("max_iter must be >= 1, max_refine >= 0 (or -1 = auto) and eps > 0")
+        wanted = self.autoscale == "auto" and autoscale_wanted(blp.b, blp.c, blp.u)
+        o = solve_opts(self.options, _native.FLAG_AUTOSCALE if wanted else 0)
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            b = torch.as_tensor(np.ascontiguousarray(blp.b), **f64)
-            c = torch.as_tensor(np.ascontiguousarray(blp.c), **f64)
-            u = torch.as_tensor(np.ascontiguousarray(blp.u), **f64)
-            x, z, s = (torch.empty((B, N), **f64) for _ in range(3))
-            y = torch.empty((B, mk), **f64)
-            pobj, dobj = torch.empty(B, **f64), torch.empty(B, **f64)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            iters = torch.empty(B, dtype=torch.int32, device=dev)
-            P = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
-            rc = getattr(_native.lib(), self._bounded_entry)(
-                self._handle, B, P(b), P(c), P(u), P(x), P(y), P(z), P(s), P(pobj), P(dobj), P(status), P(iters),
-                ctypes.byref(o), self._stream_ptr())
-            if rc == -2:
-                return None
-            _native.check(rc, self._bounded_entry)
-            torch.cuda.synchronize(dev)
-        xo, yo, zo, so = bmap.general(x.cpu().numpy(), y.cpu().numpy(), z.cpu().numpy(), s.cpu().numpy())
+        b, c, u = (torch.as_tensor(np.ascontiguousarray(v), **f64) for v in (blp.b, blp.c, blp.u))
+        out = dict(x=torch.empty((B, N), **f64), y=torch.empty((B, mk), **f64), z=torch.empty((B, N), **f64),
+                   s=torch.empty((B, N), **f64), pobj=torch.empty(B, **f64), dobj=torch.empty(B, **f64),
+                   status=torch.empty(B, dtype=torch.int32, device=dev), iters=torch.empty(B, dtype=torch.int32, device=dev))
+        try:
+            self._handle.solve_bounded(self.stream, b, c, u, out, o)
+        except NotImplementedError:
+            return None
+        torch.cuda.synchronize(dev)
+        r = {k: v.cpu().numpy() for k, v in out.items()}
+        xo, yo, zo, so = bmap.general(r["x"], r["y"], r["z"], r["s"])
         f = np.broadcast_to(blp.f, (B,))
-        return dict(x=xo, y=yo, z=zo, s=so, status=status.cpu().numpy(), iters=iters.cpu().numpy(),
-                    primal_obj=pobj.cpu().numpy() + f, dual_obj=dobj.cpu().numpy() + f)
+        return dict(x=xo, y=yo, z=zo, s=so, status=r["status"], iters=r["iters"], primal_obj=r["pobj"] + f, dual_obj=r["dobj"] + f)
 
     def solve_expanded(self, glp):
         """Solve ``glp`` through ``to_standard_form().to_equality_form()`` on ``HipDensePrimalNormalSolver`` and map the results
@@ -251,40 +209,16 @@ class HipSparseGeneralPrimalNormalSolver(HipGeneralPrimalNormalSolver):
     _rejected = _REJECTED | _native.FLAG_BLOCK_KERNEL | _native.FLAG_FORCE_GUARD_PATH
     _rejected_names = "HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and FORCE_GUARD_PATH"
     _native_kernel = "bounded wave"
-    _bounded_entry = "pycllp_hip_sparse_solve_bounded"
-
-    def _free(self):
-        if self._handle is not None:
-            _native.lib().pycllp_hip_sparse_free(self._handle)
-            self._handle = None
-            self._key = None
 
     @staticmethod
     def native_fits(glp, blp):
         return glp.A.nproblems == 1 and 1 <= blp.nrows <= WAVE_MAX_ROWS and blp.ncols <= WAVE_MAX_COLS
 
-    def _ensure_handle(self, blp):
-        """A handle for the CSR of A^ (re-made when A^ changed since the last one); False if the library declines it."""
+    @staticmethod
+    def _bounded_matrix(blp):
         A = blp.A.tocsr()
         A.sum_duplicates(); A.eliminate_zeros(); A.sort_indices()
-        data = np.ascontiguousarray(A.data, dtype=np.float64)
-        indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
-        indices = np.ascontiguousarray(A.indices, dtype=np.int32)
-        key = (A.shape, data.tobytes(), indptr.tobytes(), indices.tobytes())
-        if self._handle is not None and self._key == key:
-            return True
-        self._free()
-        with torch.cuda.device(self.device):
-            t = [torch.as_tensor(v, device=self.device) for v in (data, indptr, indices)]
-            h = ctypes.c_void_p()
-            rc = _native.lib().pycllp_hip_sparse_init(A.shape[0], A.shape[1], int(A.nnz), *(ctypes.c_void_p(v.data_ptr()) for v in t),
-                                                      self._stream_ptr(), ctypes.byref(h))
-            torch.cuda.synchronize(self.device)
-        if rc == -2:
-            return False
-        _native.check(rc, "pycllp_hip_sparse_init")
-        self._handle, self._key = h, key
-        return True
+        return A, (A.shape, A.data.tobytes(), A.indptr.tobytes(), A.indices.tobytes())
 
     def _redo(self, glp, idx):
         if idx.size:

@@ -12,6 +12,7 @@ PyTorch is plumbing only (device memory, streams); the compute is ``csrc/libpycl
 import ctypes
 
 import numpy as np
+import scipy.sparse as sp
 import torch
 
 from . import BaseSolver
@@ -100,9 +101,127 @@ def _require_gpu(device):
     return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
 
+def plugin_options(options, hsd="auto", autoscale="auto", predcorr=False, warm_start=False, warm_lift=1e-3):
+    """(hsd, autoscale, warm_start, warm_lift, options) of a solver plugin's constructor arguments: ``hsd`` and ``autoscale``
+    as True, False or 'auto' (FLAG_HSD / FLAG_AUTOSCALE in ``flags`` switch them on), ``options`` -- fields of
+    ``pycllp_hip_opts`` -- with the flags of hsd=True, autoscale=True and predcorr merged into ``flags``, names validated."""
+    if isinstance(hsd, str):
+        if hsd != "auto":
+            raise ValueError("hsd must be True, False or 'auto'")
+    elif isinstance(hsd, (bool, np.bool_, int, np.integer)):
+        hsd = bool(hsd)           # 1 / np.bool_(True) mean True (ADVICE r2: `hsd is True` tests below)
+    else:
+        raise ValueError("hsd must be True, False or 'auto'")
+    if predcorr and hsd is True:
+        raise ValueError("predcorr is an option of the reference's path; it cannot be combined with hsd=True")
+    if isinstance(autoscale, str):
+        if autoscale != "auto":
+            raise ValueError("autoscale must be True, False or 'auto'")
+    else:
+        autoscale = bool(autoscale)
+    options = dict(options)
+    flags = int(options.get("flags", 0))
+    if flags & _native.FLAG_AUTOSCALE:
+        autoscale = True
+    if flags & _native.FLAG_HSD:
+        hsd = True
+    implied = ((_native.FLAG_PREDCORR if predcorr else 0) | (_native.FLAG_AUTOSCALE if autoscale is True else 0)
+               | (_native.FLAG_HSD if hsd is True else 0))
+    if implied:
+        options["flags"] = flags | implied
+    warm_lift = float(warm_lift)
+    if not (warm_lift >= 0.0):
+        raise ValueError("warm_lift must be >= 0")
+    _native.default_opts(**options) if options else None      # validate names early
+    return hsd, autoscale, bool(warm_start), warm_lift, options
+
+
+def solve_opts(options, extra_flags=0, **overrides):
+    """The ``_native.Opts`` of one solve: a plugin's ``options`` with ``overrides`` (fields of ``pycllp_hip_opts``) and
+    ``extra_flags`` added for this call, range-checked."""
+    opts = dict(options, **overrides)
+    opts["flags"] = int(opts.get("flags", 0)) | extra_flags
+    o = _native.default_opts(**opts)
+    if o.max_iter < 1 or o.max_refine < _native.MAX_REFINE_AUTO or not (o.eps > 0):
+        raise ValueError("max_iter must be >= 1, max_refine >= 0 (or -1 = auto) and eps > 0")
+    return o
+
+
+RESULTS = ("x", "y", "z", "pobj", "dobj", "status", "iters")       # (also the order of the solve entries' outputs)
+
+
+class Handle(object):
+    """One library handle for a constraint matrix on ``device``: ``pycllp_hip_dense`` for a dense numpy ``A``,
+    ``pycllp_hip_sparse`` for a scipy CSR ``A`` (for per-problem values of A: their structure with problem 0's values), freed
+    exactly once.  The calls take torch tensors and the stream to queue on (None: torch's current stream on ``device``); an
+    answer PYCLLP_E_UNSUPPORTED -- the library declines the matrix or the call -- raises ``NotImplementedError``.  As a
+    ctypes argument the object stands for its raw handle."""
+    _as_parameter_ = None
+
+    def __init__(self, A, device, stream):
+        self.device = device
+        if isinstance(A, np.ndarray):
+            self.family, sizes, arrays = "dense", A.shape, (np.ascontiguousarray(A, dtype=np.float64),)
+        else:
+            self.family, sizes = "sparse", A.shape + (int(A.nnz),)
+            arrays = (np.ascontiguousarray(A.data, dtype=np.float64), np.ascontiguousarray(A.indptr, dtype=np.int32),
+                      np.ascontiguousarray(A.indices, dtype=np.int32))
+        arrays = [torch.as_tensor(v, device=device) for v in arrays]
+        h = ctypes.c_void_p()
+        self._call("init", *sizes, *arrays, self._stream(stream), ctypes.byref(h))    # (synchronises the stream)
+        self._as_parameter_ = h
+
+    def _stream(self, stream):
+        return ctypes.c_void_p((stream if stream is not None else torch.cuda.current_stream(self.device)).cuda_stream)
+
+    def _call(self, entry, *args):
+        name = "pycllp_hip_%s_%s" % (self.family, entry)
+        args = [ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+        with torch.cuda.device(self.device):
+            _native.check(getattr(_native.lib(), name)(*args), name)
+
+    def solve(self, stream, b, c, out, o, values=None):
+        """B LPs b [B, m], c [B, n] into ``out`` (the arrays of ``RESULTS``).  ``values`` [B, nnz]: per-problem values of A in
+        the CSR order of the handle's matrix (sparse family)."""
+        entry, lead = ("solve", ()) if values is None else ("solve_batch", (values,))
+        self._call(entry, self, int(b.shape[0]), *lead, b, c, *(out[k] for k in RESULTS), ctypes.byref(o), self._stream(stream))
+
+    def solve_bounded(self, stream, b, c, u, out, o):
+        """B LPs with the upper bounds u [B, n] into ``out`` (x, y, z, s, pobj, dobj, status, iters)."""
+        self._call("solve_bounded", self, int(b.shape[0]), b, c, u,
+                   *(out[k] for k in ("x", "y", "z", "s", "pobj", "dobj", "status", "iters")), ctypes.byref(o), self._stream(stream))
+
+    def newton(self, stream, x, z, y, b, c, mu, dy, nrefine, o):
+        self._call("newton", self, int(x.shape[0]), x, z, y, b, c, float(mu), dy, nrefine, ctypes.byref(o), self._stream(stream))
+
+    def launch_info(self):
+        """grid / block / LDS bytes of the last solve (dense family: the padded m, n too) and, where one of the kernels of
+        ``SPARSE_KERNEL_KINDS`` served it, its ``variant`` and ``kernel``."""
+        keys = ("grid", "block", "lds_bytes") + (("m_pad", "n_pad") if self.family == "dense" else ("kernel",))
+        vals = [ctypes.c_int() for _ in keys]
+        self._call("launch_info", self, *[ctypes.byref(v) for v in vals])
+        d = dict(zip(keys, [v.value for v in vals]))
+        kind = _native.lib().pycllp_hip_dense_kernel_kind(self) if self.family == "dense" else d["kernel"]
+        if kind >= 0:
+            d["variant"], d["kernel"] = SPARSE_KERNEL_KINDS[kind]
+        return d
+
+    def free(self):
+        h, self._as_parameter_ = self._as_parameter_, None
+        if h is not None:
+            getattr(_native.lib(), "pycllp_hip_%s_free" % self.family)(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class HipDensePrimalNormalSolver(BaseSolver):
     """Drop-in for ``cl_dense_primal_normal`` on MI355X.  The LP must be in equality form
-    (callers use ``StandardLP.to_equality_form()`` first, as for the OpenCL solver)."""
+    (callers use ``StandardLP.to_equality_form()`` first, as for the OpenCL solver).  Per-problem values of A
+    (``lp.A.data [nproblems, nnz]``) are served by the sparse path's per-problem kernel: one structure, values from HBM."""
     name = 'hip_dense_primal_normal'
 
     def __init__(self, device=None, stream=None, keep_on_device=False, autoscale="auto", hsd="auto", warm_start=False,
@@ -133,74 +252,22 @@ class HipDensePrimalNormalSolver(BaseSolver):
         default ``hsd="auto"`` the LPs that do not end optimal are still re-solved on the embedding.  Other keyword arguments are
         the fields of ``pycllp_hip_opts`` (eps, delta, r, pivot_floor, refine_tol, max_iter, max_refine, flags)."""
         super(HipDensePrimalNormalSolver, self).__init__()
-        if isinstance(hsd, str):
-            if hsd != "auto":
-                raise ValueError("hsd must be True, False or 'auto'")
-        elif isinstance(hsd, (bool, np.bool_, int, np.integer)):
-            hsd = bool(hsd)           # 1 / np.bool_(True) mean True (ADVICE r2: `hsd is True` tests below)
-        else:
-            raise ValueError("hsd must be True, False or 'auto'")
-        if predcorr:
-            if hsd is True:
-                raise ValueError("predcorr is an option of the reference's path; it cannot be combined with hsd=True")
-            options["flags"] = int(options.get("flags", 0)) | _native.FLAG_PREDCORR
-        if isinstance(autoscale, str):
-            if autoscale != "auto":
-                raise ValueError("autoscale must be True, False or 'auto'")
-        else:
-            autoscale = bool(autoscale)
-        if int(options.get("flags", 0)) & _native.FLAG_AUTOSCALE:
-            autoscale = True
-        if autoscale is True:
-            options["flags"] = int(options.get("flags", 0)) | _native.FLAG_AUTOSCALE
-        elif autoscale == "auto" and int(options.get("flags", 0)) & _native.FLAG_WAVE_KERNEL:
-            autoscale = False
-        self.autoscale = autoscale
+        self.hsd, self.autoscale, self.warm_start, self.warm_lift, self.options = plugin_options(
+            options, hsd, autoscale, predcorr, warm_start, warm_lift)
         self._extra_flags = 0        # flags solve(lp) adds for one call (autoscale='auto')
-        if hsd is True or (int(options.get("flags", 0)) & _native.FLAG_HSD):
-            options["flags"] = int(options.get("flags", 0)) | _native.FLAG_HSD
-            hsd = True
-        if int(options.get("flags", 0)) & _native.FLAG_WAVE_KERNEL and hsd == "auto":
-            hsd = False          # the first-generation kernel has no embedding
-        self.hsd = hsd
-        self.warm_start = bool(warm_start)
-        self.warm_lift = float(warm_lift)
-        if not (self.warm_lift >= 0.0):
-            raise ValueError("warm_lift must be >= 0")
         self._prev_B = None
         self.device = device
         self.stream = stream
         self.keep_on_device = keep_on_device
-        self.options = dict(options)
-        _native.default_opts(**self.options) if options else None  # validate names early
         self._handle = None
+        self._a_perm = self._a_values = None
         self.buffers = {}
-        self._a_row0 = None
 
     # -- helpers ---------------------------------------------------------------------------------
-    def _stream_ptr(self):
-        st = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
-        return ctypes.c_void_p(st.cuda_stream)
-
     def _dev(self, a):
         if isinstance(a, torch.Tensor):
             return a.to(device=self.device, dtype=torch.float64).contiguous()
         return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=self.device)
-
-    @staticmethod
-    def _ptr(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-    def _free(self):
-        if self._handle is not None:
-            _native.lib().pycllp_hip_dense_free(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._free()
-        except Exception:
-            pass
 
     @staticmethod
     def consume(lp):
@@ -216,43 +283,44 @@ class HipDensePrimalNormalSolver(BaseSolver):
                     b=np.ascontiguousarray(np.asarray(lp.b, dtype=np.float64)), c=np.ascontiguousarray(np.asarray(lp.c, dtype=np.float64)),
                     f=np.atleast_1d(np.asarray(getattr(lp, "f", 0.0), dtype=np.float64)))
 
+    def _shared_matrix(self, lp):
+        """The shared A as the handle takes it: densified (``pycllp/solvers/cl.py:39``)."""
+        return self.consume(lp)["A"]
+
+    def _check_batch(self, b, c):
+        if b.ndim != 2 or c.ndim != 2 or b.shape[1] != self.m or c.shape[1] != self.n or b.shape[0] != c.shape[0]:
+            raise ValueError("b must be [B,%d] and c [B,%d] with equal B; got %r and %r"
+                             % (self.m, self.n, tuple(b.shape), tuple(c.shape)))
+        return int(b.shape[0])
+
     # -- plugin API ------------------------------------------------------------------------------
     def init(self, lp, verbose=0):
-        """Densify and upload A once (``pycllp/solvers/cl.py:39,46``)."""
+        """Upload A once (``pycllp/solvers/cl.py:39,46``)."""
         self.device = _require_gpu(self.device)
-        L = _native.lib()
-        self._delegate = None
-        if type(self) is HipDensePrimalNormalSolver and getattr(lp.A, "nproblems", 1) > 1:
-            # per-problem values of A: served by the sparse path's per-problem kernel (one LP per workgroup, values from HBM)
-            d = HipSparsePrimalNormalSolver(device=self.device, stream=self.stream, keep_on_device=self.keep_on_device,
-                                            autoscale=self.autoscale, hsd=self.hsd, warm_start=self.warm_start, warm_lift=self.warm_lift,
-                                            **self.options)
-            d.init(lp, verbose=verbose)
-            self._delegate, self.m, self.n = d, d.m, d.n
-            return
         m, n = int(lp.nrows), int(lp.ncols)
-        A = lp.A.todense() if hasattr(lp.A, "todense") else lp.A
-        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
-        if A.shape != (m, n):
-            raise ValueError("A has shape %r, expected (%d, %d)" % (A.shape, m, n))
+        self._a_perm = self._a_values = None
+        if getattr(lp.A, "nproblems", 1) > 1:
+            # per-problem values on one structure (SparseMatrix.data[nproblems, nnz], pycllp/lp.py:16-54): the structure
+            # comes from the coordinate lists, the values of problem 0 only stand in at init
+            rows, cols = np.asarray(lp.A._rows), np.asarray(lp.A._cols)
+            perm = np.lexsort((cols, rows))
+            if perm.size and ((np.diff(rows[perm]) == 0) & (np.diff(cols[perm]) == 0)).any():
+                raise ValueError("per-problem A: duplicate (row, column) entries in the structure")
+            self._a_perm = perm
+            indptr = np.zeros(m + 1, dtype=np.int64)
+            np.add.at(indptr, rows + 1, 1)
+            A = sp.csr_matrix((np.asarray(lp.A.data[0], dtype=np.float64)[perm], cols[perm], np.cumsum(indptr)), shape=(m, n))
+        else:
+            A = self._shared_matrix(lp)
         if verbose > 0:
-            print("Initializing HipDensePrimalNormalSolver (m=%d, n=%d) on %s" % (m, n, self.device))
-        self._free()
-        with torch.cuda.device(self.device):
-            A_dev = self._dev(A)
-            h = ctypes.c_void_p()
-            _native.check(L.pycllp_hip_dense_init(m, n, self._ptr(A_dev), self._stream_ptr(), ctypes.byref(h)),
-                          "pycllp_hip_dense_init")
-        self._handle = h
+            print("Initializing %s (m=%d, n=%d) on %s" % (type(self).__name__, m, n, self.device))
+        self._handle = None          # (the previous handle is freed before the new one is made)
+        self._handle = Handle(A, self.device, self.stream)
         self.m, self.n = m, n
         self.buffers = {}
 
     def _pack_layout(self, B):
         return pack_layout(B, self.m, self.n)
-
-    @staticmethod
-    def unpack(packed, layout, names=("pobj", "dobj", "status", "iters", "y", "x")):
-        return unpack(packed, layout, names)
 
     def _buffers(self, B, slot=0):
         """Output tensors of one solve: views into ONE device allocation (``packed``, bytes), so that a caller who ships
@@ -265,40 +333,31 @@ class HipDensePrimalNormalSolver(BaseSolver):
             layout = self._pack_layout(B)
             packed = torch.empty(max(layout["_total_bytes"], 256), dtype=torch.uint8, device=self.device)
             cur = dict(B=B, packed=packed, layout=layout, gather_bytes=layout["_gather_bytes"])
-            cur.update(self.unpack(packed, layout, names=[n for n, _ in PACK_ORDER]))
+            cur.update(unpack(packed, layout, names=[n for n, _ in PACK_ORDER]))
             self.buffers[key] = cur
         return cur
 
     def solve_device(self, b, c, warm_start=False, slot=0, **options):
         """Device-resident entry: b [B,m], c [B,n] (torch CUDA or numpy) -> dict of CUDA tensors.
         Asynchronous on the solver's stream."""
-        if getattr(self, "_delegate", None) is not None:
-            return self._delegate.solve_device(b, c, warm_start=warm_start, slot=slot, **options)
         if self._handle is None:
             raise RuntimeError("solve() called before init()")
         b = self._dev(b); c = self._dev(c)
-        if b.ndim != 2 or c.ndim != 2 or b.shape[1] != self.m or c.shape[1] != self.n or b.shape[0] != c.shape[0]:
-            raise ValueError("b must be [B,%d] and c [B,%d] with equal B; got %r and %r"
-                             % (self.m, self.n, tuple(b.shape), tuple(c.shape)))
-        B = int(b.shape[0])
-        buf = self._buffers(B, slot)
-        opts = dict(self.options); opts.update(options)
-        opts["flags"] = int(opts.get("flags", 0)) | self._extra_flags
-        if warm_start:
-            opts["flags"] = int(opts.get("flags", 0)) | _native.FLAG_WARM_START
-        o = _native.default_opts(**opts)
-        if o.max_iter < 1 or o.max_refine < _native.MAX_REFINE_AUTO or not (o.eps > 0):
-            raise ValueError("max_iter must be >= 1, max_refine >= 0 (or -1 = auto) and eps > 0")
-        with torch.cuda.device(self.device):
-            self._launch(B, b, c, buf, o)
+        buf = self._buffers(self._check_batch(b, c), slot)
+        self._launch(b, c, buf, solve_opts(self.options, self._extra_flags | (_native.FLAG_WARM_START if warm_start else 0),
+                                           **options))
         self._keepalive = (b, c)
         return buf
 
-    def _launch(self, B, b, c, buf, o):
-        _native.check(_native.lib().pycllp_hip_dense_solve(
-            self._handle, B, self._ptr(b), self._ptr(c), self._ptr(buf["x"]), self._ptr(buf["y"]),
-            self._ptr(buf["z"]), self._ptr(buf["pobj"]), self._ptr(buf["dobj"]), self._ptr(buf["status"]),
-            self._ptr(buf["iters"]), ctypes.byref(o), self._stream_ptr()), "pycllp_hip_dense_solve")
+    def _launch(self, b, c, out, o, row0=0, values=None):
+        """One solve of the LPs b, c into ``out`` on the solver's stream.  Per-problem A: LP k takes row row0 + k of ``values``
+        (default ``_a_values``) -- a chunk of the host pipeline starts at its row of the batch."""
+        if self._a_perm is not None:
+            values = self._a_values if values is None else values
+            if values is None or values.shape[0] < row0 + b.shape[0]:
+                raise ValueError("per-problem A: no values for this batch (use lp.solve(solver))")
+            values = values[row0:row0 + b.shape[0]]
+        self._handle.solve(self.stream, b, c, out, o, values)
 
     # -- host-to-host path -----------------------------------------------------------------------
     PIPELINE_MIN_BATCH = 8192   # below this one upload / launch / download is as fast
@@ -327,32 +386,12 @@ class HipDensePrimalNormalSolver(BaseSolver):
         returned arrays are views of the solver's page-locked buffers and are overwritten by the next solve()
         (the reference's ``self.x`` behaves the same way, ``pycllp/solvers/cl.py:40,119``)."""
         b = np.ascontiguousarray(b, dtype=np.float64); c = np.ascontiguousarray(c, dtype=np.float64)
-        if b.ndim != 2 or c.ndim != 2 or b.shape[1] != self.m or c.shape[1] != self.n or b.shape[0] != c.shape[0]:
-            raise ValueError("b must be [B,%d] and c [B,%d] with equal B; got %r and %r"
-                             % (self.m, self.n, tuple(b.shape), tuple(c.shape)))
-        B = int(b.shape[0])
+        B = self._check_batch(b, c)
         st, buf = self._host_staging(B), self._buffers(B, 0)
         nchunk = max(1, min(self.PIPELINE_CHUNKS, B // self.PIPELINE_MIN_BATCH))
         edges = [B * k // nchunk for k in range(nchunk + 1)]
         compute = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
-        outs = ("x", "y", "z", "pobj", "dobj", "status", "iters")
-
-        def stage_and_upload(lo, hi):
-            # plain memcpy on this thread: torch's CPU copy_ would wake its whole intra-op thread pool, whose
-            # spin-waiting burns a container's CPU quota and shows up as sporadic ~80 ms stalls
-            np.copyto(st["hb"][lo:hi], b[lo:hi]); np.copyto(st["hc"][lo:hi], c[lo:hi])
-            with torch.cuda.stream(st["s_in"]):
-                st["db"][lo:hi].copy_(st["b"][lo:hi], non_blocking=True)
-                st["dc"][lo:hi].copy_(st["c"][lo:hi], non_blocking=True)
-                return st["s_in"].record_event()
-
-        opts = dict(self.options)
-        if warm:
-            opts["flags"] = int(opts.get("flags", 0)) | _native.FLAG_WARM_START
-        o = _native.default_opts(**opts)
-        if o.max_iter < 1 or o.max_refine < _native.MAX_REFINE_AUTO or not (o.eps > 0):
-            raise ValueError("max_iter must be >= 1, max_refine >= 0 (or -1 = auto) and eps > 0")
-        base_flags = int(o.flags)
+        o = solve_opts(self.options, _native.FLAG_WARM_START if warm else 0)
         # autoscale='auto' decided on the device (self._extra_flags is None): the chunks are solved WITHOUT the flag while their
         # band tests (two row reductions each, queued behind the chunk's upload) accumulate; if some LP of the batch turns out
         # to lie outside the band -- b or c decades away from 1: LPs that take 40-170 iterations unscaled -- the batch is solved
@@ -362,47 +401,45 @@ class HipDensePrimalNormalSolver(BaseSolver):
             # (a warm start reads the x, z, y the first pass would overwrite: decide before launching anything)
             self._extra_flags = _native.FLAG_AUTOSCALE if autoscale_wanted(b, c) else 0
         speculative = self._extra_flags is None
-        o.flags = base_flags | (0 if speculative else int(self._extra_flags))
-        lo_, hi_ = AUTOSCALE_BAND
+        if not speculative:
+            o.flags |= self._extra_flags
+        lo_band, hi_band = AUTOSCALE_BAND
         tests = []
-        with torch.cuda.device(self.device):
-            ups = []
+
+        def solve_chunks(upload):
             for lo, hi in zip(edges[:-1], edges[1:]):
-                up = stage_and_upload(lo, hi)
-                ups.append(up)
-                if speculative and hi > lo:
+                if upload:
+                    # plain memcpy on this thread: torch's CPU copy_ would wake its whole intra-op thread pool, whose
+                    # spin-waiting burns a container's CPU quota and shows up as sporadic ~80 ms stalls
+                    np.copyto(st["hb"][lo:hi], b[lo:hi]); np.copyto(st["hc"][lo:hi], c[lo:hi])
                     with torch.cuda.stream(st["s_in"]):
-                        for v in (st["db"][lo:hi], st["dc"][lo:hi]):
-                            mx = v.abs().amax(dim=-1)
-                            tests.append(((mx < lo_) | (mx > hi_)).any())
-                compute.wait_event(up)
-                part = {k: buf[k][lo:hi] for k in outs}
-                self._a_row0 = lo          # (per-problem A values of the sparse solver: rows of this chunk)
-                self._launch(hi - lo, st["db"][lo:hi], st["dc"][lo:hi], part, o)
-                self._a_row0 = None
+                        st["db"][lo:hi].copy_(st["b"][lo:hi], non_blocking=True)
+                        st["dc"][lo:hi].copy_(st["c"][lo:hi], non_blocking=True)
+                        compute.wait_event(st["s_in"].record_event())
+                        if speculative:
+                            for v in (st["db"][lo:hi], st["dc"][lo:hi]):
+                                mx = v.abs().amax(dim=-1)
+                                tests.append(((mx < lo_band) | (mx > hi_band)).any())
+                part = {k: buf[k][lo:hi] for k in RESULTS}
+                self._launch(st["db"][lo:hi], st["dc"][lo:hi], part, o, row0=lo)
                 done = compute.record_event()
                 with torch.cuda.stream(st["s_out"]):
                     st["s_out"].wait_event(done)
-                    for k in outs:
+                    for k in RESULTS:
                         st[k][lo:hi].copy_(part[k], non_blocking=True)
+
+        with torch.cuda.device(self.device):
+            solve_chunks(upload=True)
             if speculative:
-                self._extra_flags = 0
-                if tests and bool(torch.stack(tests).any()):
-                    self._extra_flags = _native.FLAG_AUTOSCALE        # (the hsd='auto' re-solve of this call runs with it too)
-                    o.flags = base_flags | _native.FLAG_AUTOSCALE
-                    st["s_out"].synchronize()
-                    for lo, hi in zip(edges[:-1], edges[1:]):
-                        part = {k: buf[k][lo:hi] for k in outs}
-                        self._a_row0 = lo
-                        self._launch(hi - lo, st["db"][lo:hi], st["dc"][lo:hi], part, o)
-                        self._a_row0 = None
-                        done = compute.record_event()
-                        with torch.cuda.stream(st["s_out"]):
-                            st["s_out"].wait_event(done)
-                            for k in outs:
-                                st[k][lo:hi].copy_(part[k], non_blocking=True)
+                compute.wait_stream(st["s_in"])          # (the band tests ran there: read them only once they are computed)
+                with torch.cuda.stream(compute):
+                    self._extra_flags = _native.FLAG_AUTOSCALE if bool(torch.stack(tests).any()) else 0
+                if self._extra_flags:                    # (the hsd='auto' re-solve of this call runs with it too)
+                    o.flags |= _native.FLAG_AUTOSCALE
+                    st["s_out"].synchronize()            # (the first pass's downloads still read the results)
+                    solve_chunks(upload=False)
             st["s_out"].synchronize()
-        return {k: st[k].numpy() for k in outs}
+        return {k: st[k].numpy() for k in RESULTS}
 
     def _prepare_warm(self, B):
         """True when this solve may start from the previous solution: same batch size, a previous solve exists.  LPs that
@@ -430,47 +467,46 @@ class HipDensePrimalNormalSolver(BaseSolver):
     def _resolve_non_optimal(self, b, c, res):
         """hsd='auto': the LPs that did not end optimal are solved again on the homogeneous self-dual embedding and their
         results replace the first verdict.  ``res``: dict of numpy arrays or CUDA tensors of the first solve."""
-        status = res["status"]
-        idx = torch.nonzero(status != 0).flatten() if isinstance(status, torch.Tensor) else np.flatnonzero(status != 0)
-        if len(idx) == 0:
+        on_device = isinstance(res["status"], torch.Tensor)
+        if on_device:
+            idx = torch.nonzero(res["status"] != 0).flatten()
+            host_idx = idx.cpu().numpy()
+        else:
+            host_idx = np.flatnonzero(res["status"] != 0)
+        if host_idx.size == 0:
             return
         flags = (int(self.options.get("flags", 0)) | _native.FLAG_HSD) & ~(_native.FLAG_WARM_START | _native.FLAG_PREDCORR)
-        full_values = getattr(self, "_a_values", None)
+        o = solve_opts(self.options, self._extra_flags, flags=flags)
         with self._on_solver_stream():       # gathers, launch and scatters in ONE stream order
+            if not on_device:
+                idx = torch.as_tensor(host_idx, device=self.device)
             if isinstance(b, torch.Tensor) or isinstance(c, torch.Tensor):
-                it = idx.to(self.device) if isinstance(idx, torch.Tensor) else torch.as_tensor(idx, device=self.device)
-                b2, c2 = self._dev(b)[it], self._dev(c)[it]
+                b2, c2 = self._dev(b)[idx], self._dev(c)[idx]
             else:
-                hi = idx.cpu().numpy() if isinstance(idx, torch.Tensor) else idx
-                b2, c2 = np.asarray(b)[hi], np.asarray(c)[hi]
-            if full_values is not None:      # per-problem A values (sparse solver): the rows of the LPs being re-solved
-                it2 = idx.to(self.device) if isinstance(idx, torch.Tensor) else torch.as_tensor(idx, device=self.device)
-                self._a_values = full_values[it2].contiguous()
-            try:
-                r2 = self.solve_device(b2, c2, slot=3, flags=flags)
-            finally:
-                if full_values is not None:
-                    self._a_values = full_values
-            for k in ("x", "y", "z", "pobj", "dobj", "status", "iters"):
-                if isinstance(res[k], torch.Tensor):
-                    res[k][idx.to(res[k].device) if isinstance(idx, torch.Tensor) else torch.as_tensor(idx, device=res[k].device)] = r2[k]
+                b2, c2 = self._dev(np.asarray(b)[host_idx]), self._dev(np.asarray(c)[host_idx])
+            r2 = self._buffers(host_idx.size, 3)
+            self._launch(b2, c2, r2, o, values=None if self._a_values is None else self._a_values[idx])
+            if on_device:
+                for k in RESULTS:
+                    res[k][idx] = r2[k]
             torch.cuda.synchronize(self.device)
-        for k in ("x", "y", "z", "pobj", "dobj", "status", "iters"):
-            if not isinstance(res[k], torch.Tensor):
-                res[k][idx.cpu().numpy() if isinstance(idx, torch.Tensor) else idx] = r2[k].cpu().numpy()
+        if not on_device:
+            for k in RESULTS:
+                res[k][host_idx] = r2[k].cpu().numpy()
 
     def solve(self, lp, verbose=0):
-        """Solve every problem of ``lp`` (current ``lp.b``, ``lp.c``); results in attributes."""
-        if getattr(self, "_delegate", None) is not None:
-            d = self._delegate
-            d.solve(lp, verbose=verbose)
-            for k in ("x", "y", "z", "status", "iters", "primal_obj", "dual_obj"):
-                setattr(self, k, getattr(d, k))
-            return self.status
+        """Solve every problem of ``lp`` (current ``lp.b``, ``lp.c``, and ``lp.A.data`` for per-problem values of A); results in
+        attributes."""
         if int(lp.nrows) != self.m or int(lp.ncols) != self.n:
             raise ValueError("LP shape changed since init(): (%d,%d) vs (%d,%d)" % (lp.nrows, lp.ncols, self.m, self.n))
         if self._handle is None:
             raise RuntimeError("solve() called before init()")
+        if self._a_perm is not None:
+            data = np.asarray(lp.A.data, dtype=np.float64)
+            if data.shape != (int(lp.nproblems), self._a_perm.size):
+                raise ValueError("per-problem A: lp.A.data must be [nproblems, nnz] = (%d, %d); got %r"
+                                 % (lp.nproblems, self._a_perm.size, data.shape))
+            self._a_values = torch.as_tensor(np.ascontiguousarray(data[:, self._a_perm]), device=self.device)
         if verbose > 0:
             print("Solving %d LPs with %s..." % (lp.nproblems, type(self).__name__))
         f = np.asarray(getattr(lp, "f", 0.0), dtype=np.float64)
@@ -502,7 +538,7 @@ class HipDensePrimalNormalSolver(BaseSolver):
         else:
             buf = self.solve_device(lp.b, lp.c, warm_start=warm)
             torch.cuda.synchronize(self.device)
-            res = {k: buf[k] for k in ("x", "y", "z", "pobj", "dobj", "status", "iters")}
+            res = {k: buf[k] for k in RESULTS}
             if self.hsd == "auto":
                 self._resolve_non_optimal(lp.b, lp.c, res)
             if self.keep_on_device:
@@ -521,122 +557,9 @@ class HipDensePrimalNormalSolver(BaseSolver):
         return self.status
 
     def newton_step(self, x, z, y, b, c, mu, **options):
-        """Stand-alone Newton step dy for B states (the reference's ``solve_primal_normal`` kernel,
-        ``pycllp/cl/ldl.cl:602-653``, as launched by its ``tests/test_ldl.py:219-273``)."""
-        if getattr(self, "_delegate", None) is not None:
-            return self._delegate.newton_step(x, z, y, b, c, mu, **options)
-        if self._handle is None:
-            raise RuntimeError("newton_step() called before init()")
-        x, z, y, b, c = [self._dev(np.atleast_2d(v) if not isinstance(v, torch.Tensor) else v) for v in (x, z, y, b, c)]
-        B = int(x.shape[0])
-        dy = torch.empty((B, self.m), dtype=torch.float64, device=self.device)
-        nref = torch.empty(B, dtype=torch.int32, device=self.device)
-        opts = dict(self.options); opts.update(options)
-        o = _native.default_opts(**opts)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().pycllp_hip_dense_newton(
-                self._handle, B, self._ptr(x), self._ptr(z), self._ptr(y), self._ptr(b), self._ptr(c), float(mu),
-                self._ptr(dy), self._ptr(nref), ctypes.byref(o), self._stream_ptr()), "pycllp_hip_dense_newton")
-        torch.cuda.synchronize(self.device)
-        self.nrefine = nref.cpu().numpy()
-        return dy.cpu().numpy()
-
-    def launch_info(self):
-        if getattr(self, "_delegate", None) is not None:
-            return self._delegate.launch_info()
-        vals = [ctypes.c_int() for _ in range(5)]
-        _native.check(_native.lib().pycllp_hip_dense_launch_info(self._handle, *[ctypes.byref(v) for v in vals]),
-                      "pycllp_hip_dense_launch_info")
-        d = dict(zip(("grid", "block", "lds_bytes", "m_pad", "n_pad"), [v.value for v in vals]))
-        kind = _native.lib().pycllp_hip_dense_kernel_kind(self._handle)
-        if kind >= 0:      # beyond the lane-group kernels: which of the sparse path's kernels served the last launch
-            d["variant"], d["kernel"] = SPARSE_KERNEL_KINDS[kind]
-        return d
-
-
-class HipSparsePrimalNormalSolver(HipDensePrimalNormalSolver):
-    """Drop-in for ``cl_sparse_primal_normal`` (``pycllp/solvers/cl.py:127-278``): shared SPARSE constraint matrix, one LP
-    per workgroup, m <= 128 rows and n <= 512 columns (equality form).  Same contract and result attributes as the
-    dense solver; ``init`` takes the CSR arrays of ``lp.A`` (the reference builds them from the densified A,
-    ``cl.py:175-178``), the transposed copy and the structure of A diag(x/z) A' are derived inside the library."""
-    name = 'hip_sparse_primal_normal'
-
-    def _free(self):
-        if self._handle is not None:
-            _native.lib().pycllp_hip_sparse_free(self._handle)
-            self._handle = None
-
-    def init(self, lp, verbose=0):
-        import scipy.sparse as sp
-        self.device = _require_gpu(self.device)
-        L = _native.lib()
-        m, n = int(lp.nrows), int(lp.ncols)
-        self._a_perm = None
-        if getattr(lp.A, "nproblems", 1) > 1:
-            # per-problem values on one structure (SparseMatrix.data[nproblems, nnz], pycllp/lp.py:16-54): the structure
-            # comes from the coordinate lists, the values of problem 0 only stand in at init
-            rows, cols = np.asarray(lp.A._rows), np.asarray(lp.A._cols)
-            perm = np.lexsort((cols, rows))
-            if perm.size and ((np.diff(rows[perm]) == 0) & (np.diff(cols[perm]) == 0)).any():
-                raise ValueError("per-problem A: duplicate (row, column) entries in the structure")
-            self._a_perm = perm
-            indptr = np.zeros(m + 1, dtype=np.int64)
-            np.add.at(indptr, rows + 1, 1)
-            A = sp.csr_matrix((np.asarray(lp.A.data[0], dtype=np.float64)[perm], cols[perm], np.cumsum(indptr)), shape=(m, n))
-        else:
-            if hasattr(lp.A, "tocsr"):
-                A = sp.csr_matrix(lp.A.tocsr())
-            else:
-                A = sp.csr_matrix(np.asarray(lp.A.todense() if hasattr(lp.A, "todense") else lp.A, dtype=np.float64))
-            A = sp.csr_matrix(A, shape=(m, n))
-            A.sum_duplicates(); A.eliminate_zeros(); A.sort_indices()
-        if verbose > 0:
-            print("Initializing HipSparsePrimalNormalSolver (m=%d, n=%d, nnz=%d) on %s" % (m, n, A.nnz, self.device))
-        self._free()
-        with torch.cuda.device(self.device):
-            data = torch.as_tensor(np.ascontiguousarray(A.data, dtype=np.float64), device=self.device)
-            indptr = torch.as_tensor(np.ascontiguousarray(A.indptr, dtype=np.int32), device=self.device)
-            indices = torch.as_tensor(np.ascontiguousarray(A.indices, dtype=np.int32), device=self.device)
-            h = ctypes.c_void_p()
-            _native.check(L.pycllp_hip_sparse_init(m, n, int(A.nnz), self._ptr(data), self._ptr(indptr), self._ptr(indices),
-                                                   self._stream_ptr(), ctypes.byref(h)), "pycllp_hip_sparse_init")
-        self._handle = h
-        self.m, self.n = m, n
-        self.buffers = {}
-        self._a_values = None
-
-    def solve(self, lp, verbose=0):
-        if self._a_perm is not None:
-            data = np.asarray(lp.A.data, dtype=np.float64)
-            if data.shape != (int(lp.nproblems), self._a_perm.size):
-                raise ValueError("per-problem A: lp.A.data must be [nproblems, nnz] = (%d, %d); got %r"
-                                 % (lp.nproblems, self._a_perm.size, data.shape))
-            self._a_values = torch.as_tensor(np.ascontiguousarray(data[:, self._a_perm]), device=self.device)
-        return super(HipSparsePrimalNormalSolver, self).solve(lp, verbose=verbose)
-
-    def _launch(self, B, b, c, buf, o):
-        if self._a_perm is not None:
-            av = self._a_values
-            if av is None or av.shape[0] < B:
-                raise ValueError("per-problem A: no values for this batch (use lp.solve(solver))")
-            # a chunk of the host pipeline, or the sub-batch of an hsd='auto' re-solve, addresses its rows of the values
-            # through the offset of its b inside the full batch
-            lo = 0
-            if getattr(self, "_a_row0", None) is not None:
-                lo = self._a_row0
-            _native.check(_native.lib().pycllp_hip_sparse_solve_batch(
-                self._handle, B, self._ptr(av[lo:lo + B]), self._ptr(b), self._ptr(c), self._ptr(buf["x"]), self._ptr(buf["y"]),
-                self._ptr(buf["z"]), self._ptr(buf["pobj"]), self._ptr(buf["dobj"]), self._ptr(buf["status"]),
-                self._ptr(buf["iters"]), ctypes.byref(o), self._stream_ptr()), "pycllp_hip_sparse_solve_batch")
-            return
-        _native.check(_native.lib().pycllp_hip_sparse_solve(
-            self._handle, B, self._ptr(b), self._ptr(c), self._ptr(buf["x"]), self._ptr(buf["y"]),
-            self._ptr(buf["z"]), self._ptr(buf["pobj"]), self._ptr(buf["dobj"]), self._ptr(buf["status"]),
-            self._ptr(buf["iters"]), ctypes.byref(o), self._stream_ptr()), "pycllp_hip_sparse_solve")
-
-    def newton_step(self, x, z, y, b, c, mu, **options):
-        """Stand-alone Newton step dy for B states with the sparse shared A: the reference's ``sparse_solve_primal_normal``
-        kernel (``pycllp/cl/ldl.cl:656-712``) as launched by its ``tests/test_ldl.py:276-361``."""
+        """Stand-alone Newton step dy for B states: the reference's ``solve_primal_normal`` kernel
+        (``pycllp/cl/ldl.cl:602-653``, as launched by its ``tests/test_ldl.py:219-273``), on a sparse shared A its
+        ``sparse_solve_primal_normal`` (``ldl.cl:656-712``, as launched by ``tests/test_ldl.py:276-361``)."""
         if self._handle is None:
             raise RuntimeError("newton_step() called before init()")
         if self._a_perm is not None:
@@ -647,21 +570,29 @@ class HipSparsePrimalNormalSolver(HipDensePrimalNormalSolver):
         B = int(x.shape[0])
         dy = torch.empty((B, self.m), dtype=torch.float64, device=self.device)
         nref = torch.empty(B, dtype=torch.int32, device=self.device)
-        opts = dict(self.options); opts.update(options)
-        o = _native.default_opts(**opts)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().pycllp_hip_sparse_newton(
-                self._handle, B, self._ptr(x), self._ptr(z), self._ptr(y), self._ptr(b), self._ptr(c), float(mu),
-                self._ptr(dy), self._ptr(nref), ctypes.byref(o), self._stream_ptr()), "pycllp_hip_sparse_newton")
+        self._handle.newton(self.stream, x, z, y, b, c, mu, dy, nref, _native.default_opts(**dict(self.options, **options)))
         torch.cuda.synchronize(self.device)
         self.nrefine = nref.cpu().numpy()
         return dy.cpu().numpy()
 
     def launch_info(self):
-        """grid / block / LDS bytes of the last solve and which kernel ran it (``SPARSE_KERNEL_KINDS``)."""
-        vals = [ctypes.c_int() for _ in range(4)]
-        _native.check(_native.lib().pycllp_hip_sparse_launch_info(self._handle, *[ctypes.byref(v) for v in vals]),
-                      "pycllp_hip_sparse_launch_info")
-        d = dict(zip(("grid", "block", "lds_bytes", "kernel"), [v.value for v in vals]))
-        d["variant"], d["kernel"] = SPARSE_KERNEL_KINDS[d["kernel"]]
-        return d
+        """grid / block / LDS bytes of the last solve and, where the sparse path's kernels served it, which one
+        (``SPARSE_KERNEL_KINDS``)."""
+        return self._handle.launch_info()
+
+
+class HipSparsePrimalNormalSolver(HipDensePrimalNormalSolver):
+    """Drop-in for ``cl_sparse_primal_normal`` (``pycllp/solvers/cl.py:127-278``): shared SPARSE constraint matrix, one LP
+    per workgroup, m <= 128 rows and n <= 512 columns (equality form).  Same contract and result attributes as the
+    dense solver; ``init`` takes the CSR arrays of ``lp.A`` (the reference builds them from the densified A,
+    ``cl.py:175-178``), the transposed copy and the structure of A diag(x/z) A' are derived inside the library."""
+    name = 'hip_sparse_primal_normal'
+
+    def _shared_matrix(self, lp):
+        if hasattr(lp.A, "tocsr"):
+            A = sp.csr_matrix(lp.A.tocsr())
+        else:
+            A = sp.csr_matrix(np.asarray(lp.A.todense() if hasattr(lp.A, "todense") else lp.A, dtype=np.float64))
+        A = sp.csr_matrix(A, shape=(int(lp.nrows), int(lp.ncols)))
+        A.sum_duplicates(); A.eliminate_zeros(); A.sort_indices()
+        return A

@@ -95,6 +95,64 @@ def test_solver_fails_loudly_without_gpu():
         solvers.HipDensePrimalNormalSolver(not_an_option=1)
 
 
+def test_plugin_option_semantics_without_gpu():
+    """The constructor options of all four plugins (no GPU needed): the spellings of hsd and autoscale, how FLAG_HSD and
+    FLAG_AUTOSCALE in ``flags`` are absorbed, the combinations that are refused, and the bounded plugins' rejections."""
+    from pycllp_amd import _native
+    flags = lambda s: int(s.options.get("flags", 0))      # noqa: E731
+    for cls in (solvers.HipDensePrimalNormalSolver, solvers.HipSparsePrimalNormalSolver):
+        assert cls().hsd == "auto" and cls().autoscale == "auto" and flags(cls()) == 0
+        for v in (True, 1, np.True_, np.int64(1)):
+            s = cls(hsd=v)
+            assert s.hsd is True and flags(s) == _native.FLAG_HSD
+            s = cls(autoscale=v)
+            assert s.autoscale is True and flags(s) == _native.FLAG_AUTOSCALE
+        for v in (False, 0, np.False_):
+            s = cls(hsd=v, autoscale=v)
+            assert s.hsd is False and s.autoscale is False and flags(s) == 0
+        assert cls(autoscale=None).autoscale is False
+        s = cls(flags=_native.FLAG_HSD)
+        assert s.hsd is True and flags(s) == _native.FLAG_HSD
+        s = cls(autoscale=False, flags=_native.FLAG_AUTOSCALE)
+        assert s.autoscale is True and flags(s) == _native.FLAG_AUTOSCALE
+        s = cls(predcorr=True, hsd=False, flags=_native.FLAG_FORCE_GUARD_PATH)
+        assert s.hsd is False and flags(s) == _native.FLAG_PREDCORR | _native.FLAG_FORCE_GUARD_PATH
+        assert cls(predcorr=True).hsd == "auto" and flags(cls(predcorr=True)) == _native.FLAG_PREDCORR
+        s = cls(warm_start=1, warm_lift=0)
+        assert s.warm_start is True and s.warm_lift == 0.0 and flags(s) == 0
+        s = cls(max_iter=50, eps=1e-9)
+        assert (s.options["max_iter"], s.options["eps"], flags(s)) == (50, 1e-9, 0)
+        for kw in (dict(hsd="yes"), dict(hsd=None), dict(hsd=1.5), dict(autoscale="sometimes"),
+                   dict(predcorr=True, hsd=True), dict(predcorr=1, hsd=np.True_),
+                   dict(warm_lift=-1e-3), dict(warm_lift=float("nan"))):
+            with pytest.raises(ValueError):
+                cls(**kw)
+        with pytest.raises(TypeError):
+            cls(not_an_option=1)
+    for cls in (solvers.HipGeneralPrimalNormalSolver, solvers.HipSparseGeneralPrimalNormalSolver):
+        assert cls().hsd == "auto" and cls().autoscale == "auto" and cls(hsd=False).hsd is False
+        for v in (True, 1, np.True_):
+            assert cls(autoscale=v).autoscale is True
+        for v in (False, 0, np.False_, None):
+            assert cls(autoscale=v).autoscale is False
+        assert cls(autoscale=False, flags=_native.FLAG_AUTOSCALE).autoscale is True
+        assert cls(max_iter=50).options["max_iter"] == 50
+        for kw in (dict(hsd=True), dict(hsd=1), dict(hsd=np.True_), dict(hsd="yes"), dict(hsd=None),
+                   dict(predcorr=True), dict(warm_start=True), dict(autoscale="sometimes"),
+                   dict(flags=_native.FLAG_HSD), dict(flags=_native.FLAG_PREDCORR), dict(flags=_native.FLAG_WARM_START),
+                   dict(flags=_native.FLAG_WAVE_KERNEL), dict(flags=_native.FLAG_NO_SLACK_PATH)):
+            with pytest.raises(ValueError):
+                cls(**kw)
+        with pytest.raises(TypeError):
+            cls(not_an_option=1)
+        with pytest.raises(TypeError):
+            cls(warm_lift=0.0)         # an option of the dense plugins only
+    for flag in (_native.FLAG_BLOCK_KERNEL, _native.FLAG_FORCE_GUARD_PATH):
+        solvers.HipGeneralPrimalNormalSolver(flags=flag)
+        with pytest.raises(ValueError):
+            solvers.HipSparseGeneralPrimalNormalSolver(flags=flag)
+
+
 def test_product_does_not_import_the_oracle():
     import os
     import re
@@ -107,11 +165,11 @@ def test_product_does_not_import_the_oracle():
                 assert "liboracle" not in text and "libhsd_ref" not in text, f
 
 
-def test_packed_result_layout_round_trip():
+def test_packed_result_layout_round_trip_through_unpack():
     """The result arrays of a solve are views into one packed byte buffer (what the multi-GPU gather ships): the layout
     must be aligned, non-overlapping, have the gathered arrays as a contiguous prefix, and unpack() must invert it."""
     import torch
-    from pycllp_amd.solvers.hip import HipDensePrimalNormalSolver
+    from pycllp_amd.solvers.hip import HipDensePrimalNormalSolver, unpack
     s = HipDensePrimalNormalSolver()
     s.m, s.n = 5, 13
     for B in (0, 1, 7, 1000):
@@ -123,11 +181,11 @@ def test_packed_result_layout_round_trip():
         assert all(off % 256 == 0 for off, _, _ in spans)
         assert lay["x"][0] + lay["x"][1] <= lay["_gather_bytes"] <= lay["z"][0] <= lay["_total_bytes"]
         packed = torch.zeros(max(lay["_total_bytes"], 256), dtype=torch.uint8)
-        views = s.unpack(packed, lay, names=("pobj", "dobj", "status", "iters", "y", "x", "z"))
+        views = unpack(packed, lay, names=("pobj", "dobj", "status", "iters", "y", "x", "z"))
         assert views["x"].shape == (B, 13) and views["y"].shape == (B, 5) and views["status"].dtype == torch.int32
         if B:
             views["x"][:] = 1.5; views["status"][:] = 7; views["z"][:] = -2.0
-            again = s.unpack(packed[:lay["_gather_bytes"]].clone(), lay)      # what a peer would receive
+            again = unpack(packed[:lay["_gather_bytes"]].clone(), lay)      # what a peer would receive
             assert float(again["x"].sum()) == 1.5 * B * 13 and int(again["status"].sum()) == 7 * B
 
 
