@@ -9,7 +9,7 @@
  * may be issued from several host threads and on several streams with one handle (the caller keeps their output
  * buffers apart).  A handle keeps 64 device work-queue counters; when 64 launches of one handle are still in flight
  * the next call waits on the host for the oldest of them (the only place a solve entry may block).
- * *_launch_info report the plan of the LAST launch on the handle.
+ * *_launch_info and *_variant_info report the plan of the LAST launch on the handle.
  * Return value: 0 on success, a negative PYCLLP_E_* code for argument errors, or a positive
  * hipError_t for runtime failures (pycllp_hip_last_error() gives the text).
  *
@@ -152,14 +152,24 @@ int pycllp_hip_dense_newton(pycllp_hip_dense *handle, long B, const double *x_de
                             const double *y_dev, const double *b_dev, const double *c_dev, double mu,
                             double *dy_dev, int *nrefine_dev, const pycllp_hip_opts *opts, void *stream);
 
-/* Kernel-level statistics of the last solve launch on this handle (host values). */
+/* Kernel-level statistics of the last launch (solve, bounded solve or Newton step) on this handle (host values).
+ * m_pad, n_pad: the (MP, NP) of the lane-group kernel that ran -- of the slack-aware table when that one ran -- and, before
+ * the first launch, the shape of the general table's kernel that covers (m, n).  A handle handed to the sparse path's
+ * kernels reports 128, 512 there (pycllp_hip_dense_variant_info gives the shape that served). */
 int pycllp_hip_dense_launch_info(const pycllp_hip_dense *handle, int *grid, int *block, int *lds_bytes,
                                  int *m_pad, int *n_pad);
 
 /* Which kernel family serves this handle: -1 = the lane-group kernels (m <= 32, n <= 128); otherwise the LP was handed to
  * the sparse path's kernels at init and the value is that of pycllp_hip_sparse_launch_info's `kernel` for the last launch
- * (0 = workgroup-per-LP block kernel, 1 = wavefront-per-LP kernel on term tables, 2 = the same on a dense image of A). */
+ * (0 = workgroup-per-LP block kernel, 1 = wavefront-per-LP kernel on term tables, 2 = the same on a dense image of A,
+ * 3 = the large-LP kernel with its Gram from a term list, 4 = the same on the matrix cores). */
 int pycllp_hip_dense_kernel_kind(const pycllp_hip_dense *handle);
+
+/* The compiled instantiation that served the last launch on this handle.  Lane-group kernels: *a, *b = its (MP, NP) and
+ * *slack = 1 when it is one of the slack-aware kernels (every bounded solve), 0 when it is one of the general ones (every
+ * Newton step); (0, 0, 0) before the first launch.  A handle handed to the sparse path's kernels: *a, *b = the (MB, NQ) of
+ * pycllp_hip_sparse_variant_info and *slack = -1. */
+int pycllp_hip_dense_variant_info(const pycllp_hip_dense *handle, int *a, int *b, int *slack);
 
 void pycllp_hip_dense_free(pycllp_hip_dense *handle);
 
@@ -228,9 +238,13 @@ int pycllp_hip_sparse_newton(pycllp_hip_sparse *handle, long B, const double *x_
                              const double *y_dev, const double *b_dev, const double *c_dev, double mu, double *dy_dev,
                              int *nrefine_dev, const pycllp_hip_opts *opts, void *stream);
 /* grid (workgroups), threads per workgroup, LDS bytes per workgroup and kernel (0 = workgroup-per-LP block kernel,
- * 1 = register-resident wavefront-per-LP kernel on term tables, 2 = the same on a dense image of A) of the last solve
- * launch on this handle (host values; not thread-safe). */
+ * 1 = register-resident wavefront-per-LP kernel on term tables, 2 = the same on a dense image of A, 3 = the large-LP kernel
+ * with its Gram from a term list, 4 = the same on the matrix cores) of the last launch (solve or Newton step) on this handle
+ * (host values). */
 int pycllp_hip_sparse_launch_info(const pycllp_hip_sparse *handle, int *grid, int *block, int *lds_bytes, int *kernel);
+/* (MB, NQ) -- 16-row blocks, 64-column registers -- of the wavefront-per-LP kernel's plan that served the last launch on
+ * this handle; (0, 0) when that launch ran on the block or the large-LP kernel, or before the first launch. */
+int pycllp_hip_sparse_variant_info(const pycllp_hip_sparse *handle, int *mb, int *nq);
 void pycllp_hip_sparse_free(pycllp_hip_sparse *handle);
 
 #ifdef __cplusplus

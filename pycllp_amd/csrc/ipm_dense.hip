@@ -492,9 +492,10 @@ struct pycllp_hip_dense {
     double* pack = nullptr;
     double* a_rm = nullptr;   // row-major copy of A [m,n] for the group kernel
     QueueRing ring; // device work-queue heads of the group kernel
-    mutable std::mutex info_mu;   // guards grid/block/lds/mp/np (what launch_info reports: the LAST launch)
+    mutable std::mutex info_mu;   // guards grid/block/lds/mp/np/sl (what launch_info and variant_info report: the LAST launch)
     int variant_sl = -1; // index into kSlackVariants when the last m columns of A are the identity, else -1
     int grid = 0, block = 0, lds = 0;
+    int sl = -1;         // the last launch ran a kernel of the slack-aware table (1) or of the general one (0); -1: none yet
     int num_cu = 0;
     int max_lds = 0;
     struct pycllp_hip_sparse* sp = nullptr;   // LPs beyond the lane-group kernels (m <= 128, n <= 512): served by the sparse path's kernels
@@ -514,11 +515,11 @@ static int pick_wpb(const pycllp_hip_dense* h) {
     return wpb;
 }
 
-struct LaunchPlan { int grid, block, lds, mp, np; };
+struct LaunchPlan { int grid, block, lds, mp, np, sl; };   // sl: a kernel of the slack-aware table
 
 static void publish(pycllp_hip_dense* h, const LaunchPlan& p) {
     std::lock_guard<std::mutex> g(h->info_mu);
-    h->grid = p.grid; h->block = p.block; h->lds = p.lds; h->mp = p.mp; h->np = p.np;
+    h->grid = p.grid; h->block = p.block; h->lds = p.lds; h->mp = p.mp; h->np = p.np; h->sl = p.sl;
 }
 
 template <int MP, int NP>
@@ -529,7 +530,7 @@ static LaunchPlan plan(const pycllp_hip_dense* h, long B) {
     const long resident = (long)h->num_cu * ((size_t)h->max_lds / G::lds_bytes(wpb) >= 2 ? 2 : 1);
     if (blocks > resident) blocks = resident;
     if (blocks < 1) blocks = 1;
-    return LaunchPlan{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP};
+    return LaunchPlan{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP, 0};
 }
 
 template <int MP, int NP>
@@ -563,7 +564,7 @@ static LaunchPlan plan_group(const pycllp_hip_dense* h, long B, int wpb, const D
     long blocks = (B + wpb - 1) / wpb;
     if (blocks > resident) blocks = resident;
     if (blocks < 1) blocks = 1;
-    return LaunchPlan{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP};
+    return LaunchPlan{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP, SL ? 1 : 0};
 }
 
 // Sets the kernel's LDS, runs launch(qhead) on a queue-ring slot and publishes the plan for launch_info
@@ -616,7 +617,9 @@ static hipError_t launch_newton(pycllp_hip_dense* h, long B, const double* x, co
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((newton_kernel<MP, NP>), dim3(p.grid), dim3(p.block), p.lds, st, h->m, h->n, B,
                        h->pack, x, z, y, b, c, mu, dy, nref, o);
-    return hipGetLastError();
+    e = hipGetLastError();
+    publish(h, p);
+    return e;
 }
 
 struct Variant {
@@ -915,6 +918,20 @@ int pycllp_hip_dense_launch_info(const pycllp_hip_dense* h, int* grid, int* bloc
     if (lds_bytes) *lds_bytes = h->lds;
     if (m_pad) *m_pad = h->mp;
     if (n_pad) *n_pad = h->np;
+    return 0;
+}
+
+int pycllp_hip_dense_variant_info(const pycllp_hip_dense* h, int* a, int* b, int* slack) {
+    if (!h) return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_variant_info: bad argument");
+    if (h->sp) {
+        if (slack) *slack = -1;
+        return pycllp_hip_sparse_variant_info(h->sp, a, b);
+    }
+    std::lock_guard<std::mutex> g(h->info_mu);
+    const bool ran = h->sl >= 0;
+    if (a) *a = ran ? h->mp : 0;
+    if (b) *b = ran ? h->np : 0;
+    if (slack) *slack = ran ? h->sl : 0;
     return 0;
 }
 
@@ -1242,7 +1259,10 @@ int pycllp_hip_sparse_newton(pycllp_hip_sparse* h, long B, const double* x_dev, 
         return 0;
     }
     if (h->wreg && !(o.flags & PYCLLP_FLAG_BLOCK_KERNEL)) {
-        hipError_t e = wreg_launch_newton(h->wreg, B, x_dev, z_dev, y_dev, b_dev, c_dev, mu, dy_dev, nrefine_dev, o, h->num_cu, st);
+        int grid_w = 0;
+        hipError_t e = wreg_launch_newton(h->wreg, B, x_dev, z_dev, y_dev, b_dev, c_dev, mu, dy_dev, nrefine_dev, o, h->num_cu, st,
+                                          &grid_w);
+        record_launch(h, h->wreg, grid_w);
         if (e != hipSuccess) return set_err((int)e, "newton_wreg_kernel launch");
         return 0;
     }
@@ -1257,6 +1277,7 @@ int pycllp_hip_sparse_newton(pycllp_hip_sparse* h, long B, const double* x_dev, 
                            (int*)nullptr, qhead, (const int*)nullptr, mu, dy_dev, nrefine_dev, (const double*)nullptr, o);
         return hipGetLastError();
     });
+    record_launch(h, nullptr, (int)blocks);
     if (e != hipSuccess) return set_err((int)e, "ipm_block_kernel (Newton mode) launch");
     return 0;
 }
@@ -1268,6 +1289,13 @@ int pycllp_hip_sparse_launch_info(const pycllp_hip_sparse* h, int* grid, int* bl
     if (block) *block = h->last_plan ? wreg_block_threads(h->last_plan) : BLK_T;
     if (lds_bytes) *lds_bytes = h->last_plan ? wreg_lds_bytes(h->last_plan) : h->lds;
     if (kernel) *kernel = h->big ? (big_dense_mode(h->big) ? 4 : 3) : (h->last_plan ? wreg_variant(h->last_plan) : 0);
+    return 0;
+}
+
+int pycllp_hip_sparse_variant_info(const pycllp_hip_sparse* h, int* mb, int* nq) {
+    if (!h) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_variant_info: bad argument");
+    std::lock_guard<std::mutex> g(h->info_mu);
+    wreg_shape(h->last_plan, mb, nq);
     return 0;
 }
 

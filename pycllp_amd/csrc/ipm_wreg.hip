@@ -2346,6 +2346,10 @@ void wreg_plan_free(WregPlan* p) {
 int wreg_lds_bytes(const WregPlan* p) { return p ? p->tab.lds_bytes : 0; }
 int wreg_block_threads(const WregPlan* p) { return p ? 64 * p->tab.wpb : 0; }
 int wreg_variant(const WregPlan* p) { return p ? (p->da ? 2 : 1) : 0; }
+void wreg_shape(const WregPlan* p, int* mb, int* nq) {
+    if (mb) *mb = p ? p->mb : 0;
+    if (nq) *nq = p ? p->nq : 0;
+}
 int wreg_has_predcorr(const WregPlan* p) { return p ? 1 : 0; }
 
 // the launchers of the plan's (MB, NQ) among the plain (pc: predictor-corrector, bd: bounded) kernels of its kind, or null
@@ -2395,7 +2399,8 @@ hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* b, const
 }
 
 hipError_t wreg_launch_newton(WregPlan* p, long B, const double* x, const double* z, const double* y, const double* b,
-                              const double* c, double mu, double* dy, int* nref, DevOpts o, int num_cu, hipStream_t st) {
+                              const double* c, double mu, double* dy, int* nref, DevOpts o, int num_cu, hipStream_t st,
+                              int* grid_out) {
     const WVariant* v = plan_launchers(p, false);
     if (!v || !v->newton) return hipErrorInvalidValue;
     int* qhead = nullptr;
@@ -2404,6 +2409,7 @@ hipError_t wreg_launch_newton(WregPlan* p, long B, const double* x, const double
     e = hipMemsetAsync(qhead, 0, sizeof(int), st);
     long grid = std::min((long)num_cu, (B + p->tab.wpb - 1) / p->tab.wpb);
     if (grid < 1) grid = 1;
+    if (grid_out) *grid_out = (int)grid;
     if (e == hipSuccess) e = v->newton(p->tab, B, x, z, y, b, c, mu, dy, nref, qhead, o, (int)grid, st);
     hipError_t e2 = hipFreeAsync(qhead, st);
     return e != hipSuccess ? e : e2;

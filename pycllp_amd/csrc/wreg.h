@@ -102,9 +102,10 @@ hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* b, const
                                      DevOpts o, int num_cu, hipStream_t st, int* grid_out);
 
 // One Newton step for B states (semantics of pycllp_hip_dense_newton).  guard_hit[0] is set to 1 if any state would
-// have needed the guard (the stand-alone step then simply ran without it).
+// have needed the guard (the stand-alone step then simply ran without it).  *grid_out (optional): the workgroups launched.
 hipError_t wreg_launch_newton(WregPlan* p, long B, const double* x, const double* z, const double* y, const double* b,
-                              const double* c, double mu, double* dy, int* nref, DevOpts o, int num_cu, hipStream_t st);
+                              const double* c, double mu, double* dy, int* nref, DevOpts o, int num_cu, hipStream_t st,
+                              int* grid_out);
 
 // out = (L D L')^-1 rhs with L D L' = A for B explicit dense symmetric matrices A [B, n, n] (lower triangle read),
 // n <= 128, pivots floored at floor_ (0: plain LDL'); one matrix per wavefront, factor held in registers.
@@ -113,5 +114,6 @@ hipError_t wreg_launch_ldl_solve(int n, long B, const double* A, const double* r
 int wreg_lds_bytes(const WregPlan* p);
 int wreg_block_threads(const WregPlan* p);   // 64 x waves per workgroup
 int wreg_variant(const WregPlan* p);         // 1 = term tables, 2 = dense image
+void wreg_shape(const WregPlan* p, int* mb, int* nq);   // the plan's (MB, NQ); (0, 0) for a null plan
 int wreg_has_predcorr(const WregPlan* p);   // 1 when the plan's kernels have a PYCLLP_FLAG_PREDCORR variant (every plan of the wave kernel)
 #endif

@@ -132,6 +132,10 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
         """The LPs among ``idx`` (not optimal on the native kernel) that ``hsd='auto'`` solves again through the expansion."""
         return idx
 
+    def launch_info(self):
+        """``Handle.launch_info()`` of the native kernel's last launch (None when no handle serves the LP)."""
+        return None if self._handle is None else self._handle.launch_info()
+
     def _solve_bounded(self, blp, bmap):
         """One upload, one launch of the bounded kernel, one download; None if the library declines A^ (PYCLLP_E_UNSUPPORTED)."""
         B, mk, N = blp.nproblems, blp.nrows, blp.ncols

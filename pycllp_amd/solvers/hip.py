@@ -195,8 +195,10 @@ class Handle(object):
         self._call("newton", self, int(x.shape[0]), x, z, y, b, c, float(mu), dy, nrefine, ctypes.byref(o), self._stream(stream))
 
     def launch_info(self):
-        """grid / block / LDS bytes of the last solve (dense family: the padded m, n too) and, where one of the kernels of
-        ``SPARSE_KERNEL_KINDS`` served it, its ``variant`` and ``kernel``."""
+        """grid / block / LDS bytes of the last launch (dense family: the padded m, n too) and, where one of the kernels of
+        ``SPARSE_KERNEL_KINDS`` served it, its ``variant`` and ``kernel``.  The compiled instantiation that served it:
+        ``wave_shape`` (MB, NQ) on the wavefront-per-LP kernel, ``group_shape`` (MP, NP) and ``slack`` (1: the slack-aware
+        kernel) on the lane-group kernels."""
         keys = ("grid", "block", "lds_bytes") + (("m_pad", "n_pad") if self.family == "dense" else ("kernel",))
         vals = [ctypes.c_int() for _ in keys]
         self._call("launch_info", self, *[ctypes.byref(v) for v in vals])
@@ -204,6 +206,13 @@ class Handle(object):
         kind = _native.lib().pycllp_hip_dense_kernel_kind(self) if self.family == "dense" else d["kernel"]
         if kind >= 0:
             d["variant"], d["kernel"] = SPARSE_KERNEL_KINDS[kind]
+        shape = [ctypes.c_int() for _ in range(3 if self.family == "dense" else 2)]
+        self._call("variant_info", self, *[ctypes.byref(v) for v in shape])
+        a, b = shape[0].value, shape[1].value
+        if a > 0 and (self.family == "sparse" or shape[2].value < 0):
+            d["wave_shape"] = (a, b)
+        elif a > 0:
+            d["group_shape"], d["slack"] = (a, b), shape[2].value
         return d
 
     def free(self):

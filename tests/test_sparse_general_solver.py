@@ -19,22 +19,23 @@ def mixed_kinds(m):
     return ["le"] + [KINDS[i % len(KINDS)] for i in range(m - 1)]
 
 
-def make_sparse_general(m, n, B, seed, density, fixed=0, mixed_u=False):
+def make_sparse_general(m, n, B, seed, density, fixed=0, mixed_u=False, kinds=None):
     """``make_general``'s batch with a SPARSE shared A: about ``density`` of the entries of rows 1.. are non-zero, every
-    column has one at least, row 0 is dense and positive."""
+    column has one at least, row 0 is dense and positive.  ``kinds``: the row kinds (default ``mixed_kinds(m)``)."""
+    kinds = mixed_kinds(m) if kinds is None else kinds
     rng = np.random.default_rng(seed)
     mask = rng.uniform(size=(m, n)) < density
     mask[rng.integers(1, m, n), np.arange(n)] = True
     mask[0] = True
     A = np.where(mask, rng.uniform(-1, 1, (m, n)), 0.0)
     A[0] = rng.uniform(0.1, 1, n)
-    g = make_general(m, n, B, seed, mixed_u=mixed_u, kinds=mixed_kinds(m), fixed=fixed)
+    g = make_general(m, n, B, seed, mixed_u=mixed_u, kinds=kinds, fixed=fixed)
     # same bounds, costs and offsets, the row bounds rebuilt around an interior point for the sparse A
     x0 = g.l + rng.uniform(0.2, 0.8, (B, n)) * np.where(np.isfinite(g.u), g.u - g.l, 1.0)
     x0[:, :fixed] = g.l[:, :fixed]
     Ax = x0 @ A.T
     a, b = np.full((B, m), -np.inf), np.full((B, m), np.inf)
-    for i, k in enumerate(mixed_kinds(m)):
+    for i, k in enumerate(kinds):
         if k == "eq":
             a[:, i] = b[:, i] = Ax[:, i]
         elif k == "rng":
