@@ -171,6 +171,9 @@ int pycllp_hip_dense_kernel_kind(const pycllp_hip_dense *handle);
  * pycllp_hip_sparse_variant_info and *slack = -1. */
 int pycllp_hip_dense_variant_info(const pycllp_hip_dense *handle, int *a, int *b, int *slack);
 
+/* pycllp_hip_sparse_plan_info of a handle handed to the sparse path's kernels; (0, 0, -1, -1) on the lane-group kernels. */
+int pycllp_hip_dense_plan_info(const pycllp_hip_dense *handle, int *wgpc, int *bnc, int *factor_in_lds, int *a_in_lds);
+
 void pycllp_hip_dense_free(pycllp_hip_dense *handle);
 
 /* Stand-alone batched LDL' (modified != 0: Nocedal-Wright modified LDL' with the given beta and delta) of B
@@ -245,6 +248,13 @@ int pycllp_hip_sparse_launch_info(const pycllp_hip_sparse *handle, int *grid, in
 /* (MB, NQ) -- 16-row blocks, 64-column registers -- of the wavefront-per-LP kernel's plan that served the last launch on
  * this handle; (0, 0) when that launch ran on the block or the large-LP kernel, or before the first launch. */
 int pycllp_hip_sparse_variant_info(const pycllp_hip_sparse *handle, int *mb, int *nq);
+/* The LDS plan of the workgroup-per-LP kernel that served the last launch on this handle (any pointer may be NULL).
+ * Large-LP kernel: *wgpc, *bnc = the compiled instantiation ipm_big_kernel<WGPC, BNC> that was launched (WGPC workgroups per
+ * CU, BNC N-vector registers per thread) and *factor_in_lds = 1 when the blocks of the factor sat in LDS, 0 when they sat in
+ * the L2-resident workspace; (0, 0, -1) otherwise.  Block kernel: *a_in_lds = 1 when the CSR / CSC copy of A sat in LDS, 0
+ * when it was read through L2; -1 otherwise (a launch of the wavefront-per-LP kernel leaves it at -1 although the block
+ * kernel stands behind it for the LPs it defers). */
+int pycllp_hip_sparse_plan_info(const pycllp_hip_sparse *handle, int *wgpc, int *bnc, int *factor_in_lds, int *a_in_lds);
 void pycllp_hip_sparse_free(pycllp_hip_sparse *handle);
 
 #ifdef __cplusplus

@@ -45,7 +45,7 @@ SIGNATURES = (
     ("pycllp_hip_dense_solve_bounded", _solve(11), _i),         # b, c, u, x, y, z, s, pobj, dobj, status, iters
     ("pycllp_hip_dense_newton", [_p, _l, _p, _p, _p, _p, _p, _d, _p, _p, _O, _p], _i),
     ("pycllp_hip_dense_launch_info", [_p] + [_ip] * 5, _i), ("pycllp_hip_dense_kernel_kind", [_p], _i),
-    ("pycllp_hip_dense_variant_info", [_p] + [_ip] * 3, _i),
+    ("pycllp_hip_dense_variant_info", [_p] + [_ip] * 3, _i), ("pycllp_hip_dense_plan_info", [_p] + [_ip] * 4, _i),
     ("pycllp_hip_dense_free", [_p], None),
     ("pycllp_hip_ldl", [_i, _l, _p, _p, _p, _i, _d, _d, _p], _i),
     ("pycllp_hip_ldl_solve", [_i, _l, _p, _p, _p, _i, _d, _d, _p], _i),
@@ -57,6 +57,7 @@ SIGNATURES = (
     ("pycllp_hip_sparse_solve_bounded", _solve(11), _i),
     ("pycllp_hip_sparse_newton", [_p, _l, _p, _p, _p, _p, _p, _d, _p, _p, _O, _p], _i),
     ("pycllp_hip_sparse_launch_info", [_p] + [_ip] * 4, _i), ("pycllp_hip_sparse_variant_info", [_p] + [_ip] * 2, _i),
+    ("pycllp_hip_sparse_plan_info", [_p] + [_ip] * 4, _i),
     ("pycllp_hip_sparse_free", [_p], None),
 )
 EXPORTS = tuple(name for name, _, _ in SIGNATURES)

@@ -22,7 +22,10 @@ hipError_t big_launch_solve(BigPlan* p, long B, const double* b, const double* c
 // One Newton step for B states (semantics of pycllp_hip_dense_newton).
 hipError_t big_launch_newton(BigPlan* p, long B, const double* x, const double* z, const double* y, const double* b,
                              const double* c, double mu, double* dy, int* nref, int* qhead, DevOpts o, int num_cu,
-                             hipStream_t st);
+                             hipStream_t st, int* grid_out);
 int big_lds_bytes(const BigPlan* p);
 int big_dense_mode(const BigPlan* p);   // 1: Gram product on the matrix cores from a dense image; 0: term list
+// the instantiation ipm_big_kernel<WGPC, BNC> the plan's last launch ran ((0, 0) before the first) and whether the factor
+// blocks sat in LDS (-1 before the first launch)
+void big_shape(const BigPlan* p, int* wgpc, int* bnc, int* m_in_lds);
 #endif

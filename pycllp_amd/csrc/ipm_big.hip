@@ -1,6 +1,7 @@
 // ipm_big.hip -- LPs beyond the register-resident kernels: one LP per WORKGROUP (four wavefronts), 128 < m <= 256 rows
 // and/or 512 < n <= 1280 columns (equality form), the m x m normal-equations matrix and its LDL' factor as 16 x 16 blocks
-// in LDS when they fit (m <= ~144) and in an L2-resident workspace otherwise.
+// in LDS when they fit beside a second workgroup (m <= 96 at most, fewer rows as n grows) and in an L2-resident workspace
+// otherwise.  Two or three workgroups share a compute unit at every size the kernel takes, never one (BIG_SHAPES below).
 //
 // Why: the reference's hosts take any (m, n) (pycllp/solvers/cl.py:28-83, 127-278; examples/random_problem.py:30-49 is run
 // with arbitrary sizes); the lane-group kernels stop at m = 32, the wavefront-per-LP kernel (ipm_wreg.hip) at m = 128 --
@@ -66,7 +67,7 @@ __device__ __forceinline__ double bmax(double v, double* red, int tid) {
 }
 
 // doubles of LDS the kernel carves (host and device agree through this one function)
-__host__ __device__ inline size_t big_lds_doubles(int MB, int n, bool m_in_lds) {
+__host__ __device__ constexpr size_t big_lds_doubles(int MB, int n, bool m_in_lds) {
     const size_t MP = 16 * (size_t)MB, NPv = ((size_t)n + 7) & ~(size_t)7;
     return (m_in_lds ? (size_t)MB * (MB + 1) / 2 * 256 : 0) + (size_t)MB * 256 + 2 * NPv + 9 * MP + 272 + 256 + 32;
 }
@@ -772,6 +773,7 @@ struct BigPlan {
     BigTab tab;
     void* dev_blob = nullptr;
     size_t ws_doubles_per_block = 0;
+    std::atomic<int> launched{0};        // WGPC << 8 | BNC of the instantiation the last launch ran (0: none yet)
 };
 
 int big_plan_create(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds, hipStream_t st,
@@ -886,20 +888,48 @@ void big_plan_free(BigPlan* p) {
 int big_lds_bytes(const BigPlan* p) { return p ? p->tab.lds_bytes : 0; }
 int big_dense_mode(const BigPlan* p) { return p ? p->tab.dense : 0; }
 
+// The compiled instantiations (WGPC workgroups per CU, BNC N-vector registers per thread), in the order the selection walks
+// them: the first with WGPC = the workgroups per CU the plan's LDS allows and n <= 256 BNC serves the plan.
+#define BIG_SHAPES(X) X(3, 2) X(2, 2) X(3, 3) X(2, 3) X(3, 5) X(2, 5)
+using big_kernel_fn = decltype(&ipm_big_kernel<2, 2>);
+struct BigVariant { int wgpc, bnc; big_kernel_fn kern; };
+static const BigVariant kBigVariants[] = {
+#define X(W, C) {W, C, ipm_big_kernel<W, C>},
+    BIG_SHAPES(X)
+#undef X
+};
+static_assert(BNC_MAX == 5, "BIG_SHAPES ends at BNC = BIG_MAX_N / BT");
+constexpr long BIG_CU_LDS = 160 * 1024;
+// the largest plan (every row and column, the factor in the workspace) still leaves room for a second workgroup, and a
+// factor in LDS is only planned where two fit (big_plan_create): no plan runs one workgroup per CU
+static_assert(2 * sizeof(double) * big_lds_doubles(BIG_MAX_M / 16, BIG_MAX_N, false) <= (size_t)BIG_CU_LDS,
+              "a plan that leaves one workgroup per CU needs an instantiation of its own");
+
+// workgroups per CU: the kernel is bound by the latency of its L2 / LDS round trips, co-resident workgroups fill them.
+// Three where the LDS allows (the instances compiled for 168 registers per lane), else two (256 registers per lane).
+static const BigVariant* big_select(int n, int lds_bytes) {
+    const int per_cu = (3 * (long)lds_bytes <= BIG_CU_LDS) ? 3 : 2;
+    for (const BigVariant& v : kBigVariants)
+        if (v.wgpc == per_cu && n <= v.bnc * BT) return &v;
+    return nullptr;
+}
+
+void big_shape(const BigPlan* p, int* wgpc, int* bnc, int* m_in_lds) {
+    const int l = p ? p->launched.load() : 0;
+    if (wgpc) *wgpc = l >> 8;
+    if (bnc) *bnc = l & 255;
+    if (m_in_lds) *m_in_lds = (p && l) ? p->tab.m_in_lds : -1;
+}
+
 static hipError_t big_launch(BigPlan* p, long B, const double* b, const double* c, double* x, double* y, double* z, double* pobj,
                              double* dobj, int* status, int* iters, int* qhead, double mu, double* nwt_dy, int* nwt_nref,
                              DevOpts o, int num_cu, hipStream_t st, int* grid_out) {
     long cus = (long)num_cu - o.reserve_cus > 0 ? (long)num_cu - o.reserve_cus : 1;
-    // two workgroups per CU where the LDS allows it (256 registers per lane each): the kernel is bound by the latency of its
-    // L2 / LDS round trips, and a second workgroup fills them
-    // workgroups per CU: the kernel is bound by the latency of its L2 / LDS round trips, co-resident workgroups fill them.
-    // Three where the LDS allows (the instance compiled for 168 registers per lane), else two, else one.
-    const long per_cu = (3 * (long)p->tab.lds_bytes <= 160 * 1024) ? 3 : ((2 * (long)p->tab.lds_bytes <= 160 * 1024) ? 2 : 1);
-    cus *= per_cu;
-    const int n_ = p->tab.n;
-    auto kern = (n_ <= 2 * BT) ? ((per_cu == 3) ? ipm_big_kernel<3, 2> : ipm_big_kernel<2, 2>)
-              : (n_ <= 3 * BT) ? ((per_cu == 3) ? ipm_big_kernel<3, 3> : ipm_big_kernel<2, 3>)
-                               : ((per_cu == 3) ? ipm_big_kernel<3, BNC_MAX> : ipm_big_kernel<2, BNC_MAX>);
+    const BigVariant* v = big_select(p->tab.n, p->tab.lds_bytes);
+    if (!v) return hipErrorInvalidConfiguration;
+    const big_kernel_fn kern = v->kern;
+    p->launched.store(v->wgpc << 8 | v->bnc);
+    cus *= v->wgpc;
     long grid = std::min(cus, B);
     if (grid < 1) grid = 1;
     if (grid_out) *grid_out = (int)grid;
@@ -925,7 +955,7 @@ hipError_t big_launch_solve(BigPlan* p, long B, const double* b, const double* c
 
 hipError_t big_launch_newton(BigPlan* p, long B, const double* x, const double* z, const double* y, const double* b,
                              const double* c, double mu, double* dy, int* nref, int* qhead, DevOpts o, int num_cu,
-                             hipStream_t st) {
+                             hipStream_t st, int* grid_out) {
     return big_launch(p, B, b, c, (double*)x, (double*)y, (double*)z, nullptr, nullptr, nullptr, nullptr, qhead, mu, dy, nref, o,
-                      num_cu, st, nullptr);
+                      num_cu, st, grid_out);
 }

@@ -685,6 +685,8 @@ struct pycllp_hip_sparse {
     BigPlan* big = nullptr;       // LPs beyond m = 128 / n = 512: the workgroup-per-LP kernel of ipm_big.hip serves the handle alone
     WregPlan* wreg_pa = nullptr;  // its per-problem-A plan (structure tables only), built by the first pycllp_hip_sparse_solve_batch
     WregPlan* last_plan = nullptr;   // the wave kernel's plan when the last solve ran on it, else null
+    int last_a_in_lds = -1;          // the block kernel served the last launch: whether A's CSR / CSC copy sat in LDS; else -1
+    int last_lds = 0;                // ... and the LDS bytes of that launch
     bool wreg_pa_tried = false;
     WregPlan* wreg_bd = nullptr;  // the plan of the bounded wave kernel (t and s behind every wave area), built by the first
     bool wreg_bd_tried = false;   // pycllp_hip_sparse_solve_bounded (under info_mu)
@@ -692,10 +694,11 @@ struct pycllp_hip_sparse {
     std::vector<double> host_val; std::vector<int> host_ptr, host_col;   // host CSR copy (what a PA plan is built from)
 };
 
-// what launch_info reports: the last solve ran on the wave kernel with `plan` (null: on the block or large-LP kernel)
-static void record_launch(pycllp_hip_sparse* h, WregPlan* plan, int grid) {
+// what launch_info reports: the last solve ran on the wave kernel with `plan` (null: on the block or large-LP kernel; the
+// block kernel with `a_in_lds` and `lds` bytes of LDS)
+static void record_launch(pycllp_hip_sparse* h, WregPlan* plan, int grid, int a_in_lds = -1, int lds = 0) {
     std::lock_guard<std::mutex> g(h->info_mu);
-    h->last_plan = plan; h->grid = grid;
+    h->last_plan = plan; h->grid = grid; h->last_a_in_lds = a_in_lds; h->last_lds = lds;
 }
 
 // A wave-kernel plan built by its first user (under info_mu; once any call has returned, *plan no longer changes), null when
@@ -932,6 +935,16 @@ int pycllp_hip_dense_variant_info(const pycllp_hip_dense* h, int* a, int* b, int
     if (a) *a = ran ? h->mp : 0;
     if (b) *b = ran ? h->np : 0;
     if (slack) *slack = ran ? h->sl : 0;
+    return 0;
+}
+
+int pycllp_hip_dense_plan_info(const pycllp_hip_dense* h, int* wgpc, int* bnc, int* factor_in_lds, int* a_in_lds) {
+    if (!h) return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_plan_info: bad argument");
+    if (h->sp) return pycllp_hip_sparse_plan_info(h->sp, wgpc, bnc, factor_in_lds, a_in_lds);
+    if (wgpc) *wgpc = 0;
+    if (bnc) *bnc = 0;
+    if (factor_in_lds) *factor_in_lds = -1;
+    if (a_in_lds) *a_in_lds = -1;
     return 0;
 }
 
@@ -1187,7 +1200,8 @@ static int sparse_solve_impl(pycllp_hip_sparse* h, long B, const double* a_batch
         return hipGetLastError();
     });
     if (worklist) { hipError_t e2 = hipFreeAsync(worklist, st); if (e == hipSuccess) e = e2; }
-    record_launch(h, use_wreg ? wplan : nullptr, use_wreg ? grid_w : (int)blocks);
+    if (use_wreg) record_launch(h, wplan, grid_w);
+    else record_launch(h, nullptr, (int)blocks, desc.a_in_lds, lds);
     if (e != hipSuccess) return set_err((int)e, "ipm_block_kernel launch");
     return 0;
 }
@@ -1252,9 +1266,12 @@ int pycllp_hip_sparse_newton(pycllp_hip_sparse* h, long B, const double* x_dev, 
     DevOpts o = to_dev(opts);
     hipStream_t st = (hipStream_t)stream;
     if (h->big) {
+        int grid_b = 0;
         const hipError_t eb = h->ring.run(st, [&](int* qb) {
-            return big_launch_newton(h->big, B, x_dev, z_dev, y_dev, b_dev, c_dev, mu, dy_dev, nrefine_dev, qb, o, h->num_cu, st);
+            return big_launch_newton(h->big, B, x_dev, z_dev, y_dev, b_dev, c_dev, mu, dy_dev, nrefine_dev, qb, o, h->num_cu, st,
+                                     &grid_b);
         });
+        record_launch(h, nullptr, grid_b);
         if (eb != hipSuccess) return set_err((int)eb, "ipm_big_kernel (Newton mode) launch");
         return 0;
     }
@@ -1277,7 +1294,7 @@ int pycllp_hip_sparse_newton(pycllp_hip_sparse* h, long B, const double* x_dev, 
                            (int*)nullptr, qhead, (const int*)nullptr, mu, dy_dev, nrefine_dev, (const double*)nullptr, o);
         return hipGetLastError();
     });
-    record_launch(h, nullptr, (int)blocks);
+    record_launch(h, nullptr, (int)blocks, h->desc.a_in_lds, h->lds);
     if (e != hipSuccess) return set_err((int)e, "ipm_block_kernel (Newton mode) launch");
     return 0;
 }
@@ -1287,7 +1304,7 @@ int pycllp_hip_sparse_launch_info(const pycllp_hip_sparse* h, int* grid, int* bl
     std::lock_guard<std::mutex> g(h->info_mu);
     if (grid) *grid = h->grid;
     if (block) *block = h->last_plan ? wreg_block_threads(h->last_plan) : BLK_T;
-    if (lds_bytes) *lds_bytes = h->last_plan ? wreg_lds_bytes(h->last_plan) : h->lds;
+    if (lds_bytes) *lds_bytes = h->last_plan ? wreg_lds_bytes(h->last_plan) : (h->last_lds ? h->last_lds : h->lds);
     if (kernel) *kernel = h->big ? (big_dense_mode(h->big) ? 4 : 3) : (h->last_plan ? wreg_variant(h->last_plan) : 0);
     return 0;
 }
@@ -1296,6 +1313,14 @@ int pycllp_hip_sparse_variant_info(const pycllp_hip_sparse* h, int* mb, int* nq)
     if (!h) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_variant_info: bad argument");
     std::lock_guard<std::mutex> g(h->info_mu);
     wreg_shape(h->last_plan, mb, nq);
+    return 0;
+}
+
+int pycllp_hip_sparse_plan_info(const pycllp_hip_sparse* h, int* wgpc, int* bnc, int* factor_in_lds, int* a_in_lds) {
+    if (!h) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_plan_info: bad argument");
+    std::lock_guard<std::mutex> g(h->info_mu);
+    big_shape(h->big, wgpc, bnc, factor_in_lds);
+    if (a_in_lds) *a_in_lds = h->last_a_in_lds;
     return 0;
 }
 

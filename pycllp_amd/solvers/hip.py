@@ -198,7 +198,9 @@ class Handle(object):
         """grid / block / LDS bytes of the last launch (dense family: the padded m, n too) and, where one of the kernels of
         ``SPARSE_KERNEL_KINDS`` served it, its ``variant`` and ``kernel``.  The compiled instantiation that served it:
         ``wave_shape`` (MB, NQ) on the wavefront-per-LP kernel, ``group_shape`` (MP, NP) and ``slack`` (1: the slack-aware
-        kernel) on the lane-group kernels."""
+        kernel) on the lane-group kernels, ``big_shape`` (WGPC, BNC) and ``factor_in_lds`` (the factor blocks in LDS, else in the
+        L2 workspace) on the large-LP kernel; ``a_in_lds`` (A's CSR / CSC copy in LDS, else read through L2) where the block
+        kernel served the launch."""
         keys = ("grid", "block", "lds_bytes") + (("m_pad", "n_pad") if self.family == "dense" else ("kernel",))
         vals = [ctypes.c_int() for _ in keys]
         self._call("launch_info", self, *[ctypes.byref(v) for v in vals])
@@ -213,6 +215,13 @@ class Handle(object):
             d["wave_shape"] = (a, b)
         elif a > 0:
             d["group_shape"], d["slack"] = (a, b), shape[2].value
+        plan = [ctypes.c_int() for _ in range(4)]
+        self._call("plan_info", self, *[ctypes.byref(v) for v in plan])
+        wgpc, bnc, factor, a_lds = [v.value for v in plan]
+        if wgpc > 0:
+            d["big_shape"], d["factor_in_lds"] = (wgpc, bnc), bool(factor)
+        if a_lds >= 0:
+            d["a_in_lds"] = bool(a_lds)
         return d
 
     def free(self):

@@ -384,22 +384,26 @@ def assert_matches(s, r, lp):
         assert abs(c @ x - b @ y) <= 1e-7 * (1 + abs(c @ x)), k
 
 
-def run_newton(case):
+def newton_matches(s, lp, B, served):
+    """The stand-alone Newton step of solver ``s`` on B random interior states of ``lp``'s matrix against the oracle's step and
+    the known-answer formula; ``served(launch_info)`` asserts what ran."""
     from oracle import port
-    lp = make_case(case[:2] + ("plain",) + case[3:])
-    s = solver_for(case)
     lp.init(s)
     A = lp.A.todense()
     m, N = A.shape
-    B = batch(m)
     rs = np.random.RandomState(7)
     x, z = 0.5 + rs.rand(B, N), 0.5 + rs.rand(B, N)
     y, b, c = rs.rand(B, m), rs.rand(B, m), rs.rand(B, N)
     dy = s.newton_step(x, z, y, b, c, 1.0)
-    assert_served_by(s.launch_info(), case)
+    served(s.launch_info())
     for i in range(B):
         np.testing.assert_allclose(dy[i], port.solve_primal_normal(A, x[i], z[i], y[i], b[i], c[i], 1.0), rtol=1e-7, atol=1e-9)
         np.testing.assert_allclose(dy[i], port.newton_step_known_answer(A, x[i], z[i], y[i], b[i], c[i], 1.0), rtol=1e-5, atol=1e-5)
+
+
+def run_newton(case):
+    lp = make_case(case[:2] + ("plain",) + case[3:])
+    newton_matches(solver_for(case), lp, batch(lp.nrows), lambda info: assert_served_by(info, case))
 
 
 def run_bounded(case):
