@@ -7,8 +7,9 @@
 //   * N-vectors: NCG = NP/MP registers per lane, column j = gl + MP*q;
 //   * the row-per-lane phases (LDL', forward/back substitution, A*dx) and the column-per-lane phases (A'u, step,
 //     ratio test, norms) are ONE instruction stream serving G LPs;
-//   * the Gram product still uses the whole wave per LP on the matrix cores (v_mfma_f64_16x16x4_f64), groups
-//     taking turns; its operands now come straight from ONE row-major image of A in LDS (odd row stride: the
+//   * the Gram product still uses the whole wave per LP on the matrix cores (v_mfma_f64_16x16x4_f64; 32-row groups:
+//     the diagonal blocks' lower tiles on v_mfma_f64_4x4x4_4b_f64, see gram_pair()), groups taking turns;
+//     its operands now come straight from ONE row-major image of A in LDS (odd row stride: the
 //     row-per-lane reads are conflict free, the MFMA-order reads see a harmless 2-way conflict);
 //   * group reductions use DPP row operations (+ one ds_swizzle for 32-lane groups) instead of ds_bpermute;
 //   * the LDL' column sweep hands the RAW column (pivot included) through LDS, so no cross-lane pivot broadcast
@@ -19,7 +20,7 @@
 // [A | I] (pycllp/lp.py:551-567) -- those columns never enter the dense machinery: their N-vector entries live in
 // the LAST register of every lane (slack i in lane gl = i), A'u is u_i, A v adds v_slack_i to row i and the Gram
 // product only gets d_slack_i added to its diagonal.  The image of A, the k-layout staging and the MFMA loop then
-// cover n - m columns instead of n (48 instead of 72 MFMAs per LP-iteration at (32, 64+32)).
+// cover n - m columns instead of n (16 instead of 24 k-steps per LP-iteration at (32, 64+32)).
 // Semantics are those of oracle/ipm_dense_ref.c (see ipm_dense.hip header); x/z, mu/x and the ratio test use
 // v_rcp_f64 + 2 Newton steps instead of IEEE division (<= 2 ulp).
 
@@ -45,8 +46,38 @@
 #define PYCLLP_FACTOR_PRIO_HSD 3   // ... of the HSD kernel (see GWave::factor_dpp)
 #endif
 #ifndef PYCLLP_WPB
-#define PYCLLP_WPB 8        // waves per workgroup of the group kernel (LDS at (32,96) slack-aware: 8 x 17.5 KB + 16.8 KB)
+#define PYCLLP_WPB 8        // waves per workgroup of the group kernel (LDS at (32,96) slack-aware: 8 x 17.5 KB + 17.5 KB)
 #endif
+
+// Tile schedule of the MP = 32 Gram product's two DIAGONAL 16x16 blocks on v_mfma_f64_4x4x4_4b_f64 (four independent 4x4x4
+// products per instruction).  The 32 rows are 8 row tiles of 4; M = A D A' is symmetric and only its lower triangle is read, so a
+// diagonal 16-block needs 10 of its 16 tiles.  Five instructions cover the 20 tiles exactly once: block b of instruction r
+// multiplies the OWNER tile (its rows scaled by d, the A operand) with the PARTNER tile (plain A, the B operand).  A pair whose
+// partner lies below its owner is the transpose of the wanted lower tile and is stored transposed.  The reference scales the
+// LOWER row of an entry, (a_ik d_k) a_jk with i >= j, and so does the 16x16 form here; a transposed pair scales the upper one
+// (same sum, products rounded differently), so the owner is the lower tile wherever the lane's own tiles allow it: 8 of the 12
+// off-diagonal pairs (all twelve would take a multiply or a select per instruction and k-step, more than the tiles save).
+// (The off-diagonal 16-block has no waste and stays one v_mfma_f64_16x16x4_f64, whose operands are the two loads the lane makes
+// anyway.)
+struct GramPair { int own, par; };
+constexpr int GRAM_INSTS = 5;
+constexpr GramPair gram_pair(int r, int b) {
+    return r == 0 ? GramPair{b, b} : r == 1 ? GramPair{b + 4, b + 4} : r == 2 ? GramPair{b, (b + 3) & 3}
+         : r == 3 ? GramPair{b + 4, 4 + ((b + 3) & 3)} : (b < 2 ? GramPair{b, b + 2} : GramPair{b + 4, b + 2});
+}
+constexpr bool gram_pairs_cover_diagonal_blocks() {
+    int cnt[8][8] = {};
+    for (int r = 0; r < GRAM_INSTS; r++)
+        for (int b = 0; b < 4; b++) {
+            const GramPair t = gram_pair(r, b);
+            cnt[t.own > t.par ? t.own : t.par][t.own > t.par ? t.par : t.own]++;
+        }
+    for (int i = 0; i < 8; i++)
+        for (int j = 0; j < 8; j++)
+            if (cnt[i][j] != ((j <= i && i / 4 == j / 4) ? 1 : 0)) return false;
+    return true;
+}
+static_assert(gram_pairs_cover_diagonal_blocks(), "the five instructions must cover the 20 lower tiles of the diagonal blocks exactly once");
 
 template <int MP, int NP, bool SL = false>
 struct GeoG {
@@ -75,7 +106,30 @@ struct GeoG {
     static constexpr int STAGE = 3 * ND;     // k-layout x, d, d*t of one LP; also reused for G*ND / G*MP vector staging
     static constexpr int STAGE_A = (G * ND > STAGE) ? G * ND : STAGE;
     static constexpr int STAGE_SZ = (2 * G * MP > STAGE_A) ? 2 * G * MP : STAGE_A;   // 2 G MP: the two-vector A'u of the HSD kernel
-    static constexpr int SHARED = AIMG + ND;                   // A image + column sums (A'1)
+    // MP = 32: where lane l of Gram instruction r stores its result, as a byte offset into the LP's slab (swizzle included), one
+    // 16-bit entry per (r, lane).  Operand / result lane map of the instruction (tools/dev/ubench_mfma4.hip): A[i][k] in lane
+    // 16 k + 4 b + i, B[k][j] in lane 16 k + 4 b + j, D[i][j] in lane 16 i + 4 b + j.  A per-workgroup LDS table: derived from the
+    // lane bits in every call the offsets cost several integer instructions each, read from here a load and an add.
+    __host__ __device__ static constexpr int gram_store(int r, int lane) {
+        const GramPair t = gram_pair(r, (lane >> 2) & 3);
+        const int ro = 4 * t.own + (lane >> 4), rp = 4 * t.par + (lane & 3);
+        return 8 * (t.par > t.own ? sidx(rp, ro) : sidx(ro, rp));
+    }
+    // Row GRAM_INSTS of the table: byte offset into the A image of the lane's row of partner tile (b + 3) % 4, which wraps for
+    // b = 0 (the same row of tile 4 + (b + 3) % 4 is 16 rows below: an immediate).
+    __host__ __device__ static constexpr int gram_wrap(int lane) { return 8 * AS * (((lane & 15) + 12) & 15); }
+    static constexpr int GROWS = GRAM_INSTS + 1;
+    static constexpr int GTAB = (MP == 32) ? GROWS * 64 / 4 : 0;   // doubles
+    static constexpr int GTAB_OFF = AIMG + ND;                     // behind the A image and the column sums
+    // (every kernel fills it next to the A image; the workgroup barrier that publishes the image publishes the table)
+    __device__ static void fill_gram_table(double* lds, int tid, int nthreads) {
+        if constexpr (MP == 32) {
+            unsigned short* tab = (unsigned short*)(lds + GTAB_OFF);
+            for (int i = tid; i < GROWS * 64; i += nthreads)
+                tab[i] = (unsigned short)(i < GRAM_INSTS * 64 ? gram_store(i >> 6, i & 63) : gram_wrap(i & 63));
+        }
+    }
+    static constexpr int SHARED = GTAB_OFF + GTAB;            // A image + column sums (A'1) + Gram store offsets
     static constexpr int WSZ = G * SLAB + STAGE_SZ;            // per-wave doubles
     static constexpr size_t lds_bytes(int wpb) { return sizeof(double) * (size_t)(SHARED + wpb * WSZ); }
     __host__ __device__ static constexpr int kpos(int j) { return (j & 3) * KS + (j >> 2); }
@@ -253,75 +307,104 @@ struct GWave {
 
     // Gram product of group g's LP on the matrix cores (whole wave), fused with A*x (AX) and A*(d.t).
     // stage holds that LP's x, d, d*t in k-layout.  M goes to group g's slab; Ax/Adt come back for rows (l & 15) + 16 J.
-    template <bool AX = true>
+    // LATE: the store offsets are read after the k-loop instead of before it (their latency is then exposed, but they are not live
+    // across the loop: the bounded kernel, which has no registers to spare there, spilt four without it).
+    template <bool AX = true, bool LATE = false>
     __device__ __forceinline__ void gram_one(int g, double (&axp)[JB], double (&adp)[JB]) const {
         int lo0_ = lane;                      // opaque copy: see ogl()
         asm volatile("" : "+v"(lo0_));
         const int kg = lo0_ >> 4, cc = lo0_ & 15;
-        double4_t acc[JB][JB];
 #pragma unroll
-        for (int I = 0; I < JB; I++) {
-            axp[I] = 0.0; adp[I] = 0.0;
-#pragma unroll
-            for (int J = 0; J < JB; J++) acc[I][J] = (double4_t){0.0, 0.0, 0.0, 0.0};
-        }
+        for (int I = 0; I < JB; I++) { axp[I] = 0.0; adp[I] = 0.0; }
         const double* px = stage + kg * KS;
         const double* pd = stage + ND + kg * KS;
         const double* pt = stage + 2 * ND + kg * KS;
         const double* arow = Aimg + cc * AS + kg;
-        constexpr int SC = (KS % 4 == 0) ? 4 : 2;
-#pragma unroll PYCLLP_GRAM_UNROLL
-        for (int s0 = 0; s0 < KS; s0 += SC) {
-#pragma unroll
-            for (int ss = 0; ss < SC; ss++) {
-                const int s = s0 + ss;
-                const double xk = AX ? px[s] : 0.0, dk = pd[s], tk = pt[s];
-                double a[JB], ad[JB];
-#pragma unroll
-                for (int J = 0; J < JB; J++) {
-                    a[J] = arow[16 * J * AS + 4 * s];      // A[16J + (l&15)][4s + (l>>4)]
-                    if (AX) axp[J] = fma(a[J], xk, axp[J]);
-                    adp[J] = fma(a[J], tk, adp[J]);
-                    ad[J] = a[J] * dk;
-                }
-#pragma unroll
-                for (int I = 0; I < JB; I++)
-#pragma unroll
-                    for (int J = 0; J <= I; J++)
-                        acc[I][J] = __builtin_amdgcn_mfma_f64_16x16x4f64(ad[I], a[J], acc[I][J], 0, 0, 0);
-            }
-        }
         double* sg = slab0 + g * G_::SLAB;
-        int lo_ = lane;                       // opaque copy: see ogl()
-        asm volatile("" : "+v"(lo_));
-        const int kg2 = lo_ >> 4, cc2 = lo_ & 15;
-        // Only the LOWER block triangle (I >= J) is stored: everything that reads the raw matrix -- load_own_row for the
-        // register-resident LDL', the guarded cold path, the diagonal -- uses entries (row, col <= row) only (round 3: the mirror
-        // of the off-diagonal blocks, which the round-1 factorisation through LDS read as broadcast rows, is gone).
-        if constexpr (G_::SWZ) {
-            // entry (16 I + kg + 4 r, 16 J + cc): (row & 15) << 1 = 2 kg + 8 r, so the swizzled column is
-            // 16 (J ^ (r >> 1)) + ((cc ^ 2 kg) ^ 8 (r & 1)): TWO lane-dependent bases and an immediate per store, where the generic
-            // sidx() costs five integer operations per store (75 per Gram product, 150 per wave-iteration)
-            const int c0 = cc2 ^ (kg2 << 1);
+        constexpr int SC = (KS % 4 == 0) ? 4 : 2;
+        // Only the LOWER triangle is needed: everything that reads the raw matrix -- load_own_row for the register-resident LDL',
+        // the guarded cold path, the diagonal -- uses entries (row, col <= row) only.
+        if constexpr (MP == 32) {
+            // The off-diagonal 16x16 block on one v_mfma_f64_16x16x4_f64 and the two diagonal blocks' lower tiles on five 4x4x4
+            // instructions (gram_pair()): 256 + 320 = 576 entries computed for the 528 needed, where three 16x16 tiles computed
+            // 768.  The lane's operand element of row tile t is A[4 t + (l & 3)][4 s + (l >> 4)]: its own tiles
+            // b = (l >> 2) & 3 and b + 4 are the two loads the fused A x / A (d t) sums and the 16x16 block take anyway; tile b + 2 sits
+            // 8 rows below (an immediate), tiles (b + 3) % 4 and 4 + (b + 3) % 4 wrap for b = 0 and get an address of their own
+            // (GeoG::gram_wrap).  Three more reads per k-step, not the six of an all-4x4 schedule: the LDS pipe, 44 % busy before,
+            // is what that schedule's gain drowned in (profiles/r04).
+            const unsigned short* tab = (const unsigned short*)(Aimg + G_::GTAB_OFF) + lo0_;
+            const __attribute__((address_space(3))) double* wrow =
+                (const __attribute__((address_space(3))) double*)(size_t)(lds_addr(Aimg + kg) + tab[64 * GRAM_INSTS]);
+            unsigned so[GRAM_INSTS];
+            if constexpr (!LATE) {
+#pragma unroll
+                for (int r = 0; r < GRAM_INSTS; r++) so[r] = tab[64 * r];
+            }
+            const bool top = cc < 8;              // instruction 4: blocks 0, 1 own tile b, blocks 2, 3 own tile b + 4
+            double4_t acc10 = (double4_t){0.0, 0.0, 0.0, 0.0};
+            double acc[GRAM_INSTS];
+#pragma unroll
+            for (int r = 0; r < GRAM_INSTS; r++) acc[r] = 0.0;
+#pragma unroll PYCLLP_GRAM_UNROLL
+            for (int s0 = 0; s0 < KS; s0 += SC) {
+#pragma unroll
+                for (int ss = 0; ss < SC; ss++) {
+                    const int s = s0 + ss;
+                    const double xk = AX ? px[s] : 0.0, dk = pd[s], tk = pt[s];
+                    double a[2], ad[2];
+#pragma unroll
+                    for (int J = 0; J < 2; J++) {
+                        a[J] = arow[16 * J * AS + 4 * s];      // A[16J + (l&15)][4s + (l>>4)]
+                        if (AX) axp[J] = fma(a[J], xk, axp[J]);
+                        adp[J] = fma(a[J], tk, adp[J]);
+                        ad[J] = a[J] * dk;
+                    }
+                    const double p3 = wrow[4 * s], p7 = wrow[16 * AS + 4 * s], p2 = arow[8 * AS + 4 * s];
+                    acc10 = __builtin_amdgcn_mfma_f64_16x16x4f64(ad[1], a[0], acc10, 0, 0, 0);
+                    acc[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad[0], a[0], acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad[1], a[1], acc[1], 0, 0, 0);
+                    acc[2] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad[0], p3, acc[2], 0, 0, 0);
+                    acc[3] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad[1], p7, acc[3], 0, 0, 0);
+                    acc[4] = __builtin_amdgcn_mfma_f64_4x4x4f64(top ? ad[0] : ad[1], p2, acc[4], 0, 0, 0);
+                }
+            }
+            int lo_ = lane;                       // opaque copy: see ogl()
+            asm volatile("" : "+v"(lo_));
+            if constexpr (LATE) {
+                const unsigned short* tab2 = (const unsigned short*)(Aimg + G_::GTAB_OFF) + lo_;
+#pragma unroll
+                for (int r = 0; r < GRAM_INSTS; r++) so[r] = tab2[64 * r];
+            }
+            const unsigned sga = lds_addr(sg);
+#pragma unroll
+            for (int r = 0; r < GRAM_INSTS; r++) *(__attribute__((address_space(3))) double*)(size_t)(sga + so[r]) = acc[r];
+            // the 16x16 block, entry (16 + kg + 4 r, cc): (row & 15) << 1 = 2 kg + 8 r, so the swizzled column is
+            // 16 (r >> 1) + ((cc ^ 2 kg) ^ 8 (r & 1)): TWO lane-dependent bases and an immediate per store
+            const int kg2 = lo_ >> 4, c0 = (lo_ & 15) ^ (kg2 << 1);
             double* e0 = sg + kg2 * G_::MS + c0;
             double* e1 = sg + kg2 * G_::MS + (c0 ^ 8);
 #pragma unroll
-            for (int I = 0; I < JB; I++)
-#pragma unroll
-                for (int J = 0; J <= I; J++)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; r4++)
-                        ((r4 & 1) ? e1 : e0)[(16 * I + 4 * r4) * G_::MS + 16 * (J ^ (r4 >> 1))] = acc[I][J][r4];
+            for (int r4 = 0; r4 < 4; r4++) ((r4 & 1) ? e1 : e0)[(16 + 4 * r4) * G_::MS + 16 * (r4 >> 1)] = acc10[r4];
         } else {
+            // one 16x16 tile (both triangles) on v_mfma_f64_16x16x4_f64
+            double4_t acc = (double4_t){0.0, 0.0, 0.0, 0.0};
+#pragma unroll PYCLLP_GRAM_UNROLL
+            for (int s0 = 0; s0 < KS; s0 += SC) {
 #pragma unroll
-            for (int I = 0; I < JB; I++)
+                for (int ss = 0; ss < SC; ss++) {
+                    const int s = s0 + ss;
+                    const double xk = AX ? px[s] : 0.0, dk = pd[s], tk = pt[s];
+                    const double a = arow[4 * s];          // A[l & 15][4s + (l >> 4)]
+                    if (AX) axp[0] = fma(a, xk, axp[0]);
+                    adp[0] = fma(a, tk, adp[0]);
+                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a * dk, a, acc, 0, 0, 0);
+                }
+            }
+            int lo_ = lane;                       // opaque copy: see ogl()
+            asm volatile("" : "+v"(lo_));
+            const int kg2 = lo_ >> 4, cc2 = lo_ & 15;
 #pragma unroll
-                for (int J = 0; J <= I; J++)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; r4++) {
-                        const int row = 16 * I + kg2 + 4 * r4, col = 16 * J + cc2;
-                        sg[G_::sidx(row, col)] = acc[I][J][r4];
-                    }
+            for (int r4 = 0; r4 < 4; r4++) sg[G_::sidx(kg2 + 4 * r4, cc2)] = acc[r4];
         }
 #pragma unroll
         for (int J = 0; J < JB; J++) {
@@ -529,6 +612,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         const int r = i / AS, cidx = i % AS;
         Aimg[i] = (r < m && cidx < nd) ? Ag[(size_t)r * n + cidx] : 0.0;
     }
+    G_::fill_gram_table(lds, tid, blockDim.x);
     __syncthreads();
     for (int j = tid; j < ND; j += blockDim.x) {
         double sacc = 0.0;

@@ -37,6 +37,7 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
         const int r = i / AS, cidx = i % AS;
         Aimg[i] = (r < m && cidx < nd) ? Ag[(size_t)r * n + cidx] : 0.0;
     }
+    G_::fill_gram_table(lds, tid, blockDim.x);
     __syncthreads();
     for (int j = tid; j < ND; j += blockDim.x) {
         double sacc = 0.0;
@@ -238,7 +239,7 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
                 }
                 wave_lds_sync();
                 double axp[JB], adp[JB];
-                w.template gram_one<true>(g, axp, adp);
+                w.template gram_one<true, true>(g, axp, adp);
                 wave_lds_sync();
                 if (grp == g) {
                     Ax_ = (JB == 1) ? axp[0] : ((gl >> 4) ? axp[JB - 1] : axp[0]);

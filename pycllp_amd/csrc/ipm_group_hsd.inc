@@ -142,6 +142,7 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         const int r = i / AS, cidx = i % AS;
         Aimg[i] = (r < m && cidx < nd) ? Ag[(size_t)r * n + cidx] : 0.0;
     }
+    G_::fill_gram_table(lds, tid, blockDim.x);
     __syncthreads();
 
     GWaveH<MP, NP, SL> w;
