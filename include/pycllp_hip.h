@@ -122,7 +122,10 @@ int pycllp_hip_dense_init(int m, int n, const double *A_dev, void *stream, pycll
 
 /* Solve B LPs.  Inputs b_dev [B,m], c_dev [B,n].  Outputs (any of y/z/pobj/dobj/iters may be NULL):
  *   x_dev [B,n], y_dev [B,m], z_dev [B,n]  primal, dual and dual-slack solutions
- *   pobj_dev, dobj_dev [B]                 c'x and b'y at exit (objective offset f NOT added)
+ *   pobj_dev, dobj_dev [B]                 c'x and b'y at exit (objective offset f NOT added).  An LP that ends at the
+ *                                          iteration limit (status 5) returns the x, y, z of its last step and the objectives
+ *                                          of the point that step started from (with PYCLLP_FLAG_HSD: divided by the final
+ *                                          tau), as the reference's loop leaves them (pycllp/cl/primal_normal.cl:245-248)
  *   status_dev [B] i32, iters_dev [B] i32  status code and IPM iterations used
  * Asynchronous on `stream`. */
 int pycllp_hip_dense_solve(pycllp_hip_dense *handle, long B, const double *b_dev, const double *c_dev,
@@ -135,7 +138,8 @@ int pycllp_hip_dense_solve(pycllp_hip_dense *handle, long B, const double *b_dev
  * [A_dense | I_m] with m <= 32 and at most 96 dense columns (the slack-aware kernels of pycllp_hip_dense_solve).
  *   u_dev [B,n]      upper bounds: +inf = no bound, 0 = the column is fixed at 0 (it ends at x = 0)
  *   s_dev [B,n]      (optional) duals of x <= u; z_dev (optional) those of x >= 0: A'y - z + s = c
- *   dobj_dev [B]     b'y + u's over the finite u; the other arguments as pycllp_hip_dense_solve
+ *   dobj_dev [B]     b'y + u's over the finite u; the other arguments as pycllp_hip_dense_solve, except that at the iteration
+ *                    limit pobj and dobj are those of the x, y, s returned (likewise pycllp_hip_sparse_solve_bounded)
  * Options: PYCLLP_FLAG_AUTOSCALE (u scales with b) and PYCLLP_FLAG_FORCE_GUARD_PATH apply.
  * Returns PYCLLP_E_BADARG for a NULL u_dev or any of the flags HSD, PREDCORR, WARM_START, WAVE_KERNEL, NO_SLACK_PATH, and
  * PYCLLP_E_UNSUPPORTED when the handle has no slack-aware lane-group kernel; both before any HIP call.

@@ -185,9 +185,22 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
                 }
             }
             if (yg && rowok) yg[lp * m + go] = y * sc;
+            // the iteration limit is met after a step, and po, du above belong to the point before it: the objectives stored are
+            // those of the point stored (as ipm_wreg_bounded_kernel and the twin store them)
+            double pof = po, duf = du;
+            if (stat_ == PYCLLP_STATUS_ITERATION_LIMIT) {
+                double pp2 = 0.0, dd2 = b * y;
+#pragma unroll
+                for (int q = 0; q < NCG; q++) {
+                    pp2 += act(q) ? c[q] * x[q] : 0.0;
+                    dd2 += bnd(q) ? u[q] * s[q] : 0.0;
+                }
+                pof = grp_sum<MP>(pp2);
+                duf = grp_sum<MP>(dd2);
+            }
             if (go == 0) {
-                if (pobj) pobj[lp] = po * (sb * sc);
-                if (dobj) dobj[lp] = du * (sb * sc);
+                if (pobj) pobj[lp] = pof * (sb * sc);
+                if (dobj) dobj[lp] = duf * (sb * sc);
                 status[lp] = stat_;
                 if (iters) iters[lp] = it;
             }

@@ -188,6 +188,7 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
     // paths that need it (loading / storing an LP) must not leave per-lane addresses alive across the iterations
     auto gcol = [&](int q, int g_) { return (q < NCD) ? g_ + MP * q : nd + g_; };
     double b = 0.0, y = 0.0, tau = 1.0, kap = 1.0, nb = 0.0, nc = 0.0;
+    double po_prev = 0.0, du_prev = 0.0;      // c'x and b'y of the point the last step started from
     int it = 0;
 
     while (__any(live)) {
@@ -293,9 +294,12 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 }
             }
             if (yg && rowok) yg[lp * m + go] = y * rt * sc;
+            // at the iteration limit: the objectives of the point the last step started from, over the tau it ended on -- what the
+            // oracle (hsd_one_raw) and the other kernels of this variant return there
+            const bool lim = stat_ == PYCLLP_STATUS_ITERATION_LIMIT && it > 0;
             if (go == 0) {
-                if (pobj) pobj[lp] = po * rt * (sb * sc);
-                if (dobj) dobj[lp] = du * rt * (sb * sc);
+                if (pobj) pobj[lp] = (lim ? po_prev : po) * rt * (sb * sc);
+                if (dobj) dobj[lp] = (lim ? du_prev : du) * rt * (sb * sc);
                 status[lp] = stat_;
                 if (iters) iters[lp] = it;
             }
@@ -339,6 +343,7 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
 
         const double mu = (gam + tau * kap) / (double)(iopaque(n) + 1), dmu = o.delta * mu;
         const double phi = du - po + kap;
+        po_prev = po; du_prev = du;
 
         // ---- Gram product, fused with A(d c) and A(d r1) ----
         double Adc = 0.0, Adr = 0.0;

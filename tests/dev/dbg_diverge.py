@@ -1,5 +1,7 @@
-"""Where do kernel and oracle part ways on the two diverging 1x2 LPs of test_infeasible_and_unbounded_status_codes_match_oracle?
-Runs both with max_iter = k for growing k and prints the first k at which x, y or z differ by more than 1e-9 relative."""
+"""Where do kernel and oracle part ways on the two diverging 1x2 LPs of
+tests/test_hip_parity.py::test_infeasible_and_unbounded_lps_reference_path_and_default?  Runs both with max_iter = k for growing k
+and prints, per k, the relative difference of x, y and z.  The scratch form of that test's trajectory comparison; every kernel
+family is held to the oracle after k iterations by tests/test_trajectory_parity.py (figures: tests/dev/trajectory_report.py)."""
 import sys, os, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from pycllp_amd.lp import SparseMatrix, EqualityLP
