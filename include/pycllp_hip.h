@@ -149,6 +149,25 @@ int pycllp_hip_dense_solve_bounded(pycllp_hip_dense *handle, long B, const doubl
                                    double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
                                    const pycllp_hip_opts *opts, void *stream);
 
+/* Solve B LPs that each have their OWN dense matrix, on the lane-group kernel for per-problem A (every lane group keeps the
+ * image of its LP's matrix in LDS and refills it from A_dev when it takes its next LP).  The handle comes from
+ * pycllp_hip_dense_init with any one matrix of the batch: that matrix fixes m, n and whether the last m columns are the
+ * identity (as the handle of pycllp_hip_sparse_solve_batch fixes the structure); its values are not read here.
+ *   A_dev [B, m, a_cols]  row-major.  a_cols = n - m on a handle whose tail is the identity (the tail is implied and not
+ *                         stored), a_cols = n otherwise -- and with PYCLLP_FLAG_NO_SLACK_PATH on such a handle, where the
+ *                         caller passes the full [m, n] matrices, identity included
+ * The other arguments, the status codes and the outputs as pycllp_hip_dense_solve, except that at the iteration limit pobj
+ * and dobj are those of the x, y returned (as pycllp_hip_dense_solve_bounded).
+ * Options: PYCLLP_FLAG_AUTOSCALE, PYCLLP_FLAG_FORCE_GUARD_PATH and PYCLLP_FLAG_NO_SLACK_PATH apply.
+ * Returns PYCLLP_E_BADARG for any of the flags HSD, PREDCORR, WARM_START, WAVE_KERNEL or an a_cols other than the above, and
+ * PYCLLP_E_UNSUPPORTED for a handle beyond the lane-group kernels (m > 32 or n > 128: use pycllp_hip_sparse_solve_batch);
+ * all before any HIP call.  Uses the handle's launch-queue ring; pycllp_hip_dense_launch_info / _variant_info report the
+ * launch as they do for the other lane-group kernels.  Asynchronous on `stream`. */
+int pycllp_hip_dense_solve_batch(pycllp_hip_dense *handle, long B, const double *A_dev, long a_cols,
+                                 const double *b_dev, const double *c_dev, double *x_dev, double *y_dev, double *z_dev,
+                                 double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
+                                 const pycllp_hip_opts *opts, void *stream);
+
 /* One Newton step of the primal normal equations for B independent states:
  *   dy <- solve( A diag(x/z) A' , -(b - A x - A diag(x/z) (c - A'y + mu/x)) )
  * x,z,c [B,n]; y,b,dy [B,m].  nrefine_dev [B] (optional) receives the refinement passes used. */

@@ -399,6 +399,7 @@ newton_kernel(int m, int n, long B, const double* __restrict__ pack, const doubl
 #include "ipm_group.inc"
 #include "ipm_group_hsd.inc"
 #include "ipm_group_bounded.inc"
+#include "group_pa.h"
 #include "ldl_batched.inc"
 #include "ipm_block.inc"
 
@@ -567,6 +568,28 @@ static LaunchPlan plan_group(const pycllp_hip_dense* h, long B, int wpb, const D
     return LaunchPlan{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP, SL ? 1 : 0};
 }
 
+// Launch plan of the lane-group kernel for per-problem dense A (ipm_group_perA.inc, compiled in ipm_group_pa.hip): nothing is
+// shared between waves there, every wave needs GeoPA::PW doubles (its G matrix areas + GeoG::WSZ), and one workgroup per CU
+// holds as many waves as the LDS takes -- at most GeoPA::WPB_MAX, what the kernel's launch bounds allow.  The small-batch rule
+// is plan_group's.
+template <int MP, int NP, bool SL>
+static LaunchPlan plan_group_pa(const pycllp_hip_dense* h, long B, const DevOpts& o) {
+    using P = GeoPA<GeoG<MP, NP, SL>>;
+    int wpb = P::WPB_MAX;
+    while (wpb > 1 && P::lds_bytes(wpb) > (size_t)h->max_lds) wpb--;
+    const long resident = (long)h->num_cu - o.reserve_cus > 0 ? (long)h->num_cu - o.reserve_cus : 1;
+    {
+        const long per_cu = (B + resident - 1) / resident;                               // LPs per CU
+        long want = (per_cu <= 4 * (long)P::G) ? (per_cu < 4 ? per_cu : 4) : (per_cu + P::G - 1) / P::G;
+        if (want < 1) want = 1;
+        if (want < wpb) wpb = (int)want;
+    }
+    long blocks = (B + wpb - 1) / wpb;
+    if (blocks > resident) blocks = resident;
+    if (blocks < 1) blocks = 1;
+    return LaunchPlan{(int)blocks, wpb * WAVE, (int)P::lds_bytes(wpb), MP, NP, SL ? 1 : 0};
+}
+
 // Sets the kernel's LDS, runs launch(qhead) on a queue-ring slot and publishes the plan for launch_info
 template <typename Launch>
 static hipError_t run_group(pycllp_hip_dense* h, const void* kernel, const LaunchPlan& p, hipStream_t st, Launch&& launch) {
@@ -652,6 +675,13 @@ static const Variant kVariants[] = { GROUP_SHAPES(VARIANT) };
 static const int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 static const SlackVariant kSlackVariants[] = { GROUP_SHAPES(SLACK_VARIANT) };
 static const int kNumSlackVariants = sizeof(kSlackVariants) / sizeof(kSlackVariants[0]);
+
+// launch plans of the kernel for per-problem dense A; its launchers are kGroupPA's (group_pa.h), matched by (mp, np, sl)
+typedef LaunchPlan (*pa_plan_fn)(const pycllp_hip_dense*, long, const DevOpts&);
+struct PaPlan { int mp, np, sl; pa_plan_fn plan; };
+#define PA_PLAN(MP, NP) { MP, NP, 0, plan_group_pa<MP, NP, false> }, { MP, NP, 1, plan_group_pa<MP, NP, true> },
+static const PaPlan kPaPlans[] = { GROUP_SHAPES(PA_PLAN) };
+static const int kNumPaPlans = sizeof(kPaPlans) / sizeof(kPaPlans[0]);
 
 static unsigned long long* g_prof = nullptr;  // diagnostic build only
 #ifdef PYCLLP_PROFILE
@@ -887,6 +917,49 @@ int pycllp_hip_dense_solve_bounded(pycllp_hip_dense* h, long B, const double* b_
     hipError_t e = kSlackVariants[h->variant_sl].solve_bounded(h, B, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev,
                                                                dobj_dev, status_dev, iters_dev, o, (hipStream_t)stream);
     if (e != hipSuccess) return set_err((int)e, "bounded solve kernel launch");
+    return 0;
+}
+
+int pycllp_hip_dense_solve_batch(pycllp_hip_dense* h, long B, const double* A_dev, long a_cols, const double* b_dev,
+                                 const double* c_dev, double* x_dev, double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev,
+                                 int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
+    // the flag and pointer checks come before the handle is read, every check before any HIP call
+    if (!h || B < 0) return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch: bad argument");
+    const int flags = opts ? opts->flags : 0;
+    if (flags & (PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL))
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch: HSD, PREDCORR, WARM_START and WAVE_KERNEL are not available "
+                                        "with per-problem matrices");
+    if (B > 0 && (!A_dev || !b_dev || !c_dev || !x_dev || !status_dev))
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch: bad argument");
+    if (h->sp)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch: per-problem dense matrices stop at m = 32, n = 128 "
+                                             "(beyond: pycllp_hip_sparse_solve_batch)");
+    const bool sl = h->variant_sl >= 0 && !(flags & PYCLLP_FLAG_NO_SLACK_PATH);
+    if (a_cols != (long)(sl ? h->n - h->m : h->n)) {
+        snprintf(g_err, sizeof(g_err), "pycllp_hip_dense_solve_batch: a_cols = %ld, expected %d (%s)", a_cols,
+                 sl ? h->n - h->m : h->n, sl ? "the columns before the identity tail" : "every column");
+        return PYCLLP_E_BADARG;
+    }
+    const int mp = sl ? kSlackVariants[h->variant_sl].mp : kVariants[h->variant].mp;
+    const int np = sl ? kSlackVariants[h->variant_sl].np : kVariants[h->variant].np;
+    const PaPlan* pp = nullptr;
+    const GroupPaVariant* pv = nullptr;
+    for (int i = 0; i < kNumPaPlans; i++)
+        if (kPaPlans[i].mp == mp && kPaPlans[i].np == np && kPaPlans[i].sl == (sl ? 1 : 0)) pp = &kPaPlans[i];
+    for (int i = 0; i < kGroupPA.n; i++)
+        if (kGroupPA.v[i].mp == mp && kGroupPA.v[i].np == np && kGroupPA.v[i].sl == (sl ? 1 : 0)) pv = &kGroupPA.v[i];
+    if (!pp || !pv) return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch: no kernel of this shape was compiled");
+    if (B == 0) return 0;
+    DevOpts o = to_dev(opts);
+    hipStream_t st = (hipStream_t)stream;
+    const LaunchPlan p = pp->plan(h, B, o);
+    const hipError_t e = h->ring.run(st, [&](int* qhead) {
+        const GroupPaArgs a = {h->m, h->n, B, A_dev, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, qhead};
+        const hipError_t el = pv->launch(a, p.grid, p.block, p.lds, o, st);
+        publish(h, p);
+        return el;
+    });
+    if (e != hipSuccess) return set_err((int)e, "per-problem solve kernel launch");
     return 0;
 }
 
