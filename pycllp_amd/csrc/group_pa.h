@@ -1,5 +1,5 @@
 // group_pa.h -- internal interface between ipm_dense.hip (C ABI, handles, launch plans) and ipm_group_pa.hip, the translation
-// unit of the lane-group kernel for per-problem dense A (ipm_group_perA.inc).  Not part of the public ABI.
+// unit of the lane-group kernel for per-problem dense A (ipm_group_slot.inc).  Not part of the public ABI.
 #ifndef PYCLLP_GROUP_PA_H
 #define PYCLLP_GROUP_PA_H
 #include "wave_common.h"

@@ -398,7 +398,7 @@ newton_kernel(int m, int n, long B, const double* __restrict__ pack, const doubl
 
 #include "ipm_group.inc"
 #include "ipm_group_hsd.inc"
-#include "ipm_group_bounded.inc"
+#include "ipm_group_slot.inc"
 #include "group_pa.h"
 #include "ldl_batched.inc"
 #include "ipm_block.inc"
@@ -568,7 +568,7 @@ static LaunchPlan plan_group(const pycllp_hip_dense* h, long B, int wpb, const D
     return LaunchPlan{(int)blocks, wpb * WAVE, (int)G::lds_bytes(wpb), MP, NP, SL ? 1 : 0};
 }
 
-// Launch plan of the lane-group kernel for per-problem dense A (ipm_group_perA.inc, compiled in ipm_group_pa.hip): nothing is
+// Launch plan of the lane-group kernel for per-problem dense A (ipm_group_slot.inc, compiled in ipm_group_pa.hip): nothing is
 // shared between waves there, every wave needs GeoPA::PW doubles (its G matrix areas + GeoG::WSZ), and one workgroup per CU
 // holds as many waves as the LDS takes -- at most GeoPA::WPB_MAX, what the kernel's launch bounds allow.  The small-batch rule
 // is plan_group's.
@@ -618,7 +618,7 @@ static hipError_t launch_solve_group(pycllp_hip_dense* h, long B, const double* 
 typedef hipError_t (*bounded_launch_fn)(pycllp_hip_dense*, long, const double*, const double*, const double*, double*, double*,
                                         double*, double*, double*, double*, int*, int*, DevOpts, hipStream_t);
 
-// the bounded slack-aware kernel (ipm_group_bounded.inc): the plan of launch_solve_group with PYCLLP_WPB_BOUNDED waves per workgroup
+// the bounded slack-aware kernel (ipm_group_slot.inc): the plan of launch_solve_group with PYCLLP_WPB_BOUNDED waves per workgroup
 template <int MP, int NP>
 static hipError_t launch_solve_bounded(pycllp_hip_dense* h, long B, const double* b, const double* c, const double* u, double* x,
                                        double* y, double* z, double* s, double* pobj, double* dobj, int* status, int* iters,

@@ -1,10 +1,10 @@
-// ipm_group_pa.hip -- translation unit of ipm_group_pa_kernel (ipm_group_perA.inc): the lane-group kernel for batches of LPs
+// ipm_group_pa.hip -- translation unit of ipm_group_pa_kernel (ipm_group_slot.inc): the lane-group kernel for batches of LPs
 // with per-problem dense A.  A unit of its own (as ipm_wreg_bd.o is for the bounded wave kernel), so that the code objects of
 // every other kernel of the library are what they were before this kernel existed.  ipm_dense.hip owns the handle, the launch
 // plan and the C ABI (pycllp_hip_dense_solve_batch) and reaches the kernels through kGroupPA (group_pa.h).
 #include "group_pa.h"
 #include "ipm_group.inc"
-#include "ipm_group_perA.inc"
+#include "ipm_group_slot.inc"
 
 template <int MP, int NP, bool SL>
 static hipError_t launch_group_pa(const GroupPaArgs& a, int grid, int block, int lds, DevOpts o, hipStream_t st) {

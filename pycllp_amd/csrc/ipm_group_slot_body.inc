@@ -1,64 +1,53 @@
-// ipm_group_bounded.inc -- the slack-aware lane-group kernel (ipm_group.inc, SL = true) for LPs with UPPER BOUNDS:
-//   maximise c'x  subject to  A x = b,  0 <= x <= u        (u_j = +inf: no bound;  u_j = 0: the column is fixed at 0)
-// the bounded equality form of a GeneralLP (pycllp_amd/lp.py, GeneralLP.to_bounded_equality_form), A = [A_dense | I].
-// Primal-normal step with x + t = u, t >= 0 and the dual Aty - z + s = c, s >= 0 (DESIGN.md section 14):
-//   d = 1 / (z/x + s/t),  t~ = c - A'y + mu/x - mu/t + (s/t) tau,  tau = u - x - t,  mu = delta gamma / (n + m + N_b)
-//   M dy = A (d t~) - rho,  dx = d (t~ - A'dy),  dz = (mu - z dx)/x - z,  dt = tau - dx,  ds = (mu - s dt)/t - s
-// A column without a bound carries no t, s: every formula is then the one of ipm_group_kernel.  A fixed column (u = 0) takes
-// no part in the iteration: it ends at x = 0 with the duals z = max(A'y - c, 0), s = max(c - A'y, 0).
-// Only the per-column phases differ from ipm_group_kernel; the Gram product, the LDL' (both paths), the substitution and
-// the refinement are the GWave<MP, NP, true> members, unchanged.  Simplifications against the plain kernel: rho = b - A x comes
-// from the Gram pass every iteration (no carried residual), so the stop test of a point runs after its Gram product and a slot
-// that finishes idles through the rest of that pass; no warm start, no predictor-corrector.
-// Registers: seven N-vectors per slot (x, z, t, s, u, c, A'y) and four kept reciprocals instead of four and two; at (32, 96)
-// that does not fit 256 registers, so the kernel runs PYCLLP_WPB_BOUNDED = 4 waves per workgroup, one per SIMD, with the
-// whole 512-register file per lane (DESIGN.md section 14 has the measured cost).
-
-#ifndef PYCLLP_WPB_BOUNDED
-#define PYCLLP_WPB_BOUNDED 4
-#endif
-
-template <int MP, int NP>
-__global__ void __launch_bounds__(PYCLLP_WPB_BOUNDED * 64)
-ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const double* __restrict__ bg,
-                   const double* __restrict__ cg, const double* __restrict__ ug, double* __restrict__ xg,
-                   double* __restrict__ yg, double* __restrict__ zg, double* __restrict__ sg, double* __restrict__ pobj,
-                   double* __restrict__ dobj, int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue,
-                   DevOpts o) {
-    using G_ = GeoG<MP, NP, true>;
+// ipm_group_slot_body.inc -- the text of one slot iteration, included into the body of ipm_bounded_kernel and of
+// ipm_group_pa_kernel (ipm_group_slot.inc, which has the algorithm notes).  It expects in scope: MP, NP and the constants SL,
+// BD (upper bounds: t, s, u), PA (per-slot A areas); the kernel arguments m, n, B, Ag, bg, cg, ug, xg, yg, zg, sg, pobj, dobj,
+// status, iters, queue, o (ug, sg: BD only).  Each phase is written once, in the form of the bounded algorithm (DESIGN.md
+// section 14); strike the BD parts and the plain step of ipm_group_kernel is left.
+    using G_ = GeoG<MP, NP, SL>;
+    using P_ = GeoPA<G_>;
     constexpr int G = G_::G, NCG = G_::NCG, NCD = G_::NCD, ND = G_::ND, JB = G_::JB, AS = G_::AS;
-    const int nd = n - m;                   // dense columns of A (the last m columns are the identity)
+    static_assert(SL || !BD, "the bounded equality form ends in the identity");
+    const int nd = SL ? n - m : n;          // dense columns of A as stored (the last m columns of the LP are the identity when SL)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
     const int wpb = blockDim.x / WAVE;
-    double* Aimg = lds;
-    double* colsum = lds + G_::AIMG;
-    for (int i = tid; i < G_::AIMG; i += blockDim.x) {
-        const int r = i / AS, cidx = i % AS;
-        Aimg[i] = (r < m && cidx < nd) ? Ag[(size_t)r * n + cidx] : 0.0;
+    if constexpr (!PA) {   // the one A of the batch: image, Gram table and column sums, once per workgroup
+        for (int i = tid; i < G_::AIMG; i += blockDim.x) {
+            const int r = i / AS, cidx = i % AS;
+            lds[i] = (r < m && cidx < nd) ? Ag[(size_t)r * n + cidx] : 0.0;
+        }
+        G_::fill_gram_table(lds, tid, blockDim.x);
+        __syncthreads();
+        for (int j = tid; j < ND; j += blockDim.x) {
+            double sacc = 0.0;
+            for (int i = 0; i < MP; i++) sacc += lds[i * AS + j];
+            lds[G_::AIMG + j] = sacc;
+        }
+        __syncthreads();
     }
-    G_::fill_gram_table(lds, tid, blockDim.x);
-    __syncthreads();
-    for (int j = tid; j < ND; j += blockDim.x) {
-        double sacc = 0.0;
-        for (int i = 0; i < MP; i++) sacc += Aimg[i * AS + j];
-        colsum[j] = sacc;
-    }
-    __syncthreads();
 
-    GWave<MP, NP, true> w;
+    GWave<MP, NP, SL> w;
     const int wave = tid / WAVE;
     const int lane = tid & 63, gl = lane & (MP - 1), grp = lane / MP;
+    double* const areas = PA ? lds + wave * P_::PW : nullptr;     // PA: G areas of this wave, then its slabs and staging region
+    if constexpr (PA) {
+        // pad rows and columns of every image (and the column sums behind it) are zero from here on; a refill writes rows < m,
+        // columns < nd only
+        for (int i = lane; i < G * P_::AREA; i += WAVE) areas[i] = 0.0;
+        wave_lds_sync();
+        for (int g = 0; g < G; g++) G_::fill_gram_table(areas + g * P_::AREA, lane, WAVE);
+    }
+    const double* const own_area = PA ? areas + grp * P_::AREA : lds;   // image, column sums and Gram table of the lane's own group
     w.lane = lane; w.gl = gl; w.grp = grp; w.m = m; w.n = n;
-    w.Aimg = Aimg;
-    w.slab0 = lds + G_::SHARED + wave * G_::WSZ;
+    w.Aimg = own_area;
+    w.slab0 = PA ? areas + G * P_::AREA : lds + G_::SHARED + wave * G_::WSZ;
     w.slab = w.slab0 + grp * G_::SLAB;
     w.stage = w.slab0 + G * G_::SLAB;
-    if constexpr (GWave<MP, NP, true>::COLB) {
+    if constexpr (GWave<MP, NP, SL>::COLB) {
 #pragma unroll
         for (int cidx = 0; cidx < 16; cidx++) w.xb[cidx] = lds_addr(w.slab) + 8u * (unsigned)G_::sidx(cidx, gl);
     }
-    if constexpr (GWave<MP, NP, true>::ROWB) {
+    if constexpr (GWave<MP, NP, SL>::ROWB) {
 #pragma unroll
         for (int p2 = 0; p2 < 16; p2++) w.rb[p2] = lds_addr(w.slab + gl * G_::MS) + 16u * (unsigned)(p2 ^ (gl & 15));
     }
@@ -67,67 +56,122 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
     const bool rowok = gl < m;
     const bool autoscale = (o.flags & PYCLLP_FLAG_AUTOSCALE) != 0;
     const unsigned long long gmask = (MP == 32) ? 0xFFFFFFFFull : 0xFFFFull;
+    const int asz = PA ? m * nd : 0;        // PA: doubles of one A_k
 
+    // slots in GROUP-major order (as ipm_group_kernel): a batch smaller than the launch's slots leaves whole lane groups idle
     const long nslots = (long)gridDim.x * wpb * G;
     long lp = (long)grp * ((long)gridDim.x * wpb) + (long)blockIdx.x * wpb + wave;
     bool live = lp < B, fresh = live;
 
-    // per-slot state.  u = 0 marks a column that takes no part (padding, or fixed); u = +inf one without an upper bound.
+    // per-slot state.  BD: u = 0 marks a column that takes no part (padding, or fixed); u = +inf one without an upper bound.
+    // Without BD, t, s, u are never written, and every read of them is an operand that BD = false or bnd(q) = false leaves unevaluated.
     double x[NCG], z[NCG], t[NCG], s[NCG], u[NCG], c[NCG], v[NCG];
     bool ok[NCG];
 #pragma unroll
     for (int q = 0; q < NCG; q++) {
         ok[q] = (q < NCD) ? (gl + MP * q < nd) : (gl < m);
-        x[q] = 1.0; z[q] = 1.0; t[q] = 1.0; s[q] = 1.0; u[q] = 0.0; c[q] = 0.0; v[q] = 0.0;
+        x[q] = 1.0; z[q] = 1.0; c[q] = 0.0; v[q] = 0.0;
+        if constexpr (BD) { t[q] = 1.0; s[q] = 1.0; u[q] = 0.0; }
     }
-    auto act = [&](int q) { return u[q] > 0.0; };
-    auto bnd = [&](int q) { return u[q] > 0.0 && u[q] < HUGE_VAL; };
+    auto act = [&](int q) { if constexpr (BD) return u[q] > 0.0; else return ok[q]; };                      // takes part
+    auto bnd = [&](int q) { if constexpr (BD) return u[q] > 0.0 && u[q] < HUGE_VAL; else return false; };   // carries t, s
+    // global column of register q (dense registers first, then (SL) the slack column of row gl) from an OPAQUE lane index: the
+    // cold paths that need it (loading / storing an LP) must not leave per-lane 64-bit addresses alive across the iterations
+    // (hoisted out of the persistent loop they cost ~30 registers and, at 256, scratch)
+    // acc + c_q x_q over the columns that take part.  Without BD c is zero where a column takes none (only a fixed column has a
+    // cost), so masking x alone is enough and the product contracts into an FMA: the form of ipm_group_kernel
+    auto add_cx = [&](int q, double acc) {
+        if constexpr (BD) return acc + (act(q) ? c[q] * x[q] : 0.0); else return acc + c[q] * (ok[q] ? x[q] : 0.0);
+    };
     auto gcol = [&](int q, int g_) { return (q < NCD) ? g_ + MP * q : nd + g_; };
     double b = 0.0, y = 0.0;
-    double tol_r = 0.0, tol_s = 0.0, tol_u = 0.0, etol = 0.0, normr0 = 1e300, norms0 = 1e300, ncomp = 1.0;
+    double tol_r = 0.0, tol_s = 0.0, tol_u = 0.0, etol = 0.0, normr0 = 1e300, norms0 = 1e300;
+    double ncomp = 1.0;                     // BD: n + m + N_b, the complementarity pairs of the slot's LP
     int it = 0;
 
     while (__any(live)) {
         if (__any(fresh)) {
+            if constexpr (PA) {
+                // ---- refill: the whole wave copies the matrix of every fresh slot into that slot's image, then its column sums ----
+#pragma unroll 1
+                for (int g = 0; g < G; g++) {
+                    if (__shfl((int)fresh, g * MP, WAVE) == 0) continue;
+                    const unsigned lo_ = (unsigned)__shfl((int)(unsigned)(lp & 0xFFFFFFFFl), g * MP, WAVE);
+                    const int hi_ = __shfl((int)(lp >> 32), g * MP, WAVE);
+                    const long lpg = ((long)hi_ << 32) | (long)lo_;
+                    const double* src = Ag + (size_t)lpg * (size_t)asz;
+                    double* img = areas + g * P_::AREA;
+                    // flat, coalesced reads, eight in flight per lane; (row, column) of element i advance by WAVE per step without a
+                    // division: WAVE = sr nd + sc
+                    int r = lane / nd, cidx = lane - r * nd;
+                    const int sr = WAVE / nd, sc = WAVE - sr * nd;
+#pragma unroll 1
+                    for (int i0 = lane; i0 < asz; i0 += 8 * WAVE) {
+                        double av[8];
+#pragma unroll
+                        for (int k = 0; k < 8; k++) av[k] = (i0 + k * WAVE < asz) ? src[i0 + k * WAVE] : 0.0;
+#pragma unroll
+                        for (int k = 0; k < 8; k++) {
+                            if (i0 + k * WAVE < asz) img[r * AS + cidx] = av[k];
+                            cidx += sc; r += sr;
+                            if (cidx >= nd) { cidx -= nd; r++; }
+                        }
+                    }
+                    wave_lds_sync();
+                    for (int j = lane; j < ND; j += WAVE) {
+                        double sacc = 0.0;
+                        for (int i = 0; i < MP; i++) sacc += img[i * AS + j];
+                        img[G_::AIMG + j] = sacc;
+                    }
+                }
+                wave_lds_sync();
+            }
             if (fresh) {
                 const int go = w.ogl();
+                const double* colsum = own_area + G_::AIMG;
 #pragma unroll
                 for (int q = 0; q < NCG; q++) {
                     const int j = gcol(q, go);
                     c[q] = ok[q] ? cg[lp * n + j] : 0.0;
-                    u[q] = ok[q] ? ug[lp * n + j] : 0.0;
+                    if constexpr (BD) u[q] = ok[q] ? ug[lp * n + j] : 0.0;
                     v[q] = (q < NCD) ? colsum[go + MP * q] : (rowok ? 1.0 : 0.0);   // A'y for y = 1
                 }
                 b = rowok ? bg[lp * m + go] : 0.0;
                 y = rowok ? 1.0 : 0.0;
             }
-            if (autoscale) {   // b, u / max|b| and c / max|c| (PYCLLP_FLAG_AUTOSCALE); undone when storing
+            if (autoscale) {   // solve the LP with b, u / max|b| and c / max|c| (PYCLLP_FLAG_AUTOSCALE); undone when storing
                 double cm = 0.0;
 #pragma unroll
-                for (int q = 0; q < NCG; q++) cm = fmax(cm, act(q) ? fabs(c[q]) : 0.0);
+                for (int q = 0; q < NCG; q++) cm = fmax(cm, (!BD || act(q)) ? fabs(c[q]) : 0.0);   // (c = 0 where !ok)
                 double sb = grp_max<MP>(fabs(b)), sc = grp_max<MP>(cm);
                 sb = (sb > 0.0) ? sb : 1.0; sc = (sc > 0.0) ? sc : 1.0;
                 if (fresh) {
                     b = b / sb;
 #pragma unroll
-                    for (int q = 0; q < NCG; q++) { c[q] = c[q] / sc; u[q] = u[q] / sb; }
+                    for (int q = 0; q < NCG; q++) {
+                        c[q] = c[q] / sc;
+                        if constexpr (BD) u[q] = u[q] / sb;
+                    }
                 }
             }
             double c2 = 0.0, u2 = 0.0, nb = 0.0;
 #pragma unroll
             for (int q = 0; q < NCG; q++) {
-                c2 += act(q) ? c[q] * c[q] : 0.0;
+                if constexpr (BD) c2 += act(q) ? c[q] * c[q] : 0.0; else c2 = fma(c[q], c[q], c2);
                 u2 += bnd(q) ? u[q] * u[q] : 0.0;
                 nb += bnd(q) ? 1.0 : 0.0;
             }
-            const double nb2 = grp_sum<MP>(b * b), nc2 = grp_sum<MP>(c2), nu2 = grp_sum<MP>(u2), nbs = grp_sum<MP>(nb);
+            const double nb2 = grp_sum<MP>(b * b), nc2 = grp_sum<MP>(c2);
+            double nu2 = 0.0, nbs = 0.0;
+            if constexpr (BD) { nu2 = grp_sum<MP>(u2); nbs = grp_sum<MP>(nb); }
             if (fresh) {
                 // start: z = s = y = 1, x = min(1, u/2), t = u - x (tau = 0)
 #pragma unroll
                 for (int q = 0; q < NCG; q++) {
                     x[q] = bnd(q) ? fmin(1.0, 0.5 * u[q]) : 1.0;
-                    t[q] = bnd(q) ? u[q] - x[q] : 1.0;
-                    z[q] = 1.0; s[q] = 1.0;
+                    if constexpr (BD) t[q] = bnd(q) ? u[q] - x[q] : 1.0;
+                    z[q] = 1.0;
+                    if constexpr (BD) s[q] = 1.0;
                 }
                 tol_r = o.eps * (1.0 + sqrt(nb2));
                 tol_s = o.eps * (1.0 + sqrt(nc2));
@@ -149,15 +193,16 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
             s2 = fma(sgq, sgq, s2);
             tau2 = fma(tau, tau, tau2);
             gam += a ? x[q] * z[q] : 0.0;
-            gam += bq ? s[q] * t[q] : 0.0;
-            pp += a ? c[q] * x[q] : 0.0;
-            du += bq ? u[q] * s[q] : 0.0;
+            if constexpr (BD) gam += bq ? s[q] * t[q] : 0.0;
+            pp = add_cx(q, pp);
+            if constexpr (BD) du += bq ? u[q] * s[q] : 0.0;
         }
-        s2 = grp_sum<MP>(s2); gam = grp_sum<MP>(gam); tau2 = grp_sum<MP>(tau2);
+        s2 = grp_sum<MP>(s2); gam = grp_sum<MP>(gam);
+        if constexpr (BD) tau2 = grp_sum<MP>(tau2);
         const double po = grp_sum<MP>(pp);
         du = grp_sum<MP>(du);
         const double norms = sqrt(s2), ntau = sqrt(tau2);
-        const double mu = o.delta * gam / ncomp;
+        const double mu = o.delta * gam / (BD ? ncomp : (double)(n + m));
 
         // store a finished LP and hand the slot its next one from the device-wide queue
         auto finalize = [&](int stat_) {
@@ -165,7 +210,7 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
             const int go = w.ogl();
             int gro = grp;
             asm volatile("" : "+v"(gro));
-            if (autoscale) {   // the scale factors from the inputs
+            if (autoscale) {   // recover the scale factors from the inputs (cheaper than carrying them in registers)
                 double cm = 0.0;
 #pragma unroll
                 for (int q = 0; q < NCG; q++) cm = fmax(cm, act(q) ? fabs(cg[lp * n + gcol(q, go)]) : 0.0);
@@ -181,7 +226,9 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
                     const double r = c[q] - v[q];      // reduced cost of a fixed column
                     xg[lp * n + j] = a ? x[q] * sb : 0.0;
                     if (zg) zg[lp * n + j] = (a ? z[q] : fmax(-r, 0.0)) * sc;
-                    if (sg) sg[lp * n + j] = (bq ? s[q] : (a ? 0.0 : fmax(r, 0.0))) * sc;
+                    if constexpr (BD) {
+                        if (sg) sg[lp * n + j] = (bq ? s[q] : (a ? 0.0 : fmax(r, 0.0))) * sc;
+                    }
                 }
             }
             if (yg && rowok) yg[lp * m + go] = y * sc;
@@ -192,8 +239,8 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
                 double pp2 = 0.0, dd2 = b * y;
 #pragma unroll
                 for (int q = 0; q < NCG; q++) {
-                    pp2 += act(q) ? c[q] * x[q] : 0.0;
-                    dd2 += bnd(q) ? u[q] * s[q] : 0.0;
+                    pp2 = add_cx(q, pp2);
+                    if constexpr (BD) dd2 += bnd(q) ? u[q] * s[q] : 0.0;
                 }
                 pof = grp_sum<MP>(pp2);
                 duf = grp_sum<MP>(dd2);
@@ -210,20 +257,26 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
             lp = nslots + (long)nxt;
             live = lp < B;
             fresh = live;
-            if (!live) {   // park the slot on harmless values
+            if (!live) {   // park the slot on harmless values (PA: its image keeps the last LP's matrix: finite, never stored from)
 #pragma unroll
-                for (int q = 0; q < NCG; q++) { x[q] = 1.0; z[q] = 1.0; t[q] = 1.0; s[q] = 1.0; u[q] = 0.0; c[q] = 0.0; v[q] = 0.0; }
+                for (int q = 0; q < NCG; q++) {
+                    x[q] = 1.0; z[q] = 1.0; c[q] = 0.0; v[q] = 0.0;
+                    if constexpr (BD) { t[q] = 1.0; s[q] = 1.0; u[q] = 0.0; }
+                }
                 b = 0.0; y = 0.0;
             }
         };
 
-        // ---- d = 1 / (z/x + s/t), t~ = c - A'y + mu/x - mu/t + (s/t) tau ----
+        // ---- d = 1 / (z/x + s/t), t~ = c - A'y + mu/x - mu/t + (s/t) tau;  no bound: d = x/z, t~ = c - A'y + mu/x ----
         double rxk[NCG], rzk[NCG], rtk[NCG];
 #pragma unroll
-        for (int q = 0; q < NCG; q++) { rxk[q] = fast_rcp(x[q]); rzk[q] = fast_rcp(z[q]); rtk[q] = fast_rcp(t[q]); }
+        for (int q = 0; q < NCG; q++) {
+            rxk[q] = fast_rcp(x[q]); rzk[q] = fast_rcp(z[q]);
+            if constexpr (BD) rtk[q] = fast_rcp(t[q]);
+        }
         auto newton_dt = [&](int q, double& dq, double& tq) {
             const bool a = act(q), bq = bnd(q);
-            const double tau = (u[q] - x[q]) - t[q];
+            const double tau = BD ? (u[q] - x[q]) - t[q] : 0.0;
             if (bq) {
                 dq = fast_rcp(fma(z[q], rxk[q], s[q] * rtk[q]));
                 tq = c[q] - v[q] + mu * rxk[q] - mu * rtk[q] + (s[q] * rtk[q]) * tau;
@@ -252,17 +305,21 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
                 }
                 wave_lds_sync();
                 double axp[JB], adp[JB];
+                if constexpr (PA) w.Aimg = areas + g * P_::AREA;       // group g's matrix (wave-uniform)
                 w.template gram_one<true, true>(g, axp, adp);
+                if constexpr (PA) w.Aimg = own_area;
                 wave_lds_sync();
                 if (grp == g) {
                     Ax_ = (JB == 1) ? axp[0] : ((gl >> 4) ? axp[JB - 1] : axp[0]);
                     Adt_ = (JB == 1) ? adp[0] : ((gl >> 4) ? adp[JB - 1] : adp[0]);
                 }
             }
-            Ax_ += act(NCG - 1) ? x[NCG - 1] : 0.0;
-            Adt_ += d[NCG - 1] * tt[NCG - 1];
-            w.slab[G_::sidx(gl, gl)] += d[NCG - 1];
-            wave_lds_sync();
+            if (SL) {   // identity columns: x_slack and (d t~)_slack go straight to row gl, d_slack onto the diagonal of M
+                Ax_ += act(NCG - 1) ? x[NCG - 1] : 0.0;
+                Adt_ += d[NCG - 1] * tt[NCG - 1];
+                w.slab[G_::sidx(gl, gl)] += d[NCG - 1];
+                wave_lds_sync();
+            }
         };
         double Ax = 0.0, Adt = 0.0;
         do_gram(Ax, Adt);
@@ -272,8 +329,8 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
         // ---- stop tests of THIS point ----
         int stat = PYCLLP_STATUS_ITERATION_LIMIT;
         bool fin = true;
-        if (!(isfinite(normr) && isfinite(norms) && isfinite(gam) && isfinite(ntau))) stat = PYCLLP_STATUS_NUMERICAL;
-        else if (normr <= tol_r && norms <= tol_s && gam <= o.eps * (1.0 + fabs(po)) && ntau <= tol_u) stat = PYCLLP_STATUS_OPTIMAL;
+        if (!(isfinite(normr) && isfinite(norms) && isfinite(gam) && (!BD || isfinite(ntau)))) stat = PYCLLP_STATUS_NUMERICAL;
+        else if (normr <= tol_r && norms <= tol_s && gam <= o.eps * (1.0 + fabs(po)) && (!BD || ntau <= tol_u)) stat = PYCLLP_STATUS_OPTIMAL;
         else if (normr > 10.0 * normr0 && normr > PYCLLP_GROWTH_FLOOR * tol_r) stat = PYCLLP_STATUS_PRIMAL_INFEASIBLE;
         else if (norms > 10.0 * norms0 && norms > PYCLLP_GROWTH_FLOOR * tol_s) stat = PYCLLP_STATUS_DUAL_INFEASIBLE;
         else fin = false;
@@ -337,11 +394,12 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
 #pragma unroll
             for (int q = 0; q < NCG; q++) {
                 const bool a = act(q), bq = bnd(q);
-                const double tau = (u[q] - x[q]) - t[q];
+                const double tau = BD ? (u[q] - x[q]) - t[q] : 0.0;
                 dz[q] = a ? (mu - z[q] * dx[q]) * rxk[q] - z[q] : 0.0;
                 dt[q] = bq ? tau - dx[q] : 0.0;
                 ds[q] = bq ? (mu - s[q] * dt[q]) * rtk[q] - s[q] : 0.0;
-                if (a) th = fmax(th, fmax(-dz[q] * rzk[q], -dx[q] * rxk[q]));
+                // (act(q) afresh: sharing dz's flag makes the BD = false kernels branch around dz instead of selecting it)
+                if (act(q)) th = fmax(th, fmax(-dz[q] * rzk[q], -dx[q] * rxk[q]));
                 if (bq) th = fmax(th, fmax(-dt[q] * rtk[q], -ds[q] * fast_rcp(s[q])));
             }
             th = grp_max<MP>(th);
@@ -349,11 +407,14 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
             y = fma(theta, dy, y);
 #pragma unroll
             for (int q = 0; q < NCG; q++) {
-                const bool a = act(q), bq = bnd(q);
+                // only a fixed column (BD) must stand still; elsewhere dx = dz = 0 where a column takes no part, and every register steps
+                const bool a = !BD || act(q), bq = bnd(q);
                 x[q] = a ? fma(theta, dx[q], x[q]) : x[q];
                 z[q] = a ? fma(theta, dz[q], z[q]) : z[q];
-                t[q] = bq ? fma(theta, dt[q], t[q]) : t[q];
-                s[q] = bq ? fma(theta, ds[q], s[q]) : s[q];
+                if constexpr (BD) {
+                    t[q] = bq ? fma(theta, dt[q], t[q]) : t[q];
+                    s[q] = bq ? fma(theta, ds[q], s[q]) : s[q];
+                }
                 v[q] = fma(theta, wv[q], v[q]);
             }
             normr0 = normr; norms0 = norms;
@@ -362,4 +423,3 @@ ipm_bounded_kernel(int m, int n, long B, const double* __restrict__ Ag, const do
         }
         if (fin && live) finalize(stat);
     }
-}

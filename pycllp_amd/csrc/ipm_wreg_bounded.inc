@@ -1,7 +1,7 @@
 // ipm_wreg_bounded.inc -- the register-resident one-LP-per-wavefront kernel (ipm_wreg_kernel) for LPs with UPPER BOUNDS:
 //   maximise c'x  subject to  A x = b,  0 <= x <= u        (u_j = +inf: no bound;  u_j = 0: the column is fixed at 0)
 // the bounded equality form of a GeneralLP (pycllp_amd/lp.py, GeneralLP.to_bounded_equality_form), any shared A.  Included by
-// ipm_wreg.hip in its seventh translation unit (WREG_PART = 6).  The step is the one of ipm_group_bounded.inc (DESIGN.md
+// ipm_wreg.hip in its seventh translation unit (WREG_PART = 6).  The step is the one of ipm_group_slot.inc (DESIGN.md
 // sections 14 and 15; tests/bounded_twin.py restates it):
 //   d = 1 / (z/x + s/t),  t~ = c - A'y + mu/x - mu/t + (s/t) tau,  tau = u - x - t,  mu = delta gamma / (n + m + N_b)
 //   M dy = A (d t~) - rho,  dx = d (t~ - A'dy),  dz = (mu - z dx)/x - z,  dt = tau - dx,  ds = (mu - s dt)/t - s

@@ -2,7 +2,7 @@
 
 ``lp.A`` is a ``SparseMatrix`` with ``data [nproblems, nnz]`` (one structure, per-problem values).  Up to m = 32 rows and
 n = 128 columns of the equality form the values are densified to ``[B, m, a_cols]`` on the host and solved on the lane-group
-kernel for per-problem A (``pycllp_hip_dense_solve_batch``, csrc/ipm_group_perA.inc): ``kernel == 'group per-problem'``.
+kernel for per-problem A (``pycllp_hip_dense_solve_batch``, csrc/ipm_group_slot.inc, PA): ``kernel == 'group per-problem'``.
 Beyond that the LP goes to ``HipSparsePrimalNormalSolver`` unchanged: ``kernel == 'delegated'``.
 """
 import numpy as np

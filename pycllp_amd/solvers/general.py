@@ -1,7 +1,7 @@
 """HIP solver plugins for ``GeneralLP``:  optimise c'x + f  s.t.  a <= A x <= b,  l <= x <= u.
 
 The LP is brought into the bounded equality form (``GeneralLP.to_bounded_equality_form``: A^ = [+-A | I], 0 <= x^ <= u^) and
-solved on the bounded slack-aware lane-group kernel (``pycllp_hip_dense_solve_bounded``, csrc/ipm_group_bounded.inc): one row
+solved on the bounded slack-aware lane-group kernel (``pycllp_hip_dense_solve_bounded``, csrc/ipm_group_slot.inc, BD): one row
 per kept row of the LP and no row per upper bound.  What that kernel does not serve -- more than 32 kept rows, more than 96
 columns, per-problem values of A -- is solved through the reference's conversion ``to_standard_form().to_equality_form()``
 (``pycllp/lp.py:725-792``) on ``HipDensePrimalNormalSolver`` and mapped back the same way, so the plugin takes every LP the

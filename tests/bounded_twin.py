@@ -1,4 +1,4 @@
-"""CPU twin of the bounded primal-normal step (csrc/ipm_group_bounded.inc), vectorised over LPs.
+"""CPU twin of the bounded primal-normal step (csrc/ipm_group_slot.inc, BD), vectorised over LPs.
 
 Test infrastructure only: a numpy restatement of the kernel's arithmetic -- start point, residuals, stop tests, the modified
 LDL' with the Nocedal-Wright guard, the x-space refinement and the step -- so that the GPU tests can compare objectives and

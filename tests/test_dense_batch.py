@@ -1,4 +1,4 @@
-"""Per-problem DENSE matrices on the lane-group kernel (pycllp_hip_dense_solve_batch, csrc/ipm_group_perA.inc) and its plugin
+"""Per-problem DENSE matrices on the lane-group kernel (pycllp_hip_dense_solve_batch, csrc/ipm_group_slot.inc, PA) and its plugin
 hip_dense_batch_primal_normal.  The reference of every comparison is oracle.port.dense_solve run LP by LP with that LP's own
 matrix; bounds are the project's: status equal and 0, iterations within 1, objectives 1e-9 relative, x at rtol 1e-5 / atol 1e-7.
 
