@@ -248,6 +248,18 @@ int oracle_solve_primal_normal(int m, int N, const double *A, const double *x, c
     return nref;
 }
 
+/* the same step under caller-given options (pivot_floor, refine_tol, max_refine); returns the refinement passes used */
+int oracle_solve_primal_normal_opts(int m, int N, const double *A, const double *x, const double *z,
+                                    const double *y, const double *b, const double *c, double mu,
+                                    const oracle_opts *o, double *dy) {
+    work wk;
+    work_alloc(&wk, m, N);
+    int nref = newton_dy(m, N, A, x, z, y, b, c, mu, o, &wk);
+    memcpy(dy, wk.dy, sizeof(double) * m);
+    work_free(&wk);
+    return nref;
+}
+
 /*
  * One LP: max c'x s.t. Ax = b, x >= 0 (equality form, lp.py:306-330), the loop of
  * primal_normal.cl:201-284 with the step of primal_normal.cl:122-156.

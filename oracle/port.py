@@ -34,6 +34,7 @@ def lib():
         _LIB.oracle_default_opts.argtypes = [ctypes.POINTER(OracleOpts)]
         _LIB.oracle_dense_solve.restype = ctypes.c_int
         _LIB.oracle_solve_primal_normal.restype = ctypes.c_int
+        _LIB.oracle_solve_primal_normal_opts.restype = ctypes.c_int
     return _LIB
 
 
@@ -77,15 +78,17 @@ def dense_solve(A, b, c, nthreads=1, x0=None, y0=None, z0=None, **opts):
     return dict(x=x, y=y, z=z, pobj=pobj, dobj=dobj, status=status, iters=iters, nrefs=nrefs)
 
 
-def solve_primal_normal(A, x, z, y, b, c, mu, pivot_floor=1e-6):
-    """One Newton step dy (ldl.cl:602-653) through the C restatement."""
+def solve_primal_normal(A, x, z, y, b, c, mu, pivot_floor=1e-6, passes=False, **opts):
+    """One Newton step dy (ldl.cl:602-653) through the C restatement; ``opts``: further fields of the oracle's options
+    (refine_tol, max_refine).  ``passes=True``: (dy, the number of refinement passes used)."""
     A = np.ascontiguousarray(A, dtype=np.float64)
     m, N = A.shape
     args = [np.ascontiguousarray(v, dtype=np.float64) for v in (x, z, y, b, c)]
     dy = np.empty(m)
-    lib().oracle_solve_primal_normal(ctypes.c_int(m), ctypes.c_int(N), _p(A), *[_p(v) for v in args],
-                                     ctypes.c_double(mu), ctypes.c_double(pivot_floor), _p(dy))
-    return dy
+    o = default_opts(pivot_floor=pivot_floor, **opts)
+    nref = lib().oracle_solve_primal_normal_opts(ctypes.c_int(m), ctypes.c_int(N), _p(A), *[_p(v) for v in args],
+                                                 ctypes.c_double(mu), ctypes.byref(o), _p(dy))
+    return (dy, int(nref)) if passes else dy
 
 
 def ldl(A, modified=False, beta=None, delta=1e-6):

@@ -45,6 +45,22 @@ def equality_batch(m, N, B, seed):
     return _frozen(EqualityLP(A_, b, c, 0.0))
 
 
+def degenerate_batch(m, N, B, seed):
+    """The construction of trajectory.degenerate LP by LP, on the matrices of ``equality_batch``: the last row of every A_k
+    replaced by its row 3 + 1e-6 noise, b and c around a strictly feasible primal-dual pair of the new matrix."""
+    A = matrices(equality_batch(m, N, B, seed)).copy()
+    rs = np.random.RandomState(31)
+    A[:, -1] = A[:, 3] + 1e-6 * rs.randn(B, N)
+    x0, y0 = rs.rand(B, N) + 0.1, rs.randn(B, m)
+    b = np.einsum("kij,kj->ki", A, x0)
+    c = np.einsum("kij,ki->kj", A, y0) - (rs.rand(B, N) + 0.1)
+    b /= np.abs(b).max(axis=1, keepdims=True)
+    c /= np.abs(c).max(axis=1, keepdims=True)
+    A_ = SparseMatrix(*dense_structure(m, N), A.reshape(B, -1))
+    A_._shape = (m, N)
+    return _frozen(EqualityLP(A_, b, c, 0.0))
+
+
 def _frozen(lp):
     for a in (lp.b, lp.c, lp.A.data):
         a.setflags(write=False)

@@ -32,6 +32,9 @@ NPERM, FACTOR, FLOOR, CEILING = 4, 32.0, 1e-13, 1e-9
 WARM, GUARD, AUTOSCALE, NO_SLACK, BLOCK = 1, 4, 8, 16, 64          # PYCLLP_FLAG_*
 ORACLE_FLAGS = dict(tkv.ORACLE_FLAGS, guard=0)
 QUANTITIES = ("x", "y", "z", "pobj", "dobj")
+# At the iteration limit the oracle and most kernels return the objectives of the iterate BEFORE the last step; the per-problem
+# dense-A lane-group kernel stores c'x, b'y of the point it stores (tests/test_dense_batch.py test_trajectory).
+STORES_ITS_OWN_OBJECTIVES = ("perA",)
 
 # family, kind, point label, mode ('cold', 'warm', 'autoscale', 'degenerate'), the k ladder, input key (see ``inputs``), what
 # must serve it (lane groups and wave kernel: the compiled shape; block and large-LP kernel: the case of
@@ -125,12 +128,15 @@ def inputs(key):
         return tkv.banded(make_general(len(kinds), n, nb, seed, kinds=kinds, fixed=2, mixed_u=True))
     if what == "degenerate":
         return _frozen(degenerate(inputs(key[1])))
+    if what in MORE_INPUTS:                                  # input keys of tests/option_cases.py
+        return MORE_INPUTS[what](key)
     if what == "scaled":                                     # the same LPs with b 1e3 and c 1e-2: what autoscale is for
         lp = inputs(key[1])
         return _frozen(EqualityLP(lp.A, lp.b * 1e3, lp.c * 1e-2, 0.0))
     raise KeyError(key)
 
 
+MORE_INPUTS = {}
 Problem = collections.namedtuple("Problem", "A b c u f bmap shared tail")
 
 
@@ -175,12 +181,15 @@ def probe_entry(P):
 def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, **opts):
     """The reference's results after k iterations: dict(x, y, z[, s], pobj, dobj, status, iters, nrefs, aty).  ``perm``: seed of
     a row-and-column permutation under which the LPs are solved (results mapped back); ``r_scale``: factor on the step
-    fraction r; ``a_scale``: factor on ``probe_entry`` of A; ``opts``: further fields of the oracle's options."""
+    fraction r; ``a_scale``: factor on ``probe_entry`` of A; ``opts``: further fields of the oracle's options (``r``: the step
+    fraction ``r_scale`` multiplies, default 0.9)."""
     from oracle import port
     bounded = case.kind == "bounded"
     P = problem(case.key, bounded)
     m, N = P.A[0].shape
     nb = P.b.shape[0]
+    opts = dict(opts)
+    r_frac = opts.pop("r", 0.9) * r_scale
     rows, cols = np.arange(m), np.arange(N)
     if perm is not None:
         rs = np.random.RandomState(1000 + perm)
@@ -199,7 +208,7 @@ def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, **opts):
     As = [np.ascontiguousarray(A[rows][:, cols]) for A in As]
     b, c = P.b[:, rows], P.c[:, cols]
     if bounded:
-        r = bounded_twin.solve(As[0], b, c, P.u[:, cols], max_iter=k, r=0.9 * r_scale, **opts)
+        r = bounded_twin.solve(As[0], b, c, P.u[:, cols], max_iter=k, r=r_frac, **opts)
         r["nrefs"] = np.zeros(nb, dtype=np.int32)
     else:
         flags = ORACLE_FLAGS[case.kind] | (AUTOSCALE if case.mode == "autoscale" else 0)
@@ -207,7 +216,7 @@ def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, **opts):
         if case.mode == "warm":
             x0, y0, z0 = warm_point(nb, m, N)
             start, flags = dict(x0=x0[:, cols], y0=y0[:, rows], z0=z0[:, cols]), flags | WARM
-        opts = dict(opts, max_iter=k, r=0.9 * r_scale, flags=flags)
+        opts = dict(opts, max_iter=k, r=r_frac, flags=flags)
         if P.shared:
             r = port.dense_solve(As[0], b, c, nthreads=8, **start, **opts)
         else:
@@ -221,6 +230,8 @@ def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, **opts):
             out[q] = r[q][:, inv_c]
     out["y"] = r["y"][:, inv_r]
     out["aty"] = a_transpose_y(P, out["y"])
+    if case.family in STORES_ITS_OWN_OBJECTIVES:
+        out["pobj"], out["dobj"] = (P.c * out["x"]).sum(axis=1), (P.b * out["y"]).sum(axis=1)
     if bounded:
         out["x"], out["y"], out["z"], out["s"] = P.bmap.general(out["x"], out["y"], out["z"], out["s"])
     return out
@@ -245,35 +256,43 @@ def deviation(a, ref):
     return np.abs(a - ref).max(axis=1) / np.where(scale > 0, scale, 1.0)
 
 
+def option_key(opts):
+    """Solver options as the hashable the caches below take."""
+    return tuple(sorted(dict(opts).items()))
+
+
 @functools.lru_cache(maxsize=None)
-def reference(cid):
-    """{k: the reference's results} of a case, computed once (read-only)."""
-    case = BY_ID[cid]
-    out = {}
-    for k in case.ks:
-        out[k] = run_reference(case, k)
-        for a in out[k].values():
-            a.setflags(write=False)
+def _reference_at(cid, k, opts):
+    out = run_reference(BY_ID[cid], k, **dict(opts))
+    for a in out.values():
+        a.setflags(write=False)
     return out
 
 
 @functools.lru_cache(maxsize=None)
-def spread(cid):
+def _spread_at(cid, k, opts):
+    case = BY_ID[cid]
+    ref = _reference_at(cid, k, opts)
+    runs = [run_reference(case, k, perm=p, **dict(opts)) for p in range(NPERM)]
+    return {q: max(float(deviation(r[q], ref[q]).max()) for r in runs) for q in quantities(case)}
+
+
+def reference(cid, opts=(), ks=None):
+    """{k: the reference's results} of a case under the options ``opts`` (``option_key``), each computed once (read-only);
+    ``ks``: the iteration counts, default the case's ladder."""
+    return {k: _reference_at(cid, k, opts) for k in (BY_ID[cid].ks if ks is None else ks)}
+
+
+def spread(cid, opts=(), ks=None):
     """{k: {quantity: largest deviation of the reference under NPERM permutations, over the LPs of the batch}}"""
-    case = BY_ID[cid]
-    ref = reference(cid)
-    out = {}
-    for k in case.ks:
-        runs = [run_reference(case, k, perm=p) for p in range(NPERM)]
-        out[k] = {q: max(float(deviation(r[q], ref[k][q]).max()) for r in runs) for q in quantities(case)}
-    return out
+    return {k: _spread_at(cid, k, opts) for k in (BY_ID[cid].ks if ks is None else ks)}
 
 
-def tolerance(cid):
+def tolerance(cid, opts=(), ks=None):
     """{k: {quantity: bound}}: max(FACTOR spread, FLOOR), or the case's explicit margin (never above CEILING)."""
     case = BY_ID[cid]
     out = {}
-    for k, sp in spread(cid).items():
+    for k, sp in spread(cid, opts, ks).items():
         out[k] = {q: max(FACTOR * v, FLOOR) for q, v in sp.items()}
         if case.margin and k in case.margin:
             assert case.cause and case.margin[k] <= CEILING
@@ -299,17 +318,19 @@ def solver_options(case):
                 **({"flags": case.flags} if case.flags else {}))
 
 
-def kernel_results(case):
-    """{k: results of the kernel after k iterations} in the layout of ``run_reference``; every launch asserts what served it."""
+def kernel_results(case, ks=None, **opts):
+    """{k: results of the kernel after k iterations} in the layout of ``run_reference``; every launch asserts what served it.
+    ``ks``: the iteration limits (default the case's ladder); ``opts``: further fields of ``pycllp_hip_opts``."""
     import torch
     from pycllp_amd.solvers import solver_registry
     lp = inputs(case.key)
+    ks = case.ks if ks is None else ks
     out = {}
     if case.kind == "bounded":
         P = problem(case.key, True)
         name = "hip_general_primal_normal" if case.family == "slack" else "hip_sparse_general_primal_normal"
-        for k in case.ks:
-            s = solver_registry[name](device="cuda:0", hsd=False, autoscale=False, max_iter=k)
+        for k in ks:
+            s = solver_registry[name](device="cuda:0", hsd=False, autoscale=False, max_iter=k, **opts)
             lp.init(s)
             lp.solve(s)
             assert_served(case, s.launch_info(), lp, s)
@@ -324,13 +345,13 @@ def kernel_results(case):
         lp.solve(s)                                        # uploads the per-problem values of A (one iteration)
     m, N = P.A[0].shape
     nb = lp.nproblems
-    for k in case.ks:
+    for k in ks:
         if case.mode == "warm":
             if "set0" not in s.buffers:
                 s.solve_device(lp.b, lp.c, max_iter=1)     # allocates the result buffers a warm start reads
             for q, v in zip(("x", "y", "z"), warm_point(nb, m, N)):
                 s.buffers["set0"][q].copy_(torch.as_tensor(v, device="cuda:0"))
-        g = s.solve_device(lp.b, lp.c, warm_start=case.mode == "warm", max_iter=k)
+        g = s.solve_device(lp.b, lp.c, warm_start=case.mode == "warm", max_iter=k, **opts)
         torch.cuda.synchronize()
         assert_served(case, s.launch_info(), lp, s)
         out[k] = {q: g[q].cpu().numpy() for q in ("x", "y", "z", "pobj", "dobj", "status", "iters")}
@@ -484,3 +505,9 @@ def build_cases():
 CASES = build_cases()
 BY_ID = {c.id: c for c in CASES}
 assert len(BY_ID) == len(CASES)
+
+
+def register(case):
+    """Make a case that is no row of ``CASES`` (tests/option_cases.py) known to ``reference``, ``spread`` and ``tolerance``."""
+    assert BY_ID.setdefault(case.id, case) == case, case.id
+    return case
