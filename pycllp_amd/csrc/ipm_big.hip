@@ -4,12 +4,12 @@
 // otherwise.  Two or three workgroups share a compute unit at every size the kernel takes, never one (BIG_SHAPES below).
 //
 // Why: the reference's hosts take any (m, n) (pycllp/solvers/cl.py:28-83, 127-278; examples/random_problem.py:30-49 is run
-// with arbitrary sizes); the lane-group kernels stop at m = 32, the wavefront-per-LP kernel (ipm_wreg.hip) at m = 128 --
+// with arbitrary sizes); the lane-group kernels stop at m = 32, the wavefront-per-LP kernel (wreg_wave.h) at m = 128 --
 // its factor fills the register file of a SIMD.  Beyond that one LP gets a whole compute unit:
 //   * M = A diag(x/z) A' and its factor are kept as the upper block triangle of U = L' in 16 x 16 blocks stored in the
 //     ACCUMULATOR layout of v_mfma_f64_16x16x4_f64 (element [4r + l/16][l%16] of a block = double r*64 + l): a block
 //     is loaded with four coalesced 512-byte reads straight into the registers an MFMA wants -- that layout is at once the
-//     B operand of the block and the A operand of its transpose (the algebra of ipm_wreg.hip, the blocks in memory instead
+//     B operand of the block and the A operand of its transpose (the algebra of wreg_wave.h, the blocks in memory instead
 //     of registers), so panel (Y_KI = L_KK^-1 M_KI) and trailing update (M_JI -= Y_KJ' D_K^-1 Y_KI) are MFMAs on loaded
 //     blocks with no layout conversion; the blocks of a stage are dealt round-robin to the four waves, three workgroup
 //     barriers per block column;
@@ -280,7 +280,7 @@ ipm_big_kernel(BigTab T, long B, const double* __restrict__ bg, const double* __
                         double aDn, rDn;
                         chain_step_pipe_relf<j>(Wd, u, nli, 0.0, myf, aDn, rDn);
                         rD = rDn;
-                        winv_step<j>(Ws, nli);      // step j of W = L_KK^-1 rides along with the sweep (see ipm_wreg.hip)
+                        winv_step<j>(Ws, nli);      // step j of W = L_KK^-1 rides along with the sweep (see wreg_wave.h)
                     }
                 });
                 if (q == 0) rdv[16 * K + c16] = rdiag;
@@ -393,7 +393,7 @@ ipm_big_kernel(BigTab T, long B, const double* __restrict__ bg, const double* __
         __syncthreads();
     };
 
-    // ---- um <- (L D L')^-1 um: block substitution on wave 0 (forms and reductions as in ipm_wreg.hip's solve()) ----
+    // ---- um <- (L D L')^-1 um: block substitution on wave 0 (forms and reductions as in wreg_wave.h's solve()) ----
     auto solve = [&]() {
         __syncthreads();
         if (wave == 0) {

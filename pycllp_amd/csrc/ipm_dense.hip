@@ -711,7 +711,7 @@ struct pycllp_hip_sparse {
     mutable std::mutex info_mu;
     int lds = 0, num_cu = 0, grid = 0;
     int lds_with_a = 0;     // LDS bytes with A's arrays in LDS (what per-problem values need), 0 when that does not fit
-    WregPlan* wreg = nullptr;     // tables of the register-resident wave kernel (ipm_wreg.hip), or nullptr when it does not cover A
+    WregPlan* wreg = nullptr;     // tables of the register-resident wave kernel (wreg_wave.h; host side ipm_wreg.hip), or nullptr when it does not cover A
     BigPlan* big = nullptr;       // LPs beyond m = 128 / n = 512: the workgroup-per-LP kernel of ipm_big.hip serves the handle alone
     WregPlan* wreg_pa = nullptr;  // its per-problem-A plan (structure tables only), built by the first pycllp_hip_sparse_solve_batch
     WregPlan* last_plan = nullptr;   // the wave kernel's plan when the last solve ran on it, else null

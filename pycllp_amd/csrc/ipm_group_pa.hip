@@ -29,7 +29,7 @@ static hipError_t launch_group_pa(const GroupPaArgs& a, int grid, int block, int
 #define GROUP_PA_VARIANT(MP, NP) { MP, NP, 0, launch_group_pa<MP, NP, false> }, { MP, NP, 1, launch_group_pa<MP, NP, true> },
 // The device pass gets a file-local copy of the table: it is never emitted, but referencing the launchers is what makes the
 // kernels get instantiated (an external table of host function pointers would be emitted into the device object and fail to
-// link there; as WREG_TABLE of ipm_wreg.hip).
+// link there; as WREG_TABLE of wreg_wave.h).
 #ifdef __HIP_DEVICE_COMPILE__
 namespace { [[maybe_unused]] const GroupPaVariant kGroupPA_instantiate[] = { GROUP_PA_SHAPES(GROUP_PA_VARIANT) }; }
 #else

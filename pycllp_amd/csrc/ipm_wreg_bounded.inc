@@ -1,7 +1,7 @@
 // ipm_wreg_bounded.inc -- the register-resident one-LP-per-wavefront kernel (ipm_wreg_kernel) for LPs with UPPER BOUNDS:
 //   maximise c'x  subject to  A x = b,  0 <= x <= u        (u_j = +inf: no bound;  u_j = 0: the column is fixed at 0)
-// the bounded equality form of a GeneralLP (pycllp_amd/lp.py, GeneralLP.to_bounded_equality_form), any shared A.  Included by
-// ipm_wreg.hip in its seventh translation unit (WREG_PART = 6).  The step is the one of ipm_group_slot.inc (DESIGN.md
+// the bounded equality form of a GeneralLP (pycllp_amd/lp.py, GeneralLP.to_bounded_equality_form), any shared A.  On
+// wreg_wave.h; compiled by ipm_wreg_bd.hip.  The step is the one of ipm_group_slot.inc (DESIGN.md
 // sections 14 and 15; tests/bounded_twin.py restates it):
 //   d = 1 / (z/x + s/t),  t~ = c - A'y + mu/x - mu/t + (s/t) tau,  tau = u - x - t,  mu = delta gamma / (n + m + N_b)
 //   M dy = A (d t~) - rho,  dx = d (t~ - A'dy),  dz = (mu - z dx)/x - z,  dt = tau - dx,  ds = (mu - s dt)/t - s
@@ -20,6 +20,8 @@
 //     point's A'y is at hand for the duals of the fixed columns; the point itself is the one the verdict was reached on.
 // No warm start, no predictor-corrector, no HSD.
 
+namespace {
+
 template <int MB, int NQ, bool DA>
 __global__ void __launch_bounds__(256, 1)
 ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const double* __restrict__ cg,
@@ -37,17 +39,10 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
     const bool autoscale = (o.flags & PYCLLP_FLAG_AUTOSCALE) != 0;
     double* vx = w.stage_();
     bool okc[NQ], okr[MR];
-#pragma unroll
-    for (int qq = 0; qq < NQ; qq++) okc[qq] = lane + 64 * qq < n;
-#pragma unroll
-    for (int r2 = 0; r2 < MR; r2++) okr[r2] = lane + 64 * r2 < m;
+    w.masks(okc, okr);
 
-    long lp;
-    {
-        int nxt = 0;
-        if (lane == 0) nxt = atomicAdd(queue, 1);
-        lp = __builtin_amdgcn_readfirstlane(nxt);
-    }
+    long lp = next_item(queue, lane);
+    STAMP_DECL
     while (lp < B) {
         // padded positions read u = 0 (buffer offset past the row): they take no part, like a fixed column
         const __amdgpu_buffer_rsrc_t rc = row_rsrc(cg + lp * n, n), ru = row_rsrc(ug + lp * n, n);
@@ -78,8 +73,8 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
             u2 += bq ? uj * uj : 0.0;
             nbc += bq ? 1.0 : 0.0;
             const double xq = bq ? fmin(1.0, 0.5 * uj) : 1.0;
-            w.stage_()[NP + lane + 64 * qq] = xq;
-            w.stage_()[2 * NP + lane + 64 * qq] = 1.0;
+            w.px(qq) = xq;
+            w.pz(qq) = 1.0;
             w.W0[TS + lane + 64 * qq] = bq ? uj - xq : 1.0;
             w.W0[TS + NP + lane + 64 * qq] = 1.0;
         }
@@ -109,8 +104,8 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
 #pragma unroll
             for (int qq = 0; qq < NQ; qq++) {
                 if (autoscale) { cq[qq] = cq[qq] / sc; uq[qq] = uq[qq] / sb; }
-                x[qq] = w.stage_()[NP + lane + 64 * qq];
-                z[qq] = w.stage_()[2 * NP + lane + 64 * qq];
+                x[qq] = w.px(qq);
+                z[qq] = w.pz(qq);
                 vx[lane + 64 * qq] = (uq[qq] > 0.0) ? x[qq] : 0.0;
             }
             wave_lds_sync();
@@ -220,16 +215,16 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
 #pragma unroll
             for (int qq = 0; qq < NQ; qq++) {
                 w.stage_()[lane + 64 * qq] = tt[qq];
-                w.stage_()[NP + lane + 64 * qq] = x[qq];
-                w.stage_()[2 * NP + lane + 64 * qq] = z[qq];
+                w.px(qq) = x[qq];
+                w.pz(qq) = z[qq];
             }
-            const bool viol = w.template factor<false>(beta2, o.pivot_floor);
+            const bool viol = w.template factor<false>(beta2, o.pivot_floor STAMP_PASS);
             if (viol) { forced = PYCLLP_STATUS_NUMERICAL; continue; }   // the guard would have bitten: no guarded kernel here
             double dy[MR], wv[NQ], dx[NQ], e[MR], rhn[MR];
             bool bad;
 #pragma unroll
             for (int r2 = 0; r2 < MR; r2++) rhn[r2] = (lane + 64 * r2 < MP) ? w.flr_()[lane + 64 * r2] : 0.0;
-            (void)newton_solve<false>(w, okc, okr, rhn, etol, o.max_refine, mu, dy, dx, wv, e, bad, nullptr);
+            (void)newton_solve<false>(w, okc, okr, rhn, etol, o.max_refine, mu, dy, dx, wv, e, bad, nullptr STAMP_PASS);
             if (bad) { forced = PYCLLP_STATUS_NUMERICAL; continue; }
             // ---- step: theta = min(r / max(0, -dx/x, -dz/z, -dt/t, -ds/s), 1) ----
             double th = 0.0;
@@ -240,7 +235,7 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
                 double uj = buf_ld(ru, jo);
                 if (autoscale) uj = uj / sb;
                 const bool a = uj > 0.0, bq = a && uj < HUGE_VAL;
-                const double xq = w.stage_()[NP + lane + 64 * qq], zq = w.stage_()[2 * NP + lane + 64 * qq];
+                const double xq = w.px(qq), zq = w.pz(qq);
                 const double tq = w.W0[TS + lane + 64 * qq], sq = w.W0[TS + NP + lane + 64 * qq];
                 const double rx = fast_rcp(xq), rz = fast_rcp(zq), rt = fast_rcp(tq);
                 const double tau = (uj - xq) - tq;
@@ -261,8 +256,8 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
 #pragma unroll
             for (int qq = 0; qq < NQ; qq++) {
                 // (dx, dz are 0 where the column takes no part, dt, ds where it has no bound: those values stay)
-                w.stage_()[NP + lane + 64 * qq] = fma(theta, dx[qq], w.stage_()[NP + lane + 64 * qq]);
-                w.stage_()[2 * NP + lane + 64 * qq] = fma(theta, dz[qq], w.stage_()[2 * NP + lane + 64 * qq]);
+                w.px(qq) = fma(theta, dx[qq], w.px(qq));
+                w.pz(qq) = fma(theta, dz[qq], w.pz(qq));
                 w.W0[TS + lane + 64 * qq] = fma(theta, dt[qq], w.W0[TS + lane + 64 * qq]);
                 w.W0[TS + NP + lane + 64 * qq] = fma(theta, ds[qq], w.W0[TS + NP + lane + 64 * qq]);
             }
@@ -272,8 +267,8 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
             if (it >= o.max_iter) forced = PYCLLP_STATUS_ITERATION_LIMIT;
         }
         wave_lds_sync();
-        int nxt = 0;
-        if (lane == 0) nxt = atomicAdd(queue, 1);
-        lp = __builtin_amdgcn_readfirstlane(nxt);
+        lp = next_item(queue, lane);
     }
 }
+
+}  // namespace

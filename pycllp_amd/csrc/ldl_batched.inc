@@ -65,7 +65,7 @@ ldl_batched_kernel(int n, long B, const double* __restrict__ Ag, double* __restr
 // prototype of the OpenCL Newton solve): the forward substitution rides on the factorisation sweep (x_j /= D_j, then
 // x_i -= u_ij x_j with the RAW column u, ldl.py:270-273), the backward substitution reuses L.  One matrix per
 // workgroup, thread i owns row i.  modified == 0 gives pycllp/ldl.py:202-239 solve_ldl (used for n > 128 never: the
-// register kernel of ipm_wreg.hip serves it; kept as the generic form).
+// register kernel of ipm_wreg.hip (ldl_solve_wreg_kernel) serves it; kept as the generic form).
 __global__ void __launch_bounds__(128)
 ldl_solve_batched_kernel(int n, long B, const double* __restrict__ Ag, const double* __restrict__ rhs,
                          double* __restrict__ xg, int modified, double beta, double delta) {

@@ -1,4 +1,4 @@
-// wave_common.h -- device helpers shared by the translation units of libpycllp_hip.so (ipm_dense.hip, ipm_wreg.hip).
+// wave_common.h -- device helpers shared by the translation units of libpycllp_hip.so (ipm_dense.hip, ipm_wreg*.hip).
 #ifndef PYCLLP_WAVE_COMMON_H
 #define PYCLLP_WAVE_COMMON_H
 #include <hip/hip_runtime.h>
@@ -480,7 +480,7 @@ __device__ __forceinline__ void winv_step(double (&Ws)[4], double nl) {
                  : "+v"(Ws[0]), "+v"(Ws[1]), "+v"(Ws[2]), "+v"(Ws[3]) : "v"(nl), "n"(J));
 }
 
-// ---- batched LDS reads (see ipm_wreg.hip for the rest of the family) -------------------------------------------
+// ---- batched LDS reads (see wreg_wave.h for the rest of the family) -------------------------------------------
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
 }

@@ -1,13 +1,40 @@
-// wreg.h -- internal interface between ipm_dense.hip (C ABI, handles) and ipm_wreg.hip (the register-resident
-// one-LP-per-wavefront kernel of the sparse shared-A path).  Not part of the public ABI.
+// wreg.h -- internal interface between ipm_dense.hip (C ABI, handles), ipm_wreg.hip (host side of the register-resident
+// one-LP-per-wavefront kernels of the sparse shared-A path) and the units that compile those kernels (ipm_wreg_*.hip on
+// wreg_wave.h).  Not part of the public ABI.
 #ifndef PYCLLP_WREG_H
 #define PYCLLP_WREG_H
 #include "wave_common.h"
 
-// ---- shared between the translation units the wave kernels are compiled in (ipm_wreg.hip, seven times: WREG_PART 0..6) ----
+// ---- shared between the host unit (ipm_wreg.hip) and the seven units the wave kernels are compiled in (ipm_wreg_*.hip) ----
 constexpr int MAX_NQ = 8;
 constexpr int META_COFF = MAX_NQ, META_SEG = 2 * MAX_NQ, META_N = META_SEG + 16;
 
+// Geometry of a wave's LDS area: the kernels (wreg_wave.h) and the plan builders of the host (ipm_wreg.hip) compute the same.
+// stage proper: N-vector staging; during factor/solve t, x and z parked at 0, NP, 2 NP and the stride-17 tile of the current
+// diagonal block behind them
+constexpr int TILE_D = 272;
+__host__ __device__ constexpr int tile_off(int NQ) { return 192 * NQ > 768 ? 192 * NQ : 768; }
+__host__ __device__ constexpr int stage_d(int NQ) { return tile_off(NQ) + TILE_D; }
+constexpr int HB = 8;            // 16 x 16 blocks per Gram staging chunk: the stage and, behind it, the still unused W area (16 KB)
+constexpr int WL = 144;          // doubles per diagonal-block slot: first the ORIGINAL diagonal block of M (lower triangle with
+                                 // diagonal, row i at i(i+1)/2: 136), from stage K on W_K (strictly lower triangle, row i at i(i-1)/2)
+template <int MB>
+struct WGeo {
+    static constexpr int MP = 16 * MB;
+    static constexpr int MR = (MP + 63) / 64;    // m-vector registers per lane in "lane = row" form
+    static constexpr int MPL = 64 * MR;
+    static constexpr int NBLK = MB * (MB - 1) / 2;
+    // off-diagonal block (K, I), K < I, of U = L'
+    __host__ __device__ static constexpr int bix(int K, int I) { return K * MB - K * (K + 1) / 2 + (I - K - 1); }
+    // Gram staging chunks: the off-diagonal blocks in bix order, HB at a time; chunk NCHUNK = the diagonal blocks
+    static constexpr int NCHUNK = (NBLK + HB - 1) / HB;
+    // the diagonal blocks' entries ride with the last chunk when its blocks end in front of the W area (where they go)
+    __host__ __device__ static constexpr bool MERGE_DIAG(int NQ) { return NBLK > 0 && (NBLK - HB * (NCHUNK - 1)) * 256 <= stage_d(NQ); }
+    static constexpr int WAVE_D(int NQ) { return stage_d(NQ) + 64 * NQ + 5 * MP + MB * WL; }   // per-wave LDS doubles
+};
+// byte offset of a padded position of the N-vectors inside an LP's row: past the row, where a buffer load reads 0 and a
+// store is dropped (row_rsrc, wreg_wave.h)
+constexpr unsigned PAD_OFF = 0x7ffffff0u;
 
 // Device view of the tables of one constraint matrix (built by wreg_plan_create).
 struct WregTab {
@@ -61,16 +88,16 @@ typedef hipError_t (*wbsolve_fn)(const WregTab&, long, const double*, const doub
 // The launchers of one (MB, NQ) of one kernel kind; a launcher the kind does not have is null.
 struct WVariant { int mb, nq; wsolve_fn solve, solve_hsd; wnewton_fn newton; wbsolve_fn solve_bounded; };
 struct WVariants { const WVariant* v; int n; };
-// One table per kind, each defined by the translation unit (ipm_wreg.hip, -DWREG_PART=k) that compiles its kernels;
-// launchers are matched across tables by (MB, NQ), never by position.
-extern const WVariants kWTab;      // 0: term tables (plain, HSD, Newton)
-extern const WVariants kWDA;       // 1: dense image (plain, HSD, Newton)
-extern const WVariants kWPA;       // 2: per-problem A on structure tables (plain, HSD)
-extern const WVariants kWPC;       // 3: predictor-corrector kernels of kWTab's kind
-extern const WVariants kWPCDA;     // 4: ... of kWDA's kind
-extern const WVariants kWPCPA;     // 5: ... of kWPA's kind
-extern const WVariants kWBD;       // 6: upper bounds, term tables
-extern const WVariants kWBDDA;     // 6: upper bounds, dense image
+// One table per kind, each defined by the translation unit that compiles its kernels; launchers are matched across tables
+// by (MB, NQ), never by position.
+extern const WVariants kWTab;      // ipm_wreg_tab.hip:  term tables (plain, HSD, Newton)
+extern const WVariants kWDA;       // ipm_wreg_da.hip:   dense image (plain, HSD, Newton)
+extern const WVariants kWPA;       // ipm_wreg_pa.hip:   per-problem A on structure tables (plain, HSD)
+extern const WVariants kWPC;       // ipm_wreg_pc.hip:   predictor-corrector kernels of kWTab's kind
+extern const WVariants kWPCDA;     // ipm_wreg_pcda.hip: ... of kWDA's kind
+extern const WVariants kWPCPA;     // ipm_wreg_pcpa.hip: ... of kWPA's kind
+extern const WVariants kWBD;       // ipm_wreg_bd.hip:   upper bounds, term tables
+extern const WVariants kWBDDA;     // ipm_wreg_bd.hip:   upper bounds, dense image
 
 struct WregPlan;   // host tables + device copies for one shared constraint matrix
 

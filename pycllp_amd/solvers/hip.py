@@ -50,7 +50,7 @@ def unpack(packed, layout, names=("pobj", "dobj", "status", "iters", "y", "x")):
 
 
 # pycllp_hip_sparse_launch_info's `kernel` -> (variant, kernel family): 'wave' = the register-resident one-LP-per-wavefront
-# kernel (csrc/ipm_wreg.hip) on Gram term tables or on a dense image of A, 'block' = the one-LP-per-workgroup kernel of
+# kernel (csrc/wreg_wave.h) on Gram term tables or on a dense image of A, 'block' = the one-LP-per-workgroup kernel of
 # csrc/ipm_block.inc (m <= 128), 'big' = the one-LP-per-workgroup kernel for large LPs (csrc/ipm_big.hip: 128 < m <= 256 or
 # 512 < n <= 1280), Gram from a term list or on the matrix cores
 SPARSE_KERNEL_KINDS = {0: ("block", "block"), 1: ("tables", "wave"), 2: ("dense image", "wave"),

@@ -1,4 +1,4 @@
-"""Bring-up checks of the register-resident wave kernel (csrc/ipm_wreg.hip) on a GPU: cross-lane primitives, the
+"""Bring-up checks of the register-resident wave kernel (csrc/wreg_wave.h) on a GPU: cross-lane primitives, the
 stand-alone register LDL' solve, the stand-alone sparse Newton step and the full solve against the oracle."""
 import ctypes, sys, os, time
 import numpy as np

@@ -1063,7 +1063,7 @@ def test_autoscale_on_badly_scaled_lps(kind):
     assert_same_results(d, off)
 
 
-# ---- register-resident wavefront-per-LP kernel of the sparse path (csrc/ipm_wreg.hip) ---------------------------------
+# ---- register-resident wavefront-per-LP kernel of the sparse path (csrc/wreg_wave.h) ----------------------------------
 
 def test_sparse_wave_and_block_kernels_agree():
     """The default (register-resident, one LP per wavefront) kernel and the workgroup-per-LP kernel (PYCLLP_FLAG_BLOCK_KERNEL)

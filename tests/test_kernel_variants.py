@@ -1,4 +1,4 @@
-"""Every compiled instantiation of the wavefront-per-LP kernel (csrc/ipm_wreg.hip; shape lists WREG_TAB_SHAPES and
+"""Every compiled instantiation of the wavefront-per-LP kernel (csrc/ipm_wreg_*.hip; shape lists WREG_TAB_SHAPES and
 WREG_DA_SHAPES of csrc/wreg.h) and of the lane-group kernels (GROUP_SHAPES of csrc/ipm_dense.hip) against the CPU references.
 
 Each shape is solved at two points of the region it serves first: FULL, its corner (every row and lane live), and RAGGED, one
@@ -126,7 +126,7 @@ def first_covering(family, shapes, m, N):
 
 
 def wave_doubles(mb, nq, bounded):
-    """LDS doubles of one wave's area (ipm_wreg.hip WGeo::WAVE_D, + t and s of the bounded kernel)."""
+    """LDS doubles of one wave's area (wreg.h WGeo::WAVE_D, + t and s of the bounded kernel)."""
     stage = max(192 * nq, 768) + 272
     return stage + 64 * nq + 5 * 16 * mb + 144 * mb + (2 * 64 * nq if bounded else 0)
 

@@ -7,8 +7,9 @@ name=$1; shift
 mkdir -p proflib
 C=pycllp_amd/csrc
 T=$(mktemp -d); trap 'rm -rf "$T"' EXIT
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -DWREG_PART=0 -DPYCLLP_DEV_ONLY_W86 "$@" -c -o $T/ipm_wreg.o $C/ipm_wreg.hip
-# the product's object list (the Makefile's), with the object rebuilt above in place of its own
-objs=$(for o in $(make -s --no-print-directory -C $C print-objs); do [ -f $T/${o##*/} ] && echo $T/${o##*/} || echo $o; done)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o proflib/$name.so $objs
+# the product's objects (the Makefile's list) next to the one rebuilt here: make finds them up to date and links
+make -s -C $C OUT=$T/ EXTRA="-DPYCLLP_DEV_ONLY_W86 $*" $T/ipm_wreg_tab.o
+for o in $(make -s --no-print-directory -C $C print-objs); do [ -f $T/${o##*/} ] || cp -p $o $T/; done
+make -s -C $C OUT=$T/
+cp $T/libpycllp_hip.so proflib/$name.so
 echo built proflib/$name.so

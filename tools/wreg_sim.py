@@ -1,4 +1,4 @@
-"""Lane-level numpy model of the register-resident LDL' / triangular solves of csrc/ipm_wreg.hip.
+"""Lane-level numpy model of the register-resident LDL' / triangular solves of csrc/wreg_wave.h.
 
 Design check, not product code: every "register" is a numpy array of 64 lane values and the cross-lane
 primitives (v_mfma_f64_16x16x4_f64, DPP row_newbcast, the quad reductions) are modelled with the lane maps the
