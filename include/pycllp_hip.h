@@ -168,6 +168,25 @@ int pycllp_hip_dense_solve_batch(pycllp_hip_dense *handle, long B, const double 
                                  double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
                                  const pycllp_hip_opts *opts, void *stream);
 
+/* Solve B LPs with UPPER BOUNDS that each have their OWN dense matrix: maximise c'x s.t. [A_k | I] x = b, 0 <= x <= u, the
+ * bounded equality form of a GeneralLP whose A has per-problem values, on the lane-group kernel that has both (the text of
+ * pycllp_hip_dense_solve_bounded's kernel on the per-slot matrix images of pycllp_hip_dense_solve_batch's).  The handle comes
+ * from pycllp_hip_dense_init with any one [A_k | I_m] of the batch: it fixes m, n and the identity tail (m <= 32, at most 96
+ * dense columns); its values are not read here.
+ *   A_dev [B, m, a_cols]  row-major, a_cols = n - m: the columns before the identity tail, which is implied and never stored
+ *   u_dev [B,n], s_dev [B,n], dobj_dev [B] = b'y + u's and the objectives at the iteration limit: as
+ *                         pycllp_hip_dense_solve_bounded; the other arguments as pycllp_hip_dense_solve
+ * Options: PYCLLP_FLAG_AUTOSCALE (u scales with b) and PYCLLP_FLAG_FORCE_GUARD_PATH apply.
+ * Returns PYCLLP_E_BADARG for a NULL u_dev, any of the flags HSD, PREDCORR, WARM_START, WAVE_KERNEL, NO_SLACK_PATH or an a_cols
+ * other than n - m, and PYCLLP_E_UNSUPPORTED when the handle has no slack-aware lane-group kernel; all before any HIP call.
+ * Uses the handle's launch-queue ring; pycllp_hip_dense_launch_info / _variant_info report the launch (slack = 1).
+ * Asynchronous on `stream`. */
+int pycllp_hip_dense_solve_batch_bounded(pycllp_hip_dense *handle, long B, const double *A_dev, long a_cols,
+                                         const double *b_dev, const double *c_dev, const double *u_dev,
+                                         double *x_dev, double *y_dev, double *z_dev, double *s_dev, double *pobj_dev,
+                                         double *dobj_dev, int *status_dev, int *iters_dev,
+                                         const pycllp_hip_opts *opts, void *stream);
+
 /* One Newton step of the primal normal equations for B independent states:
  *   dy <- solve( A diag(x/z) A' , -(b - A x - A diag(x/z) (c - A'y + mu/x)) )
  * x,z,c [B,n]; y,b,dy [B,m].  nrefine_dev [B] (optional) receives the refinement passes used. */

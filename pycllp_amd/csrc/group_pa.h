@@ -18,6 +18,8 @@ struct GeoPA {
     static_assert(FIT >= 1, "one wave must fit into the LDS of a CU");
     static_assert(AREA % 2 == 0 && PW % 2 == 0, "areas and slabs stay 16-byte aligned");
     static constexpr size_t lds_bytes(int wpb) { return sizeof(double) * (size_t)wpb * PW; }
+    // the waves of a kernel on these areas that must not exceed `cap` for another reason (ipm_bounded_pa_kernel: registers)
+    static constexpr int wpb_capped(int cap) { return WPB_MAX < cap ? WPB_MAX : cap; }
 };
 
 // One launch of ipm_group_pa_kernel<MP, NP, SL>: A [B, m, a_cols] row-major, a_cols = n - m (SL) or n; the outputs of
@@ -33,4 +35,18 @@ struct GroupPaVariant { int mp, np, sl; gpa_launch_fn launch; };
 struct GroupPaVariants { const GroupPaVariant* v; int n; };
 // every GROUP_SHAPES shape (ipm_dense.hip) with SL = 0 and SL = 1; matched by (mp, np, sl), never by position
 extern const GroupPaVariants kGroupPA;
+
+// One launch of ipm_bounded_pa_kernel<MP, NP> (ipm_group_pabd.hip): upper bounds on per-problem A.  A [B, m, n - m] row-major,
+// u [B, n]; the outputs of pycllp_hip_dense_solve_bounded.  Sets the kernel's dynamic LDS itself.
+struct GroupPaBdArgs {
+    int m, n; long B;
+    const double *A, *b, *c, *u;
+    double *x, *y, *z, *s, *pobj, *dobj;
+    int *status, *iters, *queue;
+};
+typedef hipError_t (*gpabd_launch_fn)(const GroupPaBdArgs&, int grid, int block, int lds, DevOpts, hipStream_t);
+struct GroupPaBdVariant { int mp, np; gpabd_launch_fn launch; };
+struct GroupPaBdVariants { const GroupPaBdVariant* v; int n; };
+// every GROUP_SHAPES shape (slack-aware only: the bounded equality form ends in the identity); matched by (mp, np)
+extern const GroupPaBdVariants kGroupPABD;
 #endif

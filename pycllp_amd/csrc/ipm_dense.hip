@@ -571,11 +571,12 @@ static LaunchPlan plan_group(const pycllp_hip_dense* h, long B, int wpb, const D
 // Launch plan of the lane-group kernel for per-problem dense A (ipm_group_slot.inc, compiled in ipm_group_pa.hip): nothing is
 // shared between waves there, every wave needs GeoPA::PW doubles (its G matrix areas + GeoG::WSZ), and one workgroup per CU
 // holds as many waves as the LDS takes -- at most GeoPA::WPB_MAX, what the kernel's launch bounds allow.  The small-batch rule
-// is plan_group's.
-template <int MP, int NP, bool SL>
+// is plan_group's.  CAP: the most waves per workgroup; ipm_bounded_pa_kernel (bounds on per-problem A) has fewer than WPB_MAX.
+template <int MP, int NP, bool SL, int CAP = GeoPA<GeoG<MP, NP, SL>>::WPB_MAX>
 static LaunchPlan plan_group_pa(const pycllp_hip_dense* h, long B, const DevOpts& o) {
     using P = GeoPA<GeoG<MP, NP, SL>>;
-    int wpb = P::WPB_MAX;
+    static_assert(CAP >= 1 && CAP <= P::WPB_MAX, "the cap lies within what the LDS takes");
+    int wpb = CAP;
     while (wpb > 1 && P::lds_bytes(wpb) > (size_t)h->max_lds) wpb--;
     const long resident = (long)h->num_cu - o.reserve_cus > 0 ? (long)h->num_cu - o.reserve_cus : 1;
     {
@@ -682,6 +683,11 @@ struct PaPlan { int mp, np, sl; pa_plan_fn plan; };
 #define PA_PLAN(MP, NP) { MP, NP, 0, plan_group_pa<MP, NP, false> }, { MP, NP, 1, plan_group_pa<MP, NP, true> },
 static const PaPlan kPaPlans[] = { GROUP_SHAPES(PA_PLAN) };
 static const int kNumPaPlans = sizeof(kPaPlans) / sizeof(kPaPlans[0]);
+// ... and of the kernel for upper bounds on per-problem dense A (kGroupPABD, matched by (mp, np)): the same rule, at most
+// PYCLLP_WPB_BOUNDED waves per workgroup
+#define PABD_PLAN(MP, NP) { MP, NP, 1, plan_group_pa<MP, NP, true, GeoPA<GeoG<MP, NP, true>>::wpb_capped(PYCLLP_WPB_BOUNDED)> },
+static const PaPlan kPaBdPlans[] = { GROUP_SHAPES(PABD_PLAN) };
+static const int kNumPaBdPlans = sizeof(kPaBdPlans) / sizeof(kPaBdPlans[0]);
 
 static unsigned long long* g_prof = nullptr;  // diagnostic build only
 #ifdef PYCLLP_PROFILE
@@ -960,6 +966,50 @@ int pycllp_hip_dense_solve_batch(pycllp_hip_dense* h, long B, const double* A_de
         return el;
     });
     if (e != hipSuccess) return set_err((int)e, "per-problem solve kernel launch");
+    return 0;
+}
+
+int pycllp_hip_dense_solve_batch_bounded(pycllp_hip_dense* h, long B, const double* A_dev, long a_cols, const double* b_dev,
+                                         const double* c_dev, const double* u_dev, double* x_dev, double* y_dev, double* z_dev,
+                                         double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
+                                         const pycllp_hip_opts* opts, void* stream) {
+    // every argument check comes before the handle is read and before any HIP call
+    if (!h || B < 0 || !u_dev) return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch_bounded: bad argument");
+    const int flags = opts ? opts->flags : 0;
+    const int bad = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL | PYCLLP_FLAG_NO_SLACK_PATH;
+    if (flags & bad)
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL and "
+                                        "NO_SLACK_PATH are not available with upper bounds on per-problem matrices");
+    if (B > 0 && (!A_dev || !b_dev || !c_dev || !x_dev || !status_dev))
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch_bounded: bad argument");
+    if (h->sp || h->variant_sl < 0)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch_bounded: A is not [A_dense | I] with m <= 32 and at most "
+                                             "96 dense columns (48 when m <= 16 on the 16-row kernels)");
+    if (a_cols != (long)(h->n - h->m)) {
+        snprintf(g_err, sizeof(g_err), "pycllp_hip_dense_solve_batch_bounded: a_cols = %ld, expected %d (the columns before the "
+                 "identity tail)", a_cols, h->n - h->m);
+        return PYCLLP_E_BADARG;
+    }
+    const int mp = kSlackVariants[h->variant_sl].mp, np = kSlackVariants[h->variant_sl].np;
+    const PaPlan* pp = nullptr;
+    const GroupPaBdVariant* pv = nullptr;
+    for (int i = 0; i < kNumPaBdPlans; i++)
+        if (kPaBdPlans[i].mp == mp && kPaBdPlans[i].np == np) pp = &kPaBdPlans[i];
+    for (int i = 0; i < kGroupPABD.n; i++)
+        if (kGroupPABD.v[i].mp == mp && kGroupPABD.v[i].np == np) pv = &kGroupPABD.v[i];
+    if (!pp || !pv) return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch_bounded: no kernel of this shape was compiled");
+    if (B == 0) return 0;
+    DevOpts o = to_dev(opts);
+    hipStream_t st = (hipStream_t)stream;
+    const LaunchPlan p = pp->plan(h, B, o);
+    const hipError_t e = h->ring.run(st, [&](int* qhead) {
+        const GroupPaBdArgs a = {h->m, h->n, B, A_dev, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
+                                 status_dev, iters_dev, qhead};
+        const hipError_t el = pv->launch(a, p.grid, p.block, p.lds, o, st);
+        publish(h, p);
+        return el;
+    });
+    if (e != hipSuccess) return set_err((int)e, "bounded per-problem solve kernel launch");
     return 0;
 }
 

@@ -1,8 +1,9 @@
-// ipm_group_slot.inc -- the two lane-group kernels (ipm_group.inc) that iterate in the simplified order.  They share ONE text of
-// the slot iteration, ipm_group_slot_body.inc, compiled under the constants SL, BD, PA:
+// ipm_group_slot.inc -- the three lane-group kernels (ipm_group.inc) that iterate in the simplified order.  They share ONE text
+// of the slot iteration, ipm_group_slot_body.inc, compiled under the constants SL, BD, PA:
 //   ipm_bounded_kernel<MP, NP>        SL = true, BD = true,  PA = false    LPs with UPPER BOUNDS on one shared A
 //   ipm_group_pa_kernel<MP, NP, SL>            BD = false, PA = true     EVERY LP HAS ITS OWN DENSE A
-// (BD && PA -- bounds on per-problem A -- is what this prepares; it is not instantiated.)  The text is included into each
+//   ipm_bounded_pa_kernel<MP, NP>     SL = true, BD = true,  PA = true     both (DESIGN.md section 17; ipm_group_pabd.hip)
+// The text is included into each
 // __global__, not called: behind a force-inlined function template the same text compiles to other instruction streams
 // (ipm_bounded_kernel<32, 96> then spills four VGPRs); included, the bounded kernels are what they were as a file of their own.
 //
@@ -61,5 +62,21 @@ ipm_group_pa_kernel(int m, int n, long B, const double* __restrict__ Ag, const d
                     int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue, DevOpts o) {
     constexpr bool BD = false, PA = true;
     const double* const ug = nullptr; double* const sg = nullptr;   // BD only
+#include "ipm_group_slot_body.inc"
+}
+
+// BD && PA: the union of the two above.  The bounded text needs the whole register file per lane, so never more than one wave
+// per SIMD (PYCLLP_WPB_BOUNDED), and fewer where the per-wave LDS (GeoPA::PW, as ipm_group_pa_kernel's) does not take four:
+// 4 / 4 / 4 / 4 / 3 / 2 waves per workgroup at the six shapes.  A refill needs neither u nor the other vectors of the LP (it
+// runs before they are loaded); a parked slot has u = 0, so none of its columns takes part and its image -- the last LP's
+// matrix, or zeros -- only ever meets d = 0.
+template <int MP, int NP>
+__global__ void __launch_bounds__((GeoPA<GeoG<MP, NP, true>>::wpb_capped(PYCLLP_WPB_BOUNDED) * 64))
+ipm_bounded_pa_kernel(int m, int n, long B, const double* __restrict__ Ag, const double* __restrict__ bg,
+                      const double* __restrict__ cg, const double* __restrict__ ug, double* __restrict__ xg,
+                      double* __restrict__ yg, double* __restrict__ zg, double* __restrict__ sg, double* __restrict__ pobj,
+                      double* __restrict__ dobj, int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue,
+                      DevOpts o) {
+    constexpr bool SL = true, BD = true, PA = true;
 #include "ipm_group_slot_body.inc"
 }

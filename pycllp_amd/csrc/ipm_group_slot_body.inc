@@ -1,5 +1,5 @@
-// ipm_group_slot_body.inc -- the text of one slot iteration, included into the body of ipm_bounded_kernel and of
-// ipm_group_pa_kernel (ipm_group_slot.inc, which has the algorithm notes).  It expects in scope: MP, NP and the constants SL,
+// ipm_group_slot_body.inc -- the text of one slot iteration, included into the body of ipm_bounded_kernel, of
+// ipm_group_pa_kernel and of ipm_bounded_pa_kernel (ipm_group_slot.inc, which has the algorithm notes).  It expects in scope: MP, NP and the constants SL,
 // BD (upper bounds: t, s, u), PA (per-slot A areas); the kernel arguments m, n, B, Ag, bg, cg, ug, xg, yg, zg, sg, pobj, dobj,
 // status, iters, queue, o (ug, sg: BD only).  Each phase is written once, in the form of the bounded algorithm (DESIGN.md
 // section 14); strike the BD parts and the plain step of ipm_group_kernel is left.

@@ -65,3 +65,4 @@ def register_with_pycllp():
 from .hip import HipDensePrimalNormalSolver, HipSparsePrimalNormalSolver  # noqa: E402,F401
 from .dense_batch import HipDenseBatchPrimalNormalSolver  # noqa: E402,F401
 from .general import HipGeneralPrimalNormalSolver, HipSparseGeneralPrimalNormalSolver  # noqa: E402,F401
+from .general_batch import HipGeneralBatchPrimalNormalSolver  # noqa: E402,F401

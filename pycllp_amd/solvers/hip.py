@@ -199,6 +199,14 @@ class Handle(object):
         self._call("solve_batch", self, int(b.shape[0]), A, ctypes.c_long(int(A.shape[2])), b, c, *(out[k] for k in RESULTS),
                    ctypes.byref(o), self._stream(stream))
 
+    def solve_batch_bounded(self, stream, A, b, c, u, out, o):
+        """B LPs with their own dense matrices A [B, m, n - m] (dense family, a handle whose tail is the identity) and the upper
+        bounds u [B, n] into ``out`` (x, y, z, s, pobj, dobj, status, iters)."""
+        if A.dim() != 3 or A.shape[0] != b.shape[0] or not A.is_contiguous():
+            raise ValueError("A must be a contiguous [B, m, a_cols] tensor with the B of b; got %r" % (tuple(A.shape),))
+        self._call("solve_batch_bounded", self, int(b.shape[0]), A, ctypes.c_long(int(A.shape[2])), b, c, u,
+                   *(out[k] for k in ("x", "y", "z", "s", "pobj", "dobj", "status", "iters")), ctypes.byref(o), self._stream(stream))
+
     def newton(self, stream, x, z, y, b, c, mu, dy, nrefine, o):
         self._call("newton", self, int(x.shape[0]), x, z, y, b, c, float(mu), dy, nrefine, ctypes.byref(o), self._stream(stream))
 
