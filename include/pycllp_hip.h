@@ -276,6 +276,22 @@ int pycllp_hip_sparse_solve_bounded(pycllp_hip_sparse *handle, long B, const dou
                                     const double *u_dev, double *x_dev, double *y_dev, double *z_dev, double *s_dev,
                                     double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
                                     const pycllp_hip_opts *opts, void *stream);
+/* The bounded solve with PER-PROBLEM VALUES of A on the shared structure: the union of pycllp_hip_sparse_solve_batch and
+ * pycllp_hip_sparse_solve_bounded, on the same kernel text compiled for per-problem values (csrc/ipm_wreg_bdpa.hip).
+ *   Adata_dev [B, nnz]   the values of LP k in the CSR order of the arrays given to pycllp_hip_sparse_init (whose values only
+ *                        fixed the structure); the ones of slack columns are among them, as the sparse path stores them
+ * u, s, dobj = b'y + u's, the objectives at the iteration limit and PYCLLP_FLAG_AUTOSCALE mean what they mean for
+ * pycllp_hip_sparse_solve_bounded.  An LP whose LDL' would need the Nocedal-Wright guard ends PYCLLP_STATUS_NUMERICAL.  The
+ * kernel's plan (structure tables; every wavefront keeps its LP's values, t and s behind its area, 1 to 4 wavefronts per
+ * workgroup as the LDS takes) is built on the first call and kept with the handle.
+ * Returns PYCLLP_E_BADARG for a NULL handle, Adata_dev or u_dev, B < 0, or any of the flags HSD, PREDCORR, WARM_START,
+ * WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH, FORCE_GUARD_PATH (before the handle is read and before any HIP call), and
+ * PYCLLP_E_UNSUPPORTED for a handle of the large-LP kernel (m > 128 or n > 512) or when no variant or LDS plan covers the
+ * structure.  Asynchronous on `stream`. */
+int pycllp_hip_sparse_solve_batch_bounded(pycllp_hip_sparse *handle, long B, const double *Adata_dev, const double *b_dev,
+                                          const double *c_dev, const double *u_dev, double *x_dev, double *y_dev,
+                                          double *z_dev, double *s_dev, double *pobj_dev, double *dobj_dev, int *status_dev,
+                                          int *iters_dev, const pycllp_hip_opts *opts, void *stream);
 /* One Newton step of the primal normal equations for B independent states with the sparse shared A: the reference's
  * stand-alone kernel sparse_solve_primal_normal (pycllp/cl/ldl.cl:656-712) as launched by its tests/test_ldl.py:276-361.
  * Arguments as pycllp_hip_dense_newton. */

@@ -57,6 +57,7 @@ SIGNATURES = (
     ("pycllp_hip_sparse_solve", _solve(9), _i),
     ("pycllp_hip_sparse_solve_batch", _solve(10), _i),          # A's values first
     ("pycllp_hip_sparse_solve_bounded", _solve(11), _i),
+    ("pycllp_hip_sparse_solve_batch_bounded", _solve(12), _i),  # A's values first, then as solve_bounded
     ("pycllp_hip_sparse_newton", [_p, _l, _p, _p, _p, _p, _p, _d, _p, _p, _O, _p], _i),
     ("pycllp_hip_sparse_launch_info", [_p] + [_ip] * 4, _i), ("pycllp_hip_sparse_variant_info", [_p] + [_ip] * 2, _i),
     ("pycllp_hip_sparse_plan_info", [_p] + [_ip] * 4, _i),

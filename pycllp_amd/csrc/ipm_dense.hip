@@ -726,6 +726,8 @@ struct pycllp_hip_sparse {
     bool wreg_pa_tried = false;
     WregPlan* wreg_bd = nullptr;  // the plan of the bounded wave kernel (t and s behind every wave area), built by the first
     bool wreg_bd_tried = false;   // pycllp_hip_sparse_solve_bounded (under info_mu)
+    WregPlan* wreg_bdpa = nullptr;   // the plan of the bounded wave kernel on per-problem values (structure tables; the LP's values, t
+    bool wreg_bdpa_tried = false;    // and s behind every wave area), built by the first pycllp_hip_sparse_solve_batch_bounded
     int max_lds = 0;
     std::vector<double> host_val; std::vector<int> host_ptr, host_col;   // host CSR copy (what a PA plan is built from)
 };
@@ -1371,11 +1373,49 @@ int pycllp_hip_sparse_solve_bounded(pycllp_hip_sparse* h, long B, const double* 
     DevOpts o = to_dev(opts);
     int grid = 0;
     const hipError_t e = h->ring.run(st, [&](int* qw) {
-        return wreg_launch_solve_bounded(plan, B, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev, status_dev,
+        return wreg_launch_solve_bounded(plan, B, nullptr, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev, status_dev,
                                          iters_dev, qw, o, h->num_cu, st, &grid);
     });
     record_launch(h, plan, grid);
     if (e != hipSuccess) return set_err((int)e, "ipm_wreg_bounded_kernel launch");
+    return 0;
+}
+
+int pycllp_hip_sparse_solve_batch_bounded(pycllp_hip_sparse* h, long B, const double* Adata_dev, const double* b_dev,
+                                          const double* c_dev, const double* u_dev, double* x_dev, double* y_dev, double* z_dev,
+                                          double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
+                                          const pycllp_hip_opts* opts, void* stream) {
+    // every argument check comes before the handle is read and before any HIP call
+    if (!h || B < 0 || !Adata_dev || !u_dev) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_batch_bounded: bad argument");
+    const int flags = opts ? opts->flags : 0;
+    const int bad = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL | PYCLLP_FLAG_BLOCK_KERNEL |
+                    PYCLLP_FLAG_NO_SLACK_PATH | PYCLLP_FLAG_FORCE_GUARD_PATH;
+    if (flags & bad)
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_batch_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, "
+                                        "NO_SLACK_PATH and FORCE_GUARD_PATH are not available with upper bounds on per-problem matrices");
+    if (B > 0 && (!b_dev || !c_dev || !x_dev || !status_dev))
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_batch_bounded: bad argument");
+    if (h->big)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_batch_bounded: the bounded wave kernel stops at m = 128, n = 512");
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = lazy_plan(h, &h->wreg_bdpa, &h->wreg_bdpa_tried, "wreg_plan_create_bounded_pa", [&](WregPlan** wp) {
+        return wreg_plan_create_bounded_pa(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(),
+                                           h->host_col.data(), h->max_lds, st, wp);
+    });
+    if (rc != 0) return rc;
+    WregPlan* plan = h->wreg_bdpa;
+    if (!plan)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_batch_bounded: no variant of the bounded wave kernel covers this "
+                                             "structure on per-problem values (rows, columns, or its tables in LDS)");
+    if (B == 0) return 0;
+    DevOpts o = to_dev(opts);
+    int grid = 0;
+    const hipError_t e = h->ring.run(st, [&](int* qw) {
+        return wreg_launch_solve_bounded(plan, B, Adata_dev, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
+                                         status_dev, iters_dev, qw, o, h->num_cu, st, &grid);
+    });
+    record_launch(h, plan, grid);
+    if (e != hipSuccess) return set_err((int)e, "ipm_wreg_bounded_pa_kernel launch");
     return 0;
 }
 
@@ -1503,6 +1543,7 @@ void pycllp_hip_sparse_free(pycllp_hip_sparse* h) {
     wreg_plan_free(h->wreg);
     wreg_plan_free(h->wreg_pa);
     wreg_plan_free(h->wreg_bd);
+    wreg_plan_free(h->wreg_bdpa);
     big_plan_free(h->big);
     delete h;
 }

@@ -1,6 +1,6 @@
 // ipm_wreg.hip -- host side of the register-resident one-LP-per-wavefront kernels (wreg_wave.h): the plan of one constraint
 // matrix (term tables or dense image, LDS layout), the choice of a launcher from the tables of the kernel units
-// (ipm_wreg_{tab,da,pa,pc,pcda,pcpa,bd}.hip), grid sizing and the wreg_launch_* entry points of wreg.h.  The only kernels
+// (ipm_wreg_{tab,da,pa,pc,pcda,pcpa,bd,bdpa}.hip), grid sizing and the wreg_launch_* entry points of wreg.h.  The only kernels
 // compiled here are the two that have no table: the stand-alone LDL' solve and the selftest of the cross-lane primitives.
 #include "wreg_wave.h"
 
@@ -103,7 +103,7 @@ size_t put(std::vector<char>& host, const std::vector<T>& v) {
 
 // the launcher table of a plan's kind; pc: its predictor-corrector kernels (plans of the bounded kernel have none)
 static const WVariants& table_of(bool da, bool pa, bool bd, bool pc = false) {
-    if (bd) return da ? kWBDDA : kWBD;
+    if (bd) return pa ? kWBDPA : (da ? kWBDDA : kWBD);
     if (pc) return pa ? kWPCPA : (da ? kWPCDA : kWPC);
     return pa ? kWPA : (da ? kWDA : kWTab);
 }
@@ -175,6 +175,11 @@ int wreg_plan_create_bounded(int m, int n, int nnz, const double* val, const int
     const int rc = wreg_plan_create_tables(m, n, nnz, val, ptr, col, max_lds, false, true, st, out);
     if (rc != 1) return rc;
     return wreg_plan_create_dense(m, n, nnz, val, ptr, col, max_lds, true, st, out);
+}
+
+int wreg_plan_create_bounded_pa(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
+                                hipStream_t st, WregPlan** out) {
+    return wreg_plan_create_tables(m, n, nnz, val, ptr, col, max_lds, true, true, st, out);
 }
 
 // pa: the structure-only tables of the per-problem-A variants (the values `val` only stand in where a table still wants
@@ -414,13 +419,14 @@ hipError_t wreg_launch_solve(WregPlan* p, long B, const double* a_batch, const d
     return fn(p->tab, B, a_batch, b, c, x, y, z, pobj, dobj, status, iters, qhead, defer, o, grid, st);
 }
 
-hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* b, const double* c, const double* u, double* x, double* y,
+hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* a_batch, const double* b, const double* c, const double* u, double* x, double* y,
                                      double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead,
                                      DevOpts o, int num_cu, hipStream_t st, int* grid_out) {
     const WVariant* v = plan_launchers(p, true);
-    if (!v) return hipErrorInvalidValue;
+    if (!v || (p->pa != (a_batch != nullptr))) return hipErrorInvalidValue;
     const int grid = solve_grid(p, B, o, num_cu);
     if (grid_out) *grid_out = grid;
+    if (a_batch) return v->solve_bounded_pa(p->tab, B, a_batch, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o, grid, st);
     return v->solve_bounded(p->tab, B, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o, grid, st);
 }
 

@@ -1,7 +1,7 @@
 // ipm_wreg_bounded.inc -- the register-resident one-LP-per-wavefront kernel (ipm_wreg_kernel) for LPs with UPPER BOUNDS:
 //   maximise c'x  subject to  A x = b,  0 <= x <= u        (u_j = +inf: no bound;  u_j = 0: the column is fixed at 0)
 // the bounded equality form of a GeneralLP (pycllp_amd/lp.py, GeneralLP.to_bounded_equality_form), any shared A.  On
-// wreg_wave.h; compiled by ipm_wreg_bd.hip.  The step is the one of ipm_group_slot.inc (DESIGN.md
+// wreg_wave.h; compiled by ipm_wreg_bd.hip and ipm_wreg_bdpa.hip.  The step is the one of ipm_group_slot.inc (DESIGN.md
 // sections 14 and 15; tests/bounded_twin.py restates it):
 //   d = 1 / (z/x + s/t),  t~ = c - A'y + mu/x - mu/t + (s/t) tau,  tau = u - x - t,  mu = delta gamma / (n + m + N_b)
 //   M dy = A (d t~) - rho,  dx = d (t~ - A'dy),  dz = (mu - z dx)/x - z,  dt = tau - dx,  ds = (mu - s dt)/t - s
@@ -19,9 +19,30 @@
 //   * a verdict reached inside an iteration (NUMERICAL, ITERATION_LIMIT) is stored at the top of the next pass, where the
 //     point's A'y is at hand for the duals of the fixed columns; the point itself is the one the verdict was reached on.
 // No warm start, no predictor-corrector, no HSD.
+// The text serves two units: ipm_wreg_bd.hip (ipm_wreg_bounded_kernel, a shared A) and ipm_wreg_bdpa.hip
+// (ipm_wreg_bounded_pa_kernel, per-problem values of A on structure tables; DESIGN.md section 18).
 
 namespace {
 
+// PYCLLP_WREG_BOUNDED_PA (defined by ipm_wreg_bdpa.hip in front of this text): per-problem values of A on structure-only
+// tables, WReg<MB, NQ, false, true>; the kernel is then ipm_wreg_bounded_pa_kernel<MB, NQ> and takes ag [B, nnz] in the plan's
+// CSR order.  The wave's copy of its LP's values sits where t and s sit otherwise (cvl_() = W0 + WAVE_D), so t and s go BEHIND
+// it, at the wave-uniform run-time offset WAVE_D + nnzp (nnzp is even: 16-byte alignment stays).  A preprocessor switch, not a
+// template argument: the kernel's signature differs, and the shared-A kernels stay instruction for instruction what they were.
+#ifdef PYCLLP_WREG_BOUNDED_PA
+template <int MB, int NQ>
+__global__ void __launch_bounds__(256, 1)
+ipm_wreg_bounded_pa_kernel(WregTab T, long B, const double* __restrict__ ag, const double* __restrict__ bg,
+                           const double* __restrict__ cg, const double* __restrict__ ug, double* __restrict__ xg,
+                           double* __restrict__ yg, double* __restrict__ zg, double* __restrict__ sg, double* __restrict__ pobj,
+                           double* __restrict__ dobj, int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue,
+                           DevOpts o) {
+    using G = WGeo<MB>;
+    constexpr int MR = G::MR, MP = G::MP, NP = 64 * NQ;
+    const int TS = G::WAVE_D(NQ) + T.nnzp;                                    // t at W0[TS, TS + NP), s behind it
+    extern __shared__ __attribute__((aligned(16))) unsigned char lraw[];
+    WReg<MB, NQ, false, true> w;
+#else
 template <int MB, int NQ, bool DA>
 __global__ void __launch_bounds__(256, 1)
 ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const double* __restrict__ cg,
@@ -32,6 +53,7 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
     constexpr int MR = G::MR, MP = G::MP, NP = 64 * NQ, TS = G::WAVE_D(NQ);   // t at W0[TS, TS + NP), s behind it
     extern __shared__ __attribute__((aligned(16))) unsigned char lraw[];
     WReg<MB, NQ, DA> w;
+#endif
     USE_AGPR_FORM();
     wreg_setup(w, T, lraw, threadIdx.x);
     const int& lane = w.lane;
@@ -44,6 +66,9 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
     long lp = next_item(queue, lane);
     STAMP_DECL
     while (lp < B) {
+#ifdef PYCLLP_WREG_BOUNDED_PA
+        load_lp_values(w, ag, lp, T.nnz);      // before anything reads A
+#endif
         // padded positions read u = 0 (buffer offset past the row): they take no part, like a fixed column
         const __amdgpu_buffer_rsrc_t rc = row_rsrc(cg + lp * n, n), ru = row_rsrc(ug + lp * n, n);
         // PYCLLP_FLAG_AUTOSCALE: b, u / max|b| and c / max|c| over the columns that take part (as the lane-group kernel)

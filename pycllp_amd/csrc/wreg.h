@@ -5,7 +5,7 @@
 #define PYCLLP_WREG_H
 #include "wave_common.h"
 
-// ---- shared between the host unit (ipm_wreg.hip) and the seven units the wave kernels are compiled in (ipm_wreg_*.hip) ----
+// ---- shared between the host unit (ipm_wreg.hip) and the eight units the wave kernels are compiled in (ipm_wreg_*.hip) ----
 constexpr int MAX_NQ = 8;
 constexpr int META_COFF = MAX_NQ, META_SEG = 2 * MAX_NQ, META_N = META_SEG + 16;
 
@@ -78,6 +78,9 @@ typedef hipError_t (*wnewton_fn)(const WregTab&, long, const double*, const doub
 // the kernel for LPs with upper bounds (ipm_wreg_bounded.inc): argument meaning of pycllp_hip_sparse_solve_bounded
 typedef hipError_t (*wbsolve_fn)(const WregTab&, long, const double*, const double*, const double*, double*, double*, double*,
                                  double*, double*, double*, int*, int*, int*, DevOpts, int, hipStream_t);
+// ... on per-problem values of A: a_batch [B, nnz] in front of b (argument meaning of pycllp_hip_sparse_solve_batch_bounded)
+typedef hipError_t (*wbpsolve_fn)(const WregTab&, long, const double*, const double*, const double*, const double*, double*,
+                                  double*, double*, double*, double*, double*, int*, int*, int*, DevOpts, int, hipStream_t);
 
 // The (MB, NQ) geometries of the wave kernels (MB 16-row blocks, NQ 64-column N-vector registers), ordered by cost: a plan
 // takes the first of its kind with 16 MB >= m and 64 NQ >= n.  One list for the kernels on term tables, one for those on a
@@ -86,7 +89,7 @@ typedef hipError_t (*wbsolve_fn)(const WregTab&, long, const double*, const doub
 #define WREG_DA_SHAPES(X)  X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4) X(8, 6)
 
 // The launchers of one (MB, NQ) of one kernel kind; a launcher the kind does not have is null.
-struct WVariant { int mb, nq; wsolve_fn solve, solve_hsd; wnewton_fn newton; wbsolve_fn solve_bounded; };
+struct WVariant { int mb, nq; wsolve_fn solve, solve_hsd; wnewton_fn newton; wbsolve_fn solve_bounded; wbpsolve_fn solve_bounded_pa; };
 struct WVariants { const WVariant* v; int n; };
 // One table per kind, each defined by the translation unit that compiles its kernels; launchers are matched across tables
 // by (MB, NQ), never by position.
@@ -98,6 +101,7 @@ extern const WVariants kWPCDA;     // ipm_wreg_pcda.hip: ... of kWDA's kind
 extern const WVariants kWPCPA;     // ipm_wreg_pcpa.hip: ... of kWPA's kind
 extern const WVariants kWBD;       // ipm_wreg_bd.hip:   upper bounds, term tables
 extern const WVariants kWBDDA;     // ipm_wreg_bd.hip:   upper bounds, dense image
+extern const WVariants kWBDPA;     // ipm_wreg_bdpa.hip: upper bounds, per-problem A on structure tables
 
 struct WregPlan;   // host tables + device copies for one shared constraint matrix
 
@@ -112,6 +116,11 @@ int wreg_plan_create(int m, int n, int nnz, const double* val, const int* ptr, c
 // covers A.
 int wreg_plan_create_bounded(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
                              hipStream_t st, WregPlan** out);
+// The plan of the bounded kernel on per-problem values of A: structure-only tables with nnzp + 2 NP doubles behind every wave
+// area (the LP's values, then t and s), as many waves per workgroup (4 at most, 1 at least) as the LDS takes.  Returns 1 when
+// no variant covers (m, n), when nnz >= 65535 or when not even one wave fits.  `val` is not read.
+int wreg_plan_create_bounded_pa(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
+                                hipStream_t st, WregPlan** out);
 void wreg_plan_free(WregPlan* p);
 
 // Solve B LPs (same argument meaning as pycllp_hip_sparse_solve).  LPs whose factorisation would have needed the
@@ -124,7 +133,8 @@ hipError_t wreg_launch_solve(WregPlan* p, long B, const double* a_batch, const d
 
 // Solve B LPs with upper bounds on a plan of wreg_plan_create_bounded (argument meaning of pycllp_hip_sparse_solve_bounded).
 // An LP whose factorisation would have needed the Nocedal-Wright guard ends PYCLLP_STATUS_NUMERICAL.
-hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* b, const double* c, const double* u, double* x, double* y,
+// a_batch: [B, nnz] values of every LP in the plan's CSR order, on a plan of wreg_plan_create_bounded_pa only (else null).
+hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* a_batch, const double* b, const double* c, const double* u, double* x, double* y,
                                      double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead,
                                      DevOpts o, int num_cu, hipStream_t st, int* grid_out);
 

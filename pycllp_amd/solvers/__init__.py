@@ -66,3 +66,4 @@ from .hip import HipDensePrimalNormalSolver, HipSparsePrimalNormalSolver  # noqa
 from .dense_batch import HipDenseBatchPrimalNormalSolver  # noqa: E402,F401
 from .general import HipGeneralPrimalNormalSolver, HipSparseGeneralPrimalNormalSolver  # noqa: E402,F401
 from .general_batch import HipGeneralBatchPrimalNormalSolver  # noqa: E402,F401
+from .sparse_general_batch import HipSparseGeneralBatchPrimalNormalSolver  # noqa: E402,F401

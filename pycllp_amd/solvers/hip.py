@@ -186,9 +186,11 @@ class Handle(object):
         entry, lead = ("solve", ()) if values is None else ("solve_batch", (values,))
         self._call(entry, self, int(b.shape[0]), *lead, b, c, *(out[k] for k in RESULTS), ctypes.byref(o), self._stream(stream))
 
-    def solve_bounded(self, stream, b, c, u, out, o):
-        """B LPs with the upper bounds u [B, n] into ``out`` (x, y, z, s, pobj, dobj, status, iters)."""
-        self._call("solve_bounded", self, int(b.shape[0]), b, c, u,
+    def solve_bounded(self, stream, b, c, u, out, o, values=None):
+        """B LPs with the upper bounds u [B, n] into ``out`` (x, y, z, s, pobj, dobj, status, iters).  ``values`` [B, nnz]:
+        per-problem values of A in the CSR order of the handle's matrix (sparse family)."""
+        entry, lead = ("solve_bounded", ()) if values is None else ("solve_batch_bounded", (values,))
+        self._call(entry, self, int(b.shape[0]), *lead, b, c, u,
                    *(out[k] for k in ("x", "y", "z", "s", "pobj", "dobj", "status", "iters")), ctypes.byref(o), self._stream(stream))
 
     def solve_batch_dense(self, stream, A, b, c, out, o):
