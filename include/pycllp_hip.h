@@ -10,6 +10,23 @@
  * buffers apart).  A handle keeps 64 device work-queue counters; when 64 launches of one handle are still in flight
  * the next call waits on the host for the oldest of them (the only place a solve entry may block).
  * *_launch_info and *_variant_info report the plan of the LAST launch on the handle.
+ *
+ * Alignment: a device array needs only the natural alignment of its element type -- 8 bytes for double, 4 for int.  No kernel
+ * reads or writes a caller's array through a wider vector type, so an array may start anywhere such an element may (a
+ * double array at an address = 8 mod 16, an int array at one = 4 mod 8), e.g. inside a packed allocation of the caller's.
+ *
+ * Footprint: an entry reads its input arrays and writes its output arrays, element [0] to the last element of the shapes given
+ * below, and no other byte of the caller's memory -- no padded row or column of a kernel reaches memory.  An optional output
+ * passed as NULL is not written and costs nothing; an input array is never written.  Outputs per status: every LP of a solve
+ * entry gets ALL of x, y, z (s), pobj, dobj, status and iters written, whatever its status (OPTIMAL, PRIMAL_INFEASIBLE,
+ * NUMERICAL, DUAL_INFEASIBLE, ITERATION_LIMIT): for a status other than OPTIMAL they hold the last iterate (with
+ * PYCLLP_FLAG_HSD and status 2 / 4: the certificate) and its objectives.  A Newton entry writes dy and nrefine of every state.
+ * ONE EXCEPTION: pycllp_hip_sparse_solve_batch on a structure whose per-problem values only the wavefront-per-LP kernel serves
+ * (A's arrays beside the packed factor do not fit the block kernel's 160 KB of LDS, e.g. m = 128, n = 512 from 3 324
+ * non-zeros on).  An LP whose LDL' would need the Nocedal-Wright guard there -- every LP with PYCLLP_FLAG_FORCE_GUARD_PATH --
+ * has no guarded kernel to go to: it ends PYCLLP_STATUS_NUMERICAL and its status is ALL that is written; its x, y, z, pobj,
+ * dobj and iters keep what the caller's arrays held.  Read them only where status != PYCLLP_STATUS_NUMERICAL on that entry.
+ * A call that returns a negative PYCLLP_E_* code has written nothing.  tests/test_memory_footprint.py pins all of this.
  * Return value: 0 on success, a negative PYCLLP_E_* code for argument errors, or a positive
  * hipError_t for runtime failures (pycllp_hip_last_error() gives the text).
  *
