@@ -1,5 +1,6 @@
-// group_pa.h -- internal interface between ipm_dense.hip (C ABI, handles, launch plans) and ipm_group_pa.hip, the translation
-// unit of the lane-group kernel for per-problem dense A (ipm_group_slot.inc).  Not part of the public ABI.
+// group_pa.h -- internal interface between ipm_dense.hip (C ABI, handles, launch plans) and ipm_group_pa.hip / ipm_group_pabd.hip,
+// the translation units of the lane-group kernels for per-problem dense A (ipm_group_slot.inc), and the home of GROUP_SHAPES,
+// the shape list of all three.  Not part of the public ABI.
 #ifndef PYCLLP_GROUP_PA_H
 #define PYCLLP_GROUP_PA_H
 #include "wave_common.h"
@@ -22,31 +23,31 @@ struct GeoPA {
     static constexpr int wpb_capped(int cap) { return WPB_MAX < cap ? WPB_MAX : cap; }
 };
 
-// One launch of ipm_group_pa_kernel<MP, NP, SL>: A [B, m, a_cols] row-major, a_cols = n - m (SL) or n; the outputs of
-// pycllp_hip_dense_solve; queue: a zeroed work-queue head.  Sets the kernel's dynamic LDS itself.
-struct GroupPaArgs {
-    int m, n; long B;
-    const double *A, *b, *c;
-    double *x, *y, *z, *pobj, *dobj;
-    int *status, *iters, *queue;
-};
-typedef hipError_t (*gpa_launch_fn)(const GroupPaArgs&, int grid, int block, int lds, DevOpts, hipStream_t);
-struct GroupPaVariant { int mp, np, sl; gpa_launch_fn launch; };
-struct GroupPaVariants { const GroupPaVariant* v; int n; };
-// every GROUP_SHAPES shape (ipm_dense.hip) with SL = 0 and SL = 1; matched by (mp, np, sl), never by position
-extern const GroupPaVariants kGroupPA;
+// the lane-group shapes (MP, NP), ordered by cost: the first that covers (m, n) is used, in every table of ipm_dense.hip,
+// ipm_group_pa.hip and ipm_group_pabd.hip (the one list; tests/test_kernel_variants.py compares it with the Python side's)
+#if defined(PYCLLP_DEV_ONLY_3296)   // development builds (tools/ab_*.sh): only the headline shape, compiles in a fraction of the time
+#define GROUP_SHAPES(X) X(32, 96)
+#elif defined(PYCLLP_DEV_ONLY_1648)
+#define GROUP_SHAPES(X) X(16, 48)
+#else
+#define GROUP_SHAPES(X) X(16, 32) X(16, 48) X(16, 64) X(32, 64) X(32, 96) X(32, 128)
+#endif
 
-// One launch of ipm_bounded_pa_kernel<MP, NP> (ipm_group_pabd.hip): upper bounds on per-problem A.  A [B, m, n - m] row-major,
-// u [B, n]; the outputs of pycllp_hip_dense_solve_bounded.  Sets the kernel's dynamic LDS itself.
-struct GroupPaBdArgs {
+// One launch of ipm_group_pa_kernel<MP, NP, SL> (ipm_group_pa.hip) or, with upper bounds, of ipm_bounded_pa_kernel<MP, NP>
+// (ipm_group_pabd.hip): A [B, m, a_cols] row-major, a_cols = n - m (SL) or n; u [B, n] and s: null without bounds; the outputs
+// of pycllp_hip_dense_solve / pycllp_hip_dense_solve_bounded; queue: a zeroed work-queue head.  Sets the kernel's dynamic LDS
+// itself.
+struct GroupPaArgs {
     int m, n; long B;
     const double *A, *b, *c, *u;
     double *x, *y, *z, *s, *pobj, *dobj;
     int *status, *iters, *queue;
 };
-typedef hipError_t (*gpabd_launch_fn)(const GroupPaBdArgs&, int grid, int block, int lds, DevOpts, hipStream_t);
-struct GroupPaBdVariant { int mp, np; gpabd_launch_fn launch; };
-struct GroupPaBdVariants { const GroupPaBdVariant* v; int n; };
-// every GROUP_SHAPES shape (slack-aware only: the bounded equality form ends in the identity); matched by (mp, np)
-extern const GroupPaBdVariants kGroupPABD;
+typedef hipError_t (*gpa_launch_fn)(const GroupPaArgs&, int grid, int block, int lds, DevOpts, hipStream_t);
+struct GroupPaVariant { int mp, np, sl; gpa_launch_fn launch; };
+struct GroupPaVariants { const GroupPaVariant* v; int n; };
+// every GROUP_SHAPES shape with SL = 0 and SL = 1; matched by (mp, np, sl), never by position
+extern const GroupPaVariants kGroupPA;
+// ... and with upper bounds: every GROUP_SHAPES shape, slack-aware only (sl = 1: the bounded equality form ends in the identity)
+extern const GroupPaVariants kGroupPABD;
 #endif

@@ -664,30 +664,31 @@ struct SlackVariant { int mp, np; solve_launch_fn solve_group, solve_hsd, solve_
 #define SLACK_VARIANT(MP, NP) { MP, NP, launch_solve_group<MP, NP, true>, launch_solve_group<MP, NP, true, true>, \
                                 launch_solve_group<MP, NP, true, false, true>, launch_solve_bounded<MP, NP> },
 
-// the lane-group shapes (MP, NP), ordered by cost: the first that covers (m, n) is used, in both tables
-#if defined(PYCLLP_DEV_ONLY_3296)   // development builds (tools/ab_*.sh): only the headline shape, compiles in a fraction of the time
-#define GROUP_SHAPES(X) X(32, 96)
-#elif defined(PYCLLP_DEV_ONLY_1648)
-#define GROUP_SHAPES(X) X(16, 48)
-#else
-#define GROUP_SHAPES(X) X(16, 32) X(16, 48) X(16, 64) X(32, 64) X(32, 96) X(32, 128)
-#endif
+// one row per lane-group shape of GROUP_SHAPES (group_pa.h), in its order: the first that covers (m, n) is used, in both tables
 static const Variant kVariants[] = { GROUP_SHAPES(VARIANT) };
 static const int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 static const SlackVariant kSlackVariants[] = { GROUP_SHAPES(SLACK_VARIANT) };
 static const int kNumSlackVariants = sizeof(kSlackVariants) / sizeof(kSlackVariants[0]);
 
-// launch plans of the kernel for per-problem dense A; its launchers are kGroupPA's (group_pa.h), matched by (mp, np, sl)
+// launch plans of the kernels for per-problem dense A; their launchers are kGroupPA's and kGroupPABD's (group_pa.h)
 typedef LaunchPlan (*pa_plan_fn)(const pycllp_hip_dense*, long, const DevOpts&);
 struct PaPlan { int mp, np, sl; pa_plan_fn plan; };
+struct PaPlans { const PaPlan* v; int n; };
 #define PA_PLAN(MP, NP) { MP, NP, 0, plan_group_pa<MP, NP, false> }, { MP, NP, 1, plan_group_pa<MP, NP, true> },
-static const PaPlan kPaPlans[] = { GROUP_SHAPES(PA_PLAN) };
-static const int kNumPaPlans = sizeof(kPaPlans) / sizeof(kPaPlans[0]);
-// ... and of the kernel for upper bounds on per-problem dense A (kGroupPABD, matched by (mp, np)): the same rule, at most
-// PYCLLP_WPB_BOUNDED waves per workgroup
+static const PaPlan kPaPlans_v[] = { GROUP_SHAPES(PA_PLAN) };
+static const PaPlans kPaPlans = { kPaPlans_v, (int)(sizeof(kPaPlans_v) / sizeof(kPaPlans_v[0])) };
+// ... and with upper bounds: the same rule, at most PYCLLP_WPB_BOUNDED waves per workgroup
 #define PABD_PLAN(MP, NP) { MP, NP, 1, plan_group_pa<MP, NP, true, GeoPA<GeoG<MP, NP, true>>::wpb_capped(PYCLLP_WPB_BOUNDED)> },
-static const PaPlan kPaBdPlans[] = { GROUP_SHAPES(PABD_PLAN) };
-static const int kNumPaBdPlans = sizeof(kPaBdPlans) / sizeof(kPaBdPlans[0]);
+static const PaPlan kPaBdPlans_v[] = { GROUP_SHAPES(PABD_PLAN) };
+static const PaPlans kPaBdPlans = { kPaBdPlans_v, (int)(sizeof(kPaBdPlans_v) / sizeof(kPaBdPlans_v[0])) };
+
+// the row of a per-problem-A table (PaPlans, GroupPaVariants) for (mp, np, sl) -- never by position --, or null
+template <typename Table>
+static auto find_pa(const Table& t, int mp, int np, bool sl) -> decltype(t.v) {
+    for (int i = 0; i < t.n; i++)
+        if (t.v[i].mp == mp && t.v[i].np == np && t.v[i].sl == (sl ? 1 : 0)) return &t.v[i];
+    return nullptr;
+}
 
 static unsigned long long* g_prof = nullptr;  // diagnostic build only
 #ifdef PYCLLP_PROFILE
@@ -761,6 +762,29 @@ static T* blob_put(char* host, size_t& off, const std::vector<T>& v, char* dev_b
     off += v.size() * sizeof(T);
     return p;
 }
+
+// g_err <- "<entry>: <what>": the messages of entries that share a body keep the entry's own name
+static int entry_err(int code, const char* entry, const char* what) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", entry, what);
+    return code;
+}
+
+// The argument checks that open the five restricted entries (pycllp_hip_dense_solve_bounded, _dense_solve_batch,
+// _dense_solve_batch_bounded, _sparse_solve_bounded, _sparse_solve_batch_bounded), in their order: the handle and B with the
+// pointers the entry needs whatever B is (`always`), the flags it rejects (`rejected`, with the entry's sentence about them),
+// the pointers it needs when B > 0 (`with_lps`).  The handle is not read and no HIP call is made: every one of these checks
+// comes before either.  Returns 0 or PYCLLP_E_BADARG.
+static int check_restricted(const char* entry, const void* h, long B, bool always, const pycllp_hip_opts* opts, int rejected,
+                            const char* rejected_what, bool with_lps) {
+    if (!h || B < 0 || !always) return entry_err(PYCLLP_E_BADARG, entry, "bad argument");
+    if ((opts ? opts->flags : 0) & rejected) return entry_err(PYCLLP_E_BADARG, entry, rejected_what);
+    if (B > 0 && !with_lps) return entry_err(PYCLLP_E_BADARG, entry, "bad argument");
+    return 0;
+}
+// what the entries with upper bounds reject: on the lane-group kernels, and on the wave kernel
+static constexpr int kBoundedRejected = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL |
+                                        PYCLLP_FLAG_NO_SLACK_PATH;
+static constexpr int kWaveBoundedRejected = kBoundedRejected | PYCLLP_FLAG_BLOCK_KERNEL | PYCLLP_FLAG_FORCE_GUARD_PATH;
 
 extern "C" {
 
@@ -908,15 +932,10 @@ int pycllp_hip_dense_solve(pycllp_hip_dense* h, long B, const double* b_dev, con
 int pycllp_hip_dense_solve_bounded(pycllp_hip_dense* h, long B, const double* b_dev, const double* c_dev, const double* u_dev,
                                    double* x_dev, double* y_dev, double* z_dev, double* s_dev, double* pobj_dev, double* dobj_dev,
                                    int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
-    // every argument check comes before the handle is read and before any HIP call
-    if (!h || B < 0 || !u_dev) return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_bounded: bad argument");
-    const int flags = opts ? opts->flags : 0;
-    const int bad = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL | PYCLLP_FLAG_NO_SLACK_PATH;
-    if (flags & bad)
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH "
-                                        "are not available with upper bounds");
-    if (B > 0 && (!b_dev || !c_dev || !x_dev || !status_dev))
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_bounded: bad argument");
+    const int rc = check_restricted("pycllp_hip_dense_solve_bounded", h, B, u_dev, opts, kBoundedRejected,
+                                    "HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH are not available with upper bounds",
+                                    b_dev && c_dev && x_dev && status_dev);
+    if (rc != 0) return rc;
     if (h->sp || h->variant_sl < 0)
         return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_bounded: A is not [A_dense | I] with m <= 32 and at most 96 "
                                              "dense columns (48 when m <= 16 on the 16-row kernels)");
@@ -928,91 +947,66 @@ int pycllp_hip_dense_solve_bounded(pycllp_hip_dense* h, long B, const double* b_
     return 0;
 }
 
-int pycllp_hip_dense_solve_batch(pycllp_hip_dense* h, long B, const double* A_dev, long a_cols, const double* b_dev,
-                                 const double* c_dev, double* x_dev, double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev,
-                                 int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
-    // the flag and pointer checks come before the handle is read, every check before any HIP call
-    if (!h || B < 0) return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch: bad argument");
-    const int flags = opts ? opts->flags : 0;
-    if (flags & (PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL))
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch: HSD, PREDCORR, WARM_START and WAVE_KERNEL are not available "
-                                        "with per-problem matrices");
-    if (B > 0 && (!A_dev || !b_dev || !c_dev || !x_dev || !status_dev))
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch: bad argument");
-    if (h->sp)
-        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch: per-problem dense matrices stop at m = 32, n = 128 "
-                                             "(beyond: pycllp_hip_sparse_solve_batch)");
-    const bool sl = h->variant_sl >= 0 && !(flags & PYCLLP_FLAG_NO_SLACK_PATH);
+// The body of pycllp_hip_dense_solve_batch and, with u_dev, of pycllp_hip_dense_solve_batch_bounded, behind their argument
+// checks and their look at the handle.  sl: the matrices come without the identity tail (the slack-aware kernels).
+static int dense_solve_batch_impl(const char* entry, pycllp_hip_dense* h, long B, bool sl, const double* A_dev, long a_cols,
+                                  const double* b_dev, const double* c_dev, const double* u_dev, double* x_dev, double* y_dev,
+                                  double* z_dev, double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
+                                  const pycllp_hip_opts* opts, void* stream) {
+    const bool bd = u_dev != nullptr;
     if (a_cols != (long)(sl ? h->n - h->m : h->n)) {
-        snprintf(g_err, sizeof(g_err), "pycllp_hip_dense_solve_batch: a_cols = %ld, expected %d (%s)", a_cols,
-                 sl ? h->n - h->m : h->n, sl ? "the columns before the identity tail" : "every column");
+        snprintf(g_err, sizeof(g_err), "%s: a_cols = %ld, expected %d (%s)", entry, a_cols, sl ? h->n - h->m : h->n,
+                 sl ? "the columns before the identity tail" : "every column");
         return PYCLLP_E_BADARG;
     }
     const int mp = sl ? kSlackVariants[h->variant_sl].mp : kVariants[h->variant].mp;
     const int np = sl ? kSlackVariants[h->variant_sl].np : kVariants[h->variant].np;
-    const PaPlan* pp = nullptr;
-    const GroupPaVariant* pv = nullptr;
-    for (int i = 0; i < kNumPaPlans; i++)
-        if (kPaPlans[i].mp == mp && kPaPlans[i].np == np && kPaPlans[i].sl == (sl ? 1 : 0)) pp = &kPaPlans[i];
-    for (int i = 0; i < kGroupPA.n; i++)
-        if (kGroupPA.v[i].mp == mp && kGroupPA.v[i].np == np && kGroupPA.v[i].sl == (sl ? 1 : 0)) pv = &kGroupPA.v[i];
-    if (!pp || !pv) return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch: no kernel of this shape was compiled");
+    const PaPlan* pp = find_pa(bd ? kPaBdPlans : kPaPlans, mp, np, sl);
+    const GroupPaVariant* pv = find_pa(bd ? kGroupPABD : kGroupPA, mp, np, sl);
+    if (!pp || !pv) return entry_err(PYCLLP_E_UNSUPPORTED, entry, "no kernel of this shape was compiled");
     if (B == 0) return 0;
     DevOpts o = to_dev(opts);
     hipStream_t st = (hipStream_t)stream;
     const LaunchPlan p = pp->plan(h, B, o);
     const hipError_t e = h->ring.run(st, [&](int* qhead) {
-        const GroupPaArgs a = {h->m, h->n, B, A_dev, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, qhead};
+        const GroupPaArgs a = {h->m, h->n, B, A_dev, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
+                               status_dev, iters_dev, qhead};
         const hipError_t el = pv->launch(a, p.grid, p.block, p.lds, o, st);
         publish(h, p);
         return el;
     });
-    if (e != hipSuccess) return set_err((int)e, "per-problem solve kernel launch");
+    if (e != hipSuccess) return set_err((int)e, bd ? "bounded per-problem solve kernel launch" : "per-problem solve kernel launch");
     return 0;
+}
+
+int pycllp_hip_dense_solve_batch(pycllp_hip_dense* h, long B, const double* A_dev, long a_cols, const double* b_dev,
+                                 const double* c_dev, double* x_dev, double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev,
+                                 int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
+    const int rc = check_restricted("pycllp_hip_dense_solve_batch", h, B, true, opts, kBoundedRejected & ~PYCLLP_FLAG_NO_SLACK_PATH,
+                                    "HSD, PREDCORR, WARM_START and WAVE_KERNEL are not available with per-problem matrices",
+                                    A_dev && b_dev && c_dev && x_dev && status_dev);
+    if (rc != 0) return rc;
+    if (h->sp)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch: per-problem dense matrices stop at m = 32, n = 128 "
+                                             "(beyond: pycllp_hip_sparse_solve_batch)");
+    const bool sl = h->variant_sl >= 0 && !((opts ? opts->flags : 0) & PYCLLP_FLAG_NO_SLACK_PATH);
+    return dense_solve_batch_impl("pycllp_hip_dense_solve_batch", h, B, sl, A_dev, a_cols, b_dev, c_dev, nullptr, x_dev, y_dev,
+                                  z_dev, nullptr, pobj_dev, dobj_dev, status_dev, iters_dev, opts, stream);
 }
 
 int pycllp_hip_dense_solve_batch_bounded(pycllp_hip_dense* h, long B, const double* A_dev, long a_cols, const double* b_dev,
                                          const double* c_dev, const double* u_dev, double* x_dev, double* y_dev, double* z_dev,
                                          double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
                                          const pycllp_hip_opts* opts, void* stream) {
-    // every argument check comes before the handle is read and before any HIP call
-    if (!h || B < 0 || !u_dev) return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch_bounded: bad argument");
-    const int flags = opts ? opts->flags : 0;
-    const int bad = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL | PYCLLP_FLAG_NO_SLACK_PATH;
-    if (flags & bad)
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL and "
-                                        "NO_SLACK_PATH are not available with upper bounds on per-problem matrices");
-    if (B > 0 && (!A_dev || !b_dev || !c_dev || !x_dev || !status_dev))
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve_batch_bounded: bad argument");
+    const int rc = check_restricted("pycllp_hip_dense_solve_batch_bounded", h, B, u_dev, opts, kBoundedRejected,
+                                    "HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH are not available with upper bounds "
+                                    "on per-problem matrices", A_dev && b_dev && c_dev && x_dev && status_dev);
+    if (rc != 0) return rc;
     if (h->sp || h->variant_sl < 0)
         return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch_bounded: A is not [A_dense | I] with m <= 32 and at most "
                                              "96 dense columns (48 when m <= 16 on the 16-row kernels)");
-    if (a_cols != (long)(h->n - h->m)) {
-        snprintf(g_err, sizeof(g_err), "pycllp_hip_dense_solve_batch_bounded: a_cols = %ld, expected %d (the columns before the "
-                 "identity tail)", a_cols, h->n - h->m);
-        return PYCLLP_E_BADARG;
-    }
-    const int mp = kSlackVariants[h->variant_sl].mp, np = kSlackVariants[h->variant_sl].np;
-    const PaPlan* pp = nullptr;
-    const GroupPaBdVariant* pv = nullptr;
-    for (int i = 0; i < kNumPaBdPlans; i++)
-        if (kPaBdPlans[i].mp == mp && kPaBdPlans[i].np == np) pp = &kPaBdPlans[i];
-    for (int i = 0; i < kGroupPABD.n; i++)
-        if (kGroupPABD.v[i].mp == mp && kGroupPABD.v[i].np == np) pv = &kGroupPABD.v[i];
-    if (!pp || !pv) return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch_bounded: no kernel of this shape was compiled");
-    if (B == 0) return 0;
-    DevOpts o = to_dev(opts);
-    hipStream_t st = (hipStream_t)stream;
-    const LaunchPlan p = pp->plan(h, B, o);
-    const hipError_t e = h->ring.run(st, [&](int* qhead) {
-        const GroupPaBdArgs a = {h->m, h->n, B, A_dev, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
-                                 status_dev, iters_dev, qhead};
-        const hipError_t el = pv->launch(a, p.grid, p.block, p.lds, o, st);
-        publish(h, p);
-        return el;
-    });
-    if (e != hipSuccess) return set_err((int)e, "bounded per-problem solve kernel launch");
-    return 0;
+    return dense_solve_batch_impl("pycllp_hip_dense_solve_batch_bounded", h, B, true, A_dev, a_cols, b_dev, c_dev, u_dev, x_dev,
+                                  y_dev, z_dev, s_dev, pobj_dev, dobj_dev, status_dev, iters_dev, opts, stream);
 }
 
 int pycllp_hip_dense_newton(pycllp_hip_dense* h, long B, const double* x_dev, const double* z_dev,
@@ -1344,79 +1338,62 @@ int pycllp_hip_sparse_solve_batch(pycllp_hip_sparse* h, long B, const double* Ad
     return sparse_solve_impl(h, B, Adata_dev, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, opts, stream);
 }
 
-int pycllp_hip_sparse_solve_bounded(pycllp_hip_sparse* h, long B, const double* b_dev, const double* c_dev, const double* u_dev,
-                                    double* x_dev, double* y_dev, double* z_dev, double* s_dev, double* pobj_dev, double* dobj_dev,
-                                    int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
-    // every argument check comes before the handle is read and before any HIP call
-    if (!h || B < 0 || !u_dev) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_bounded: bad argument");
-    const int flags = opts ? opts->flags : 0;
-    const int bad = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL | PYCLLP_FLAG_BLOCK_KERNEL |
-                    PYCLLP_FLAG_NO_SLACK_PATH | PYCLLP_FLAG_FORCE_GUARD_PATH;
-    if (flags & bad)
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, "
-                                        "NO_SLACK_PATH and FORCE_GUARD_PATH are not available with upper bounds");
-    if (B > 0 && (!b_dev || !c_dev || !x_dev || !status_dev))
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_bounded: bad argument");
-    if (h->big)
-        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_bounded: the bounded wave kernel stops at m = 128, n = 512");
+// The body of pycllp_hip_sparse_solve_bounded and, with a_batch, of pycllp_hip_sparse_solve_batch_bounded, behind their
+// argument checks (as sparse_solve_impl is of the entries without bounds).  plan / tried: the entry's plan slot of the handle;
+// create: its constructor, named create_what in a HIP error of the build.
+typedef int (*bounded_plan_fn)(int, int, int, const double*, const int*, const int*, int, hipStream_t, WregPlan**);
+static int sparse_solve_bounded_impl(const char* entry, pycllp_hip_sparse* h, long B, const double* a_batch, WregPlan** plan,
+                                     bool* tried, bounded_plan_fn create, const char* create_what, const double* b_dev,
+                                     const double* c_dev, const double* u_dev, double* x_dev, double* y_dev, double* z_dev,
+                                     double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
+                                     const pycllp_hip_opts* opts, void* stream) {
+    if (h->big) return entry_err(PYCLLP_E_UNSUPPORTED, entry, "the bounded wave kernel stops at m = 128, n = 512");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = lazy_plan(h, &h->wreg_bd, &h->wreg_bd_tried, "wreg_plan_create_bounded", [&](WregPlan** wp) {
-        return wreg_plan_create_bounded(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(), h->host_col.data(),
-                                        h->max_lds, st, wp);
+    const int rc = lazy_plan(h, plan, tried, create_what, [&](WregPlan** wp) {
+        return create(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(), h->host_col.data(), h->max_lds, st, wp);
     });
     if (rc != 0) return rc;
-    WregPlan* plan = h->wreg_bd;
-    if (!plan)
-        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_bounded: no variant of the bounded wave kernel covers this A "
-                                             "(rows, columns, or its tables in LDS)");
+    if (!*plan)
+        return entry_err(PYCLLP_E_UNSUPPORTED, entry,
+                         a_batch ? "no variant of the bounded wave kernel covers this structure on per-problem values (rows, "
+                                   "columns, or its tables in LDS)"
+                                 : "no variant of the bounded wave kernel covers this A (rows, columns, or its tables in LDS)");
     if (B == 0) return 0;
     DevOpts o = to_dev(opts);
     int grid = 0;
     const hipError_t e = h->ring.run(st, [&](int* qw) {
-        return wreg_launch_solve_bounded(plan, B, nullptr, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev, status_dev,
-                                         iters_dev, qw, o, h->num_cu, st, &grid);
+        return wreg_launch_solve_bounded(*plan, B, a_batch, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
+                                         status_dev, iters_dev, qw, o, h->num_cu, st, &grid);
     });
-    record_launch(h, plan, grid);
-    if (e != hipSuccess) return set_err((int)e, "ipm_wreg_bounded_kernel launch");
+    record_launch(h, *plan, grid);
+    if (e != hipSuccess) return set_err((int)e, a_batch ? "ipm_wreg_bounded_pa_kernel launch" : "ipm_wreg_bounded_kernel launch");
     return 0;
+}
+
+int pycllp_hip_sparse_solve_bounded(pycllp_hip_sparse* h, long B, const double* b_dev, const double* c_dev, const double* u_dev,
+                                    double* x_dev, double* y_dev, double* z_dev, double* s_dev, double* pobj_dev, double* dobj_dev,
+                                    int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
+    const int rc = check_restricted("pycllp_hip_sparse_solve_bounded", h, B, u_dev, opts, kWaveBoundedRejected,
+                                    "HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and FORCE_GUARD_PATH are "
+                                    "not available with upper bounds", b_dev && c_dev && x_dev && status_dev);
+    if (rc != 0) return rc;
+    return sparse_solve_bounded_impl("pycllp_hip_sparse_solve_bounded", h, B, nullptr, &h->wreg_bd, &h->wreg_bd_tried,
+                                     wreg_plan_create_bounded, "wreg_plan_create_bounded", b_dev, c_dev, u_dev, x_dev, y_dev, z_dev,
+                                     s_dev, pobj_dev, dobj_dev, status_dev, iters_dev, opts, stream);
 }
 
 int pycllp_hip_sparse_solve_batch_bounded(pycllp_hip_sparse* h, long B, const double* Adata_dev, const double* b_dev,
                                           const double* c_dev, const double* u_dev, double* x_dev, double* y_dev, double* z_dev,
                                           double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
                                           const pycllp_hip_opts* opts, void* stream) {
-    // every argument check comes before the handle is read and before any HIP call
-    if (!h || B < 0 || !Adata_dev || !u_dev) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_batch_bounded: bad argument");
-    const int flags = opts ? opts->flags : 0;
-    const int bad = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL | PYCLLP_FLAG_BLOCK_KERNEL |
-                    PYCLLP_FLAG_NO_SLACK_PATH | PYCLLP_FLAG_FORCE_GUARD_PATH;
-    if (flags & bad)
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_batch_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, "
-                                        "NO_SLACK_PATH and FORCE_GUARD_PATH are not available with upper bounds on per-problem matrices");
-    if (B > 0 && (!b_dev || !c_dev || !x_dev || !status_dev))
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve_batch_bounded: bad argument");
-    if (h->big)
-        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_batch_bounded: the bounded wave kernel stops at m = 128, n = 512");
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = lazy_plan(h, &h->wreg_bdpa, &h->wreg_bdpa_tried, "wreg_plan_create_bounded_pa", [&](WregPlan** wp) {
-        return wreg_plan_create_bounded_pa(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(),
-                                           h->host_col.data(), h->max_lds, st, wp);
-    });
+    const int rc = check_restricted("pycllp_hip_sparse_solve_batch_bounded", h, B, Adata_dev && u_dev, opts, kWaveBoundedRejected,
+                                    "HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and FORCE_GUARD_PATH are "
+                                    "not available with upper bounds on per-problem matrices",
+                                    b_dev && c_dev && x_dev && status_dev);
     if (rc != 0) return rc;
-    WregPlan* plan = h->wreg_bdpa;
-    if (!plan)
-        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_solve_batch_bounded: no variant of the bounded wave kernel covers this "
-                                             "structure on per-problem values (rows, columns, or its tables in LDS)");
-    if (B == 0) return 0;
-    DevOpts o = to_dev(opts);
-    int grid = 0;
-    const hipError_t e = h->ring.run(st, [&](int* qw) {
-        return wreg_launch_solve_bounded(plan, B, Adata_dev, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
-                                         status_dev, iters_dev, qw, o, h->num_cu, st, &grid);
-    });
-    record_launch(h, plan, grid);
-    if (e != hipSuccess) return set_err((int)e, "ipm_wreg_bounded_pa_kernel launch");
-    return 0;
+    return sparse_solve_bounded_impl("pycllp_hip_sparse_solve_batch_bounded", h, B, Adata_dev, &h->wreg_bdpa, &h->wreg_bdpa_tried,
+                                     wreg_plan_create_bounded_pa, "wreg_plan_create_bounded_pa", b_dev, c_dev, u_dev, x_dev, y_dev,
+                                     z_dev, s_dev, pobj_dev, dobj_dev, status_dev, iters_dev, opts, stream);
 }
 
 int pycllp_hip_sparse_newton(pycllp_hip_sparse* h, long B, const double* x_dev, const double* z_dev, const double* y_dev,

@@ -18,21 +18,14 @@ static hipError_t launch_group_pa(const GroupPaArgs& a, int grid, int block, int
     return hipGetLastError();
 }
 
-// the list of GROUP_SHAPES (ipm_dense.hip), development builds included (tests/test_dense_batch.py compares the two)
-#if defined(PYCLLP_DEV_ONLY_3296)
-#define GROUP_PA_SHAPES(X) X(32, 96)
-#elif defined(PYCLLP_DEV_ONLY_1648)
-#define GROUP_PA_SHAPES(X) X(16, 48)
-#else
-#define GROUP_PA_SHAPES(X) X(16, 32) X(16, 48) X(16, 64) X(32, 64) X(32, 96) X(32, 128)
-#endif
+// one launcher per GROUP_SHAPES shape (group_pa.h) and SL
 #define GROUP_PA_VARIANT(MP, NP) { MP, NP, 0, launch_group_pa<MP, NP, false> }, { MP, NP, 1, launch_group_pa<MP, NP, true> },
 // The device pass gets a file-local copy of the table: it is never emitted, but referencing the launchers is what makes the
 // kernels get instantiated (an external table of host function pointers would be emitted into the device object and fail to
 // link there; as WREG_TABLE of wreg_wave.h).
 #ifdef __HIP_DEVICE_COMPILE__
-namespace { [[maybe_unused]] const GroupPaVariant kGroupPA_instantiate[] = { GROUP_PA_SHAPES(GROUP_PA_VARIANT) }; }
+namespace { [[maybe_unused]] const GroupPaVariant kGroupPA_instantiate[] = { GROUP_SHAPES(GROUP_PA_VARIANT) }; }
 #else
-namespace { const GroupPaVariant kGroupPA_v[] = { GROUP_PA_SHAPES(GROUP_PA_VARIANT) }; }
+namespace { const GroupPaVariant kGroupPA_v[] = { GROUP_SHAPES(GROUP_PA_VARIANT) }; }
 extern const GroupPaVariants kGroupPA = { kGroupPA_v, (int)(sizeof(kGroupPA_v) / sizeof(kGroupPA_v[0])) };
 #endif

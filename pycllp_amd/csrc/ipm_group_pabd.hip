@@ -8,7 +8,7 @@
 #include "ipm_group_slot.inc"
 
 template <int MP, int NP>
-static hipError_t launch_group_pabd(const GroupPaBdArgs& a, int grid, int block, int lds, DevOpts o, hipStream_t st) {
+static hipError_t launch_group_pabd(const GroupPaArgs& a, int grid, int block, int lds, DevOpts o, hipStream_t st) {
     using P = GeoPA<GeoG<MP, NP, true>>;
     auto kernel = ipm_bounded_pa_kernel<MP, NP>;
     if (block > P::wpb_capped(PYCLLP_WPB_BOUNDED) * WAVE || (size_t)lds < P::lds_bytes(block / WAVE))
@@ -20,19 +20,12 @@ static hipError_t launch_group_pabd(const GroupPaBdArgs& a, int grid, int block,
     return hipGetLastError();
 }
 
-// the list of GROUP_SHAPES (ipm_dense.hip), development builds included (tests/test_general_batch.py compares the two)
-#if defined(PYCLLP_DEV_ONLY_3296)
-#define GROUP_PABD_SHAPES(X) X(32, 96)
-#elif defined(PYCLLP_DEV_ONLY_1648)
-#define GROUP_PABD_SHAPES(X) X(16, 48)
-#else
-#define GROUP_PABD_SHAPES(X) X(16, 32) X(16, 48) X(16, 64) X(32, 64) X(32, 96) X(32, 128)
-#endif
-#define GROUP_PABD_VARIANT(MP, NP) { MP, NP, launch_group_pabd<MP, NP> },
+// one launcher per GROUP_SHAPES shape (group_pa.h)
+#define GROUP_PABD_VARIANT(MP, NP) { MP, NP, 1, launch_group_pabd<MP, NP> },
 // (the device pass gets a file-local copy of the table, as in ipm_group_pa.hip: referencing the launchers instantiates the kernels)
 #ifdef __HIP_DEVICE_COMPILE__
-namespace { [[maybe_unused]] const GroupPaBdVariant kGroupPABD_instantiate[] = { GROUP_PABD_SHAPES(GROUP_PABD_VARIANT) }; }
+namespace { [[maybe_unused]] const GroupPaVariant kGroupPABD_instantiate[] = { GROUP_SHAPES(GROUP_PABD_VARIANT) }; }
 #else
-namespace { const GroupPaBdVariant kGroupPABD_v[] = { GROUP_PABD_SHAPES(GROUP_PABD_VARIANT) }; }
-extern const GroupPaBdVariants kGroupPABD = { kGroupPABD_v, (int)(sizeof(kGroupPABD_v) / sizeof(kGroupPABD_v[0])) };
+namespace { const GroupPaVariant kGroupPABD_v[] = { GROUP_SHAPES(GROUP_PABD_VARIANT) }; }
+extern const GroupPaVariants kGroupPABD = { kGroupPABD_v, (int)(sizeof(kGroupPABD_v) / sizeof(kGroupPABD_v[0])) };
 #endif

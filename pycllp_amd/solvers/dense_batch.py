@@ -11,7 +11,7 @@ import torch
 from . import BaseSolver
 from .. import _native
 from ..lp import EqualityLP, SparseMatrix
-from .hip import (RESULTS, Handle, HipSparsePrimalNormalSolver, _require_gpu, autoscale_wanted, plugin_options,
+from .hip import (RESULTS, DeviceArrays, Handle, HipSparsePrimalNormalSolver, _require_gpu, autoscale_wanted, plugin_options,
                   solve_opts)
 
 GROUP_MAX_ROWS, GROUP_MAX_COLS = 32, 128      # the lane-group kernels
@@ -50,7 +50,7 @@ def densify_batch(rows, cols, data, m, a_cols):
     return out.reshape(data.shape[0], m, a_cols)
 
 
-class HipDenseBatchPrimalNormalSolver(BaseSolver):
+class HipDenseBatchPrimalNormalSolver(DeviceArrays, BaseSolver):
     """``lp.init(s); lp.solve(s)`` on an equality-form LP with per-problem values of a dense A; results as the other HIP
     plugins leave them (``x, y, z, status, iters, primal_obj, dual_obj``) and ``kernel``: which path served the last solve."""
     name = 'hip_dense_batch_primal_normal'
@@ -103,11 +103,6 @@ class HipDenseBatchPrimalNormalSolver(BaseSolver):
         if verbose > 0:
             print("Initializing %s (m=%d, n=%d, a_cols=%d) on %s" % (type(self).__name__, m, n, self.a_cols, self.device))
         self._handle = Handle(np.ascontiguousarray(A.todense(0), dtype=np.float64).reshape(m, n), self.device, self.stream)
-
-    def _dev(self, a):
-        if isinstance(a, torch.Tensor):
-            return a.to(device=self.device, dtype=torch.float64).contiguous()
-        return torch.as_tensor(np.require(a, dtype=np.float64, requirements=["C", "W"]), device=self.device)   # (a read-only array is copied)
 
     def solve_device(self, A_dev, b_dev, c_dev, **options):
         """Device-resident entry: A [B, m, a_cols] (``self.a_cols``: n - m where the identity tail is implied, else n),

@@ -17,7 +17,8 @@ import torch
 from . import BaseGeneralSolver
 from .. import _native
 from ..lp import GeneralLP, SparseMatrix
-from .hip import Handle, HipDensePrimalNormalSolver, _require_gpu, autoscale_wanted, plugin_options, solve_opts
+from .hip import (DeviceArrays, Handle, HipDensePrimalNormalSolver, _require_gpu, autoscale_wanted, bounded_outputs,
+                  plugin_options, solve_opts)
 
 NATIVE_MAX_ROWS, NATIVE_MAX_COLS = 32, 96      # the slack-aware kernels: m' <= 32 rows, n <= 96 original columns
 WAVE_MAX_ROWS, WAVE_MAX_COLS = 128, 512        # the bounded wave kernel: m' <= 128 rows, N <= 512 columns of A^
@@ -44,7 +45,17 @@ def subset(glp, idx):
     return GeneralLP(A2, glp.b[idx], glp.c[idx], a=glp.a[idx], l=glp.l[idx], u=glp.u[idx], f=glp.f[idx])
 
 
-class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
+def download_bounded(out, blp, bmap, device):
+    """The tail of a bounded solve: waits for ``device``, downloads ``out`` (``bounded_outputs``) and maps it back to the
+    GeneralLP's variables with ``bmap``; the objectives get the bounded form's ``f``."""
+    torch.cuda.synchronize(device)
+    r = {k: v.cpu().numpy() for k, v in out.items()}
+    xo, yo, zo, so = bmap.general(r["x"], r["y"], r["z"], r["s"])
+    f = np.broadcast_to(blp.f, (blp.nproblems,))
+    return dict(x=xo, y=yo, z=zo, s=so, status=r["status"], iters=r["iters"], primal_obj=r["pobj"] + f, dual_obj=r["dobj"] + f)
+
+
+class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
     """``glp.init(s); glp.solve(s)`` on a ``GeneralLP``; results in the ORIGINAL variables: ``x [B, n]``, ``y [B, m]`` (one
     per row of the LP, 0 for a row without bounds), ``z`` / ``s [B, n]`` (duals of x >= l / x <= u), ``status``, ``iters``,
     ``primal_obj``, ``dual_obj`` (f and c'l included)."""
@@ -138,24 +149,15 @@ class HipGeneralPrimalNormalSolver(BaseGeneralSolver):
 
     def _solve_bounded(self, blp, bmap):
         """One upload, one launch of the bounded kernel, one download; None if the library declines A^ (PYCLLP_E_UNSUPPORTED)."""
-        B, mk, N = blp.nproblems, blp.nrows, blp.ncols
         wanted = self.autoscale == "auto" and autoscale_wanted(blp.b, blp.c, blp.u)
         o = solve_opts(self.options, _native.FLAG_AUTOSCALE if wanted else 0)
-        dev = self.device
-        f64 = dict(dtype=torch.float64, device=dev)
-        b, c, u = (torch.as_tensor(np.ascontiguousarray(v), **f64) for v in (blp.b, blp.c, blp.u))
-        out = dict(x=torch.empty((B, N), **f64), y=torch.empty((B, mk), **f64), z=torch.empty((B, N), **f64),
-                   s=torch.empty((B, N), **f64), pobj=torch.empty(B, **f64), dobj=torch.empty(B, **f64),
-                   status=torch.empty(B, dtype=torch.int32, device=dev), iters=torch.empty(B, dtype=torch.int32, device=dev))
+        b, c, u = (torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64, device=self.device) for v in (blp.b, blp.c, blp.u))
+        out = bounded_outputs(blp.nproblems, blp.nrows, blp.ncols, self.device)
         try:
             self._handle.solve_bounded(self.stream, b, c, u, out, o)
         except NotImplementedError:
             return None
-        torch.cuda.synchronize(dev)
-        r = {k: v.cpu().numpy() for k, v in out.items()}
-        xo, yo, zo, so = bmap.general(r["x"], r["y"], r["z"], r["s"])
-        f = np.broadcast_to(blp.f, (B,))
-        return dict(x=xo, y=yo, z=zo, s=so, status=r["status"], iters=r["iters"], primal_obj=r["pobj"] + f, dual_obj=r["dobj"] + f)
+        return download_bounded(out, blp, bmap, self.device)
 
     def solve_expanded(self, glp):
         """Solve ``glp`` through ``to_standard_form().to_equality_form()`` on ``HipDensePrimalNormalSolver`` and map the results
@@ -230,3 +232,122 @@ class HipSparseGeneralPrimalNormalSolver(HipGeneralPrimalNormalSolver):
             if rows > L.pycllp_hip_dense_max_rows() or glp.ncols + rows > L.pycllp_hip_dense_max_cols():
                 return idx[:0]
         return idx
+
+
+class PerProblemBounded(object):
+    """Mix-in in front of one of the two plugins above, for batches with per-problem values of A on a bounded kernel that takes
+    them: ``init`` makes the handle from the bounded form (or, where the kernel does not serve it, a delegate: the plugin
+    behind the mix-in, with the same options, whose ``kernel`` and results are reported unchanged), ``solve_device`` and
+    ``solve`` launch the one entry.  A subclass states ``_delegate_class``, ``native_fits``, ``_make_handle(blp)`` (the
+    ``Handle`` of the bounded form; ``NotImplementedError`` where the library declines it), ``_values(blp)`` (the per-problem
+    array as the entry takes it, numpy), ``_values_spec(B)`` (the shape that array must have, and the text that says so),
+    ``_call(A, b, c, u, out, o)`` (the ``Handle`` call) and ``_needs`` (what ``solve_device`` asks of ``init``);
+    ``_unchanged``, ``_solve_delegate`` and ``_solve_again`` where it differs."""
+    _changed_what = "%d kept rows (%d at init), %d matrices"
+
+    def __init__(self, *args, **kwargs):
+        super(PerProblemBounded, self).__init__(*args, **kwargs)
+        self._delegate = None
+        self._keepalive = None
+        self.mk = None
+
+    def _make_delegate(self, glp):
+        self._handle = None
+        self._delegate = self._delegate_class(device=self.device, stream=self.stream, autoscale=self.autoscale, hsd=self.hsd,
+                                              **self.options)
+        self._delegate.init(glp)
+
+    # -- plugin API ------------------------------------------------------------------------------
+    def init(self, lp, verbose=0):
+        """Fixes the shape of the bounded form (m' kept rows, N = n + m' columns) and makes the handle from it."""
+        self.device = _require_gpu(self.device)
+        glp = as_general(lp)
+        blp, _ = glp.to_bounded_equality_form()
+        self.m, self.n, self.mk = glp.nrows, glp.ncols, blp.nrows
+        self._handle = self._delegate = self._keepalive = None
+        if self.native_fits(glp, blp):
+            try:
+                self._handle = self._make_handle(blp)
+            except NotImplementedError:
+                pass
+        if self._handle is None:
+            self._make_delegate(glp)
+
+    def solve_device(self, A_dev, b_dev, c_dev, u_dev, **options):
+        """Device-resident entry, in the bounded form's variables: the per-problem array (``_values_spec``; the subclass says
+        how to make it), b [B, m'], c and u [B, N] (torch CUDA tensors or numpy) -> dict of CUDA tensors (``BOUNDED_RESULTS``).
+        Asynchronous on the solver's stream; the kernel's verdict stands (no look at the data: ``autoscale='auto'`` and
+        ``hsd='auto'`` count as off)."""
+        if self._handle is None:
+            raise RuntimeError("solve_device() needs init() on an LP the %s" % self._needs)
+        return self._launch(self._dev(A_dev), self._dev(b_dev), self._dev(c_dev), self._dev(u_dev), 0, options)
+
+    def _launch(self, A, b, c, u, extra_flags, overrides):
+        B, mk, N = int(b.shape[0]), self.mk, self.n + self.mk
+        a_shape, a_text = self._values_spec(B)
+        if (b.dim() != 2 or b.shape[1] != mk or tuple(c.shape) != (B, N) or tuple(u.shape) != (B, N)
+                or tuple(A.shape) != a_shape):
+            raise ValueError("%s, b [B,%d], c and u [B,%d] with equal B; got %r, %r, %r and %r"
+                             % (a_text, mk, N, tuple(A.shape), tuple(b.shape), tuple(c.shape), tuple(u.shape)))
+        out = bounded_outputs(B, mk, N, self.device)
+        o = solve_opts(self.options, extra_flags, **overrides)
+        if B:                                   # (an empty tensor has no address to hand over; the entry launches nothing for B = 0)
+            self._call(A, b, c, u, out, o)
+        self._keepalive = (A, b, c, u)
+        self.kernel = self._native_kernel
+        return out
+
+    def _unchanged(self, glp, blp):
+        return self.native_fits(glp, blp) and blp.nrows == self.mk
+
+    def _solve_delegate(self, glp, verbose):
+        self._delegate.solve(glp, verbose=verbose)
+        self.kernel = self._delegate.kernel
+
+    def _solve_again(self, glp):
+        """``solve_expanded`` for the LPs that ``hsd='auto'`` solves again; None: the kernel's status stands."""
+        return self.solve_expanded(glp)
+
+    def solve(self, lp, verbose=0):
+        if self._delegate is None and self._handle is None:
+            raise RuntimeError("solve() called before init()")
+        glp = as_general(lp)
+        if glp.nrows != self.m or glp.ncols != self.n:
+            raise ValueError("LP shape changed since init(): (%d,%d) vs (%d,%d)" % (glp.nrows, glp.ncols, self.m, self.n))
+        res = None
+        if self._delegate is None:
+            blp, bmap = glp.to_bounded_equality_form()
+            if not self._unchanged(glp, blp):
+                raise ValueError("the bounded form changed since init(): " + self._changed_what
+                                 % (blp.nrows, self.mk, glp.A.nproblems))
+            res = self._solve_bounded(blp, bmap)
+            if res is None:                     # the entry answers PYCLLP_E_UNSUPPORTED
+                self._make_delegate(glp)
+        if res is None:
+            self._solve_delegate(glp, verbose)
+            for k in RESULTS:
+                setattr(self, k, getattr(self._delegate, k))
+            return self.status
+        if self.hsd == "auto":
+            idx = self._redo(glp, np.flatnonzero(res["status"] != 0))
+            r2 = self._solve_again(subset(glp, idx)) if idx.size else None
+            if r2 is not None:
+                for k in RESULTS:
+                    res[k][idx] = r2[k]
+        for k in RESULTS:
+            setattr(self, k, res[k])
+        return self.status
+
+    def _solve_bounded(self, blp, bmap):
+        """One upload, one launch, one download; None if the entry declines the handle (PYCLLP_E_UNSUPPORTED)."""
+        wanted = self.autoscale == "auto" and autoscale_wanted(blp.b, blp.c, blp.u)
+        A, b, c, u = (self._dev(np.ascontiguousarray(v)) for v in (self._values(blp), blp.b, blp.c, blp.u))
+        try:
+            out = self._launch(A, b, c, u, _native.FLAG_AUTOSCALE if wanted else 0, {})
+        except NotImplementedError:
+            return None
+        return download_bounded(out, blp, bmap, self.device)
+
+    def launch_info(self):
+        """``Handle.launch_info()`` of the kernel's last launch; the delegate's where it served the solve."""
+        return self._delegate.launch_info() if self._delegate is not None else self._handle.launch_info()

@@ -148,6 +148,24 @@ def solve_opts(options, extra_flags=0, **overrides):
 
 
 RESULTS = ("x", "y", "z", "pobj", "dobj", "status", "iters")       # (also the order of the solve entries' outputs)
+BOUNDED_RESULTS = ("x", "y", "z", "s", "pobj", "dobj", "status", "iters")      # ... and of the entries with upper bounds
+
+
+def bounded_outputs(B, m, N, device):
+    """Uninitialised output tensors of a bounded solve of B LPs with m rows and N columns (``BOUNDED_RESULTS``)."""
+    shapes = dict(x=(B, N), y=(B, m), z=(B, N), s=(B, N), pobj=(B,), dobj=(B,), status=(B,), iters=(B,))
+    return {k: torch.empty(shapes[k], dtype=torch.int32 if k in ("status", "iters") else torch.float64, device=device)
+            for k in BOUNDED_RESULTS}
+
+
+class DeviceArrays(object):
+    """Mix-in of the plugins: what they upload goes through ``_dev``."""
+
+    def _dev(self, a):
+        """``a`` (torch tensor or numpy) as a contiguous float64 tensor on ``self.device``."""
+        if isinstance(a, torch.Tensor):
+            return a.to(device=self.device, dtype=torch.float64).contiguous()
+        return torch.as_tensor(np.require(a, dtype=np.float64, requirements=["C", "W"]), device=self.device)   # (a read-only array is copied)
 
 
 class Handle(object):
@@ -190,24 +208,25 @@ class Handle(object):
         """B LPs with the upper bounds u [B, n] into ``out`` (x, y, z, s, pobj, dobj, status, iters).  ``values`` [B, nnz]:
         per-problem values of A in the CSR order of the handle's matrix (sparse family)."""
         entry, lead = ("solve_bounded", ()) if values is None else ("solve_batch_bounded", (values,))
-        self._call(entry, self, int(b.shape[0]), *lead, b, c, u,
-                   *(out[k] for k in ("x", "y", "z", "s", "pobj", "dobj", "status", "iters")), ctypes.byref(o), self._stream(stream))
+        self._call(entry, self, int(b.shape[0]), *lead, b, c, u, *(out[k] for k in BOUNDED_RESULTS), ctypes.byref(o),
+                   self._stream(stream))
+
+    def _solve_batch(self, entry, stream, A, vectors, outputs, o):
+        """``entry`` of the dense family on per-problem matrices: A must be a contiguous [B, m, a_cols] with the B of b."""
+        B = int(vectors[0].shape[0])
+        if A.dim() != 3 or A.shape[0] != B or not A.is_contiguous():
+            raise ValueError("A must be a contiguous [B, m, a_cols] tensor with the B of b; got %r" % (tuple(A.shape),))
+        self._call(entry, self, B, A, ctypes.c_long(int(A.shape[2])), *vectors, *outputs, ctypes.byref(o), self._stream(stream))
 
     def solve_batch_dense(self, stream, A, b, c, out, o):
         """B LPs with their own dense matrices A [B, m, a_cols] (dense family; a_cols = n - m where the handle's tail is the
         identity and ``o`` does not carry FLAG_NO_SLACK_PATH, else n) into ``out`` (the arrays of ``RESULTS``)."""
-        if A.dim() != 3 or A.shape[0] != b.shape[0] or not A.is_contiguous():
-            raise ValueError("A must be a contiguous [B, m, a_cols] tensor with the B of b; got %r" % (tuple(A.shape),))
-        self._call("solve_batch", self, int(b.shape[0]), A, ctypes.c_long(int(A.shape[2])), b, c, *(out[k] for k in RESULTS),
-                   ctypes.byref(o), self._stream(stream))
+        self._solve_batch("solve_batch", stream, A, (b, c), [out[k] for k in RESULTS], o)
 
     def solve_batch_bounded(self, stream, A, b, c, u, out, o):
         """B LPs with their own dense matrices A [B, m, n - m] (dense family, a handle whose tail is the identity) and the upper
         bounds u [B, n] into ``out`` (x, y, z, s, pobj, dobj, status, iters)."""
-        if A.dim() != 3 or A.shape[0] != b.shape[0] or not A.is_contiguous():
-            raise ValueError("A must be a contiguous [B, m, a_cols] tensor with the B of b; got %r" % (tuple(A.shape),))
-        self._call("solve_batch_bounded", self, int(b.shape[0]), A, ctypes.c_long(int(A.shape[2])), b, c, u,
-                   *(out[k] for k in ("x", "y", "z", "s", "pobj", "dobj", "status", "iters")), ctypes.byref(o), self._stream(stream))
+        self._solve_batch("solve_batch_bounded", stream, A, (b, c, u), [out[k] for k in BOUNDED_RESULTS], o)
 
     def newton(self, stream, x, z, y, b, c, mu, dy, nrefine, o):
         self._call("newton", self, int(x.shape[0]), x, z, y, b, c, float(mu), dy, nrefine, ctypes.byref(o), self._stream(stream))
@@ -254,7 +273,7 @@ class Handle(object):
             pass
 
 
-class HipDensePrimalNormalSolver(BaseSolver):
+class HipDensePrimalNormalSolver(DeviceArrays, BaseSolver):
     """Drop-in for ``cl_dense_primal_normal`` on MI355X.  The LP must be in equality form
     (callers use ``StandardLP.to_equality_form()`` first, as for the OpenCL solver).  Per-problem values of A
     (``lp.A.data [nproblems, nnz]``) are served by the sparse path's per-problem kernel: one structure, values from HBM."""
@@ -300,11 +319,6 @@ class HipDensePrimalNormalSolver(BaseSolver):
         self.buffers = {}
 
     # -- helpers ---------------------------------------------------------------------------------
-    def _dev(self, a):
-        if isinstance(a, torch.Tensor):
-            return a.to(device=self.device, dtype=torch.float64).contiguous()
-        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=self.device)
-
     @staticmethod
     def consume(lp):
         """Everything a HIP host reads from an LP object -- the reference's ``EqualityLP`` or this package's -- as plain

@@ -48,3 +48,58 @@ def test_defaults_and_argument_errors_without_gpu():
 
 def test_struct_layout_matches_header():
     assert ctypes.sizeof(_native.Opts) == 5 * 8 + 4 * 4
+
+
+_BOUNDED = ("b", "c", "u", "x", "y", "z", "s", "pobj", "dobj", "status", "iters")
+_GROUP_FLAGS = ("HSD", "PREDCORR", "WARM_START", "WAVE_KERNEL", "NO_SLACK_PATH")
+_WAVE_FLAGS = _GROUP_FLAGS + ("BLOCK_KERNEL", "FORCE_GUARD_PATH")
+# entry -> (its device arrays in order, the pointers it requires, the flags it rejects, its sentence about them): the strings
+# are the library's, byte for byte
+RESTRICTED = {
+    "pycllp_hip_dense_solve_bounded": (
+        _BOUNDED, ("b", "c", "u", "x", "status"), _GROUP_FLAGS,
+        b"pycllp_hip_dense_solve_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH are not available with "
+        b"upper bounds"),
+    "pycllp_hip_dense_solve_batch": (
+        ("A", "b", "c", "x", "y", "z", "pobj", "dobj", "status", "iters"), ("A", "b", "c", "x", "status"), _GROUP_FLAGS[:4],
+        b"pycllp_hip_dense_solve_batch: HSD, PREDCORR, WARM_START and WAVE_KERNEL are not available with per-problem matrices"),
+    "pycllp_hip_dense_solve_batch_bounded": (
+        ("A",) + _BOUNDED, ("A", "b", "c", "u", "x", "status"), _GROUP_FLAGS,
+        b"pycllp_hip_dense_solve_batch_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH are not available "
+        b"with upper bounds on per-problem matrices"),
+    "pycllp_hip_sparse_solve_bounded": (
+        _BOUNDED, ("b", "c", "u", "x", "status"), _WAVE_FLAGS,
+        b"pycllp_hip_sparse_solve_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and "
+        b"FORCE_GUARD_PATH are not available with upper bounds"),
+    "pycllp_hip_sparse_solve_batch_bounded": (
+        ("Adata",) + _BOUNDED, ("Adata", "b", "c", "u", "x", "status"), _WAVE_FLAGS,
+        b"pycllp_hip_sparse_solve_batch_bounded: HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and "
+        b"FORCE_GUARD_PATH are not available with upper bounds on per-problem matrices"),
+}
+
+
+@pytest.mark.parametrize("entry", sorted(RESTRICTED))
+def test_restricted_entries_refuse_with_their_own_messages(entry):
+    """The argument checks of the entries that take only some flags come before the handle is read (the handle here is 64
+    zero bytes) and before any HIP call, and each names its own entry in ``pycllp_hip_last_error()``."""
+    L = _native.lib()
+    arrays, required, rejected, sentence = RESTRICTED[entry]
+    fn = getattr(L, entry)
+    fake = ctypes.create_string_buffer(64)
+    handle = ctypes.cast(fake, ctypes.c_void_p)
+    bad_argument = entry.encode() + b": bad argument"
+
+    def call(h, flags=0, null=None):
+        args = [h, 4]
+        for name in arrays:
+            args.append(None if name == null else ctypes.c_void_p(8))
+            if name == "A":
+                args.append(5)                                   # a_cols: read only after the checks
+        return fn(*args, ctypes.byref(_native.default_opts(flags=flags)), None)
+
+    assert call(None) == -1 and L.pycllp_hip_last_error() == bad_argument
+    for name in required:
+        assert call(handle, null=name) == -1 and L.pycllp_hip_last_error() == bad_argument, name
+    for name in rejected:
+        assert call(handle, flags=getattr(_native, "FLAG_" + name)) == -1 and L.pycllp_hip_last_error() == sentence, name
+    assert fake.raw == bytes(64)

@@ -95,11 +95,16 @@ def _structure(lp):
 
 
 def test_kernel_shape_list_matches_the_dense_kernels():
-    src = lambda f: open(os.path.join(ROOT, "pycllp_amd", "csrc", f)).read()
-    a = re.search(r"#else\s*\n#define GROUP_SHAPES\(X\)(.*)", src("ipm_dense.hip")).group(1)
-    b = re.search(r"#else\s*\n#define GROUP_PA_SHAPES\(X\)(.*)", src("ipm_group_pa.hip")).group(1)
+    csrc = os.path.join(ROOT, "pycllp_amd", "csrc")
+    src = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc"))}
+    a = re.search(r"#else\s*\n#define GROUP_SHAPES\(X\)(.*)", src["group_pa.h"]).group(1)
     shapes = lambda t: [tuple(map(int, s)) for s in re.findall(r"X\((\d+),\s*(\d+)\)", t)]
-    assert shapes(a) == shapes(b) == dbc.GROUP_SHAPES
+    assert shapes(a) == dbc.GROUP_SHAPES
+    # the one list: no translation unit keeps a copy of its own, and all three expand this one
+    defined = {f: set(re.findall(r"#define\s+(GROUP_\w*SHAPES)\b", t)) for f, t in src.items()}
+    assert {f: d for f, d in defined.items() if d} == {"group_pa.h": {"GROUP_SHAPES"}}
+    for f in ("ipm_dense.hip", "ipm_group_pa.hip", "ipm_group_pabd.hip"):
+        assert '#include "group_pa.h"' in src[f] and "GROUP_SHAPES(" in src[f], f
 
 
 def test_init_needs_a_gpu():

@@ -72,14 +72,18 @@ def test_entry_checks_its_arguments_before_any_device_call():
 
 
 def test_kernel_shape_list_matches_the_dense_kernels():
-    src = lambda f: open(os.path.join(ROOT, "pycllp_amd", "csrc", f)).read()
-    a = re.search(r"#else\s*\n#define GROUP_SHAPES\(X\)(.*)", src("ipm_dense.hip")).group(1)
-    b = re.search(r"#else\s*\n#define GROUP_PABD_SHAPES\(X\)(.*)", src("ipm_group_pabd.hip")).group(1)
+    csrc = os.path.join(ROOT, "pycllp_amd", "csrc")
+    src = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc"))}
+    a = re.search(r"#else\s*\n#define GROUP_SHAPES\(X\)(.*)", src["group_pa.h"]).group(1)
     shapes = lambda t: [tuple(map(int, s)) for s in re.findall(r"X\((\d+),\s*(\d+)\)", t)]
-    assert shapes(a) == shapes(b) == gbc.GROUP_SHAPES
-    for dev in ("PYCLLP_DEV_ONLY_3296", "PYCLLP_DEV_ONLY_1648"):       # the development subsets too
-        pick = lambda t, macro: re.search(r"defined\(%s\).*\n#define %s\(X\)(.*)" % (dev, macro), t).group(1)
-        assert shapes(pick(src("ipm_dense.hip"), "GROUP_SHAPES")) == shapes(pick(src("ipm_group_pabd.hip"), "GROUP_PABD_SHAPES"))
+    assert shapes(a) == gbc.GROUP_SHAPES
+    for dev, only in (("PYCLLP_DEV_ONLY_3296", (32, 96)), ("PYCLLP_DEV_ONLY_1648", (16, 48))):     # the development subsets too
+        pick = re.search(r"defined\(%s\).*\n#define GROUP_SHAPES\(X\)(.*)" % dev, src["group_pa.h"]).group(1)
+        assert shapes(pick) == [only] and only in gbc.GROUP_SHAPES
+    # the one list: it is defined in group_pa.h alone (three times: the default and the two subsets), so no unit has a copy
+    defines = {f: re.findall(r"#define\s+(GROUP_\w*SHAPES)\b", t) for f, t in src.items()}
+    assert {f: d for f, d in defines.items() if d} == {"group_pa.h": ["GROUP_SHAPES"] * 3}
+    assert "GROUP_SHAPES(" in src["ipm_group_pabd.hip"] and '#include "group_pa.h"' in src["ipm_group_pabd.hip"]
 
 
 def test_densification_keeps_signs_and_drops_rows():

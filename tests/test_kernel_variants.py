@@ -1,5 +1,5 @@
 """Every compiled instantiation of the wavefront-per-LP kernel (csrc/ipm_wreg_*.hip; shape lists WREG_TAB_SHAPES and
-WREG_DA_SHAPES of csrc/wreg.h) and of the lane-group kernels (GROUP_SHAPES of csrc/ipm_dense.hip) against the CPU references.
+WREG_DA_SHAPES of csrc/wreg.h) and of the lane-group kernels (GROUP_SHAPES of csrc/group_pa.h) against the CPU references.
 
 Each shape is solved at two points of the region it serves first: FULL, its corner (every row and lane live), and RAGGED, one
 row past the previous 16-row block and one column past the previous 64-column register (the last block and the last register
@@ -160,7 +160,7 @@ def image_form(case):
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
 def test_case_table_covers_every_shape_and_kind_of_the_sources():
     lists = {"tables": source_list("wreg.h", "WREG_TAB_SHAPES"), "image": source_list("wreg.h", "WREG_DA_SHAPES"),
-             "group": source_list("ipm_dense.hip", "GROUP_SHAPES"), "slack": source_list("ipm_dense.hip", "GROUP_SHAPES")}
+             "group": source_list("group_pa.h", "GROUP_SHAPES"), "slack": source_list("group_pa.h", "GROUP_SHAPES")}
     for family, shapes in lists.items():
         assert shapes == SHAPES[family], (family, shapes)
         want = {(s, k, p) for s in shapes for k in KINDS[family] for p in ("full", "ragged")}

@@ -12,7 +12,6 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -20,10 +19,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from pycllp_amd import _native  # noqa: E402
 from pycllp_amd.lp import GeneralLP, SparseMatrix  # noqa: E402
 from pycllp_amd.solvers import HipDensePrimalNormalSolver  # noqa: E402
+from timing import BOUNDED_RESULTS, bounded_outputs, timed, write_lines  # noqa: E402
 
 
 def workload(neq, nrng, nle, n, B, seed):
@@ -40,16 +41,6 @@ def workload(neq, nrng, nle, n, B, seed):
     return GeneralLP(SparseMatrix(matrix=A), b, rng.uniform(-1, 1, (B, n)), a=a, l=np.zeros(n), u=u, f=0.0)
 
 
-def timed(fn, runs):
-    fn(); torch.cuda.synchronize()                        # warm-up (and kernel load)
-    ts = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), ts
-
-
 def measure(name, glp, runs):
     dev = torch.device("cuda:0")
     B = glp.nproblems
@@ -60,19 +51,16 @@ def measure(name, glp, runs):
     _native.check(L.pycllp_hip_dense_init(blp.nrows, blp.ncols, ctypes.c_void_p(Ah.data_ptr()), None, ctypes.byref(h)), "init")
     f64 = dict(dtype=torch.float64, device=dev)
     b, c, u = (torch.as_tensor(np.ascontiguousarray(v), **f64) for v in (blp.b, blp.c, blp.u))
-    x, z, s = (torch.empty((B, blp.ncols), **f64) for _ in range(3))
-    y = torch.empty((B, blp.nrows), **f64)
-    po, do = torch.empty(B, **f64), torch.empty(B, **f64)
-    st, it = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+    out = bounded_outputs(B, blp.nrows, blp.ncols, dev)
     o = _native.default_opts()
     P = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
 
     def native():
-        _native.check(L.pycllp_hip_dense_solve_bounded(h, B, P(b), P(c), P(u), P(x), P(y), P(z), P(s), P(po), P(do), P(st), P(it),
+        _native.check(L.pycllp_hip_dense_solve_bounded(h, B, P(b), P(c), P(u), *(P(out[k]) for k in BOUNDED_RESULTS),
                                                        ctypes.byref(o), None), "solve_bounded")
     t_nat, ts_nat = timed(native, runs)
-    st_nat, it_nat = st.cpu().numpy(), it.cpu().numpy()
-    pobj_nat = po.cpu().numpy() + blp.f
+    st_nat, it_nat = out["status"].cpu().numpy(), out["iters"].cpu().numpy()
+    pobj_nat = out["pobj"].cpu().numpy() + blp.f
     L.pycllp_hip_dense_free(h)
 
     eq = glp.to_standard_form().to_equality_form()
@@ -106,10 +94,7 @@ def main():
              json.dumps(measure("12x32 (4 eq, 4 ranged, 4 le), finite u", workload(4, 4, 4, 32, args.B, 2), args.runs))]
     for ln in lines:
         print(ln)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    write_lines(lines, args.out)
 
 
 if __name__ == "__main__":

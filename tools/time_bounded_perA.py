@@ -18,10 +18,8 @@ Device-resident: everything is on the GPU before timing; each path is warmed up,
 synchronise, median of --runs.  A library without the new entry (a build of the parent commit) serves --paths b only.
 """
 import argparse
-import ctypes
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -29,9 +27,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from pycllp_amd import _native  # noqa: E402
 from pycllp_amd.lp import GeneralLP, SparseMatrix  # noqa: E402
+from timing import bounded_outputs, require_entry, stats, timed, write_lines  # noqa: E402
 
 ENTRY = "pycllp_hip_dense_solve_batch_bounded"
 
@@ -50,23 +50,6 @@ def workload(neq, nrng, nle, n, B, seed):
     As = SparseMatrix(np.repeat(np.arange(m), n), np.tile(np.arange(n), m), A.reshape(B, -1))
     As._shape = (m, n)
     return GeneralLP(As, b, rng.uniform(-1, 1, (B, n)), a=a, l=np.zeros(n), u=u, f=0.0)
-
-
-def timed(fn, runs):
-    fn(); torch.cuda.synchronize()                        # warm-up (and kernel load)
-    ts = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), ts
-
-
-def stats(prefix, B, t, ts, status, iters, info):
-    return {prefix + "_B": B, prefix + "_ms": round(t, 3), prefix + "_Mlps": round(B / t / 1e3, 4),
-            prefix + "_runs_ms": [round(v, 3) for v in ts], prefix + "_optimal": int((status == 0).sum()),
-            prefix + "_mean_iters": round(float(iters.mean()), 2), prefix + "_grid": info["grid"],
-            prefix + "_waves_per_cu": info["block"] // 64, prefix + "_lds_bytes": info["lds_bytes"]}
 
 
 def measure(name, glp, Bb, runs, paths):
@@ -93,10 +76,7 @@ def measure(name, glp, Bb, runs, paths):
     if "c" in paths:
         h = Handle(np.ascontiguousarray(blp.A.todense(0)), dev, None)
         b, c, u = t(blp.b), t(blp.c), t(blp.u)
-        f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)   # noqa: E731
-        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)     # noqa: E731
-        rc = dict(x=f64(B, blp.ncols), y=f64(B, blp.nrows), z=f64(B, blp.ncols), s=f64(B, blp.ncols), pobj=f64(B), dobj=f64(B),
-                  status=i32(B), iters=i32(B))
+        rc = bounded_outputs(B, blp.nrows, blp.ncols, dev)
         o = solve_opts({})
         tc, tsc = timed(lambda: h.solve_bounded(None, b, c, u, rc, o), runs)
         ic = h.launch_info()
@@ -133,19 +113,13 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     paths = set(args.paths.split(","))
-    if not hasattr(ctypes.CDLL(_native.LIB_PATH), ENTRY):  # a build of the parent commit: (b) only
-        if paths != {"b"}:
-            raise SystemExit("%s has no %s: it serves --paths b only" % (_native.LIB_PATH, ENTRY))
-        _native.SIGNATURES = tuple(s for s in _native.SIGNATURES if s[0] != ENTRY)
+    require_entry(ENTRY, paths)
     lines = []
     for name, shape, seed in (("24x64 (8 eq, 8 ranged, 8 le), finite u, per-problem A", (8, 8, 8, 64), 1),
                               ("12x32 (4 eq, 4 ranged, 4 le), finite u, per-problem A", (4, 4, 4, 32), 2)):
         lines.append(json.dumps(measure(name, workload(*shape, args.B, seed), min(args.Bb, args.B), args.runs, paths)))
         print(lines[-1], flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    write_lines(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -20,7 +20,6 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -29,10 +28,13 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from pycllp_amd import _native  # noqa: E402
 from pycllp_amd.lp import GeneralLP, SparseMatrix  # noqa: E402
 from pycllp_amd.solvers import HipDensePrimalNormalSolver  # noqa: E402
+from pycllp_amd.solvers.hip import RESULTS  # noqa: E402
+from timing import BOUNDED_RESULTS, bounded_outputs, timed, write_lines  # noqa: E402
 
 
 def workload(neq, nrng, nle, n, B, seed, density=1.0):
@@ -51,16 +53,6 @@ def workload(neq, nrng, nle, n, B, seed, density=1.0):
     return GeneralLP(SparseMatrix(matrix=A), b, rng.uniform(-1, 1, (B, n)), a=a, l=np.zeros(n), u=u, f=0.0)
 
 
-def timed(fn, runs):
-    fn(); torch.cuda.synchronize()                        # warm-up (and kernel load, plan build)
-    ts = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), ts
-
-
 class Sparse:
     """A sparse handle for A^ and device buffers for B LPs."""
 
@@ -76,14 +68,9 @@ class Sparse:
         self.h = ctypes.c_void_p()
         _native.check(self.L.pycllp_hip_sparse_init(A.shape[0], A.shape[1], int(A.nnz), *(self.P(t) for t in self._a), None,
                                                     ctypes.byref(self.h)), "pycllp_hip_sparse_init")
-        B, m, N = blp.nproblems, blp.nrows, blp.ncols
-        self.B = B
+        self.B = blp.nproblems
         self.b, self.c, self.u = (torch.as_tensor(np.ascontiguousarray(v), **f64) for v in (blp.b, blp.c, blp.u))
-        self.x, self.z, self.s = (torch.empty((B, N), **f64) for _ in range(3))
-        self.y = torch.empty((B, m), **f64)
-        self.po, self.do = torch.empty(B, **f64), torch.empty(B, **f64)
-        self.st = torch.empty(B, dtype=torch.int32, device=self.dev)
-        self.it = torch.empty(B, dtype=torch.int32, device=self.dev)
+        self.out = bounded_outputs(self.B, blp.nrows, blp.ncols, self.dev)
         self.o = _native.default_opts()
 
     def set_c(self, c):
@@ -95,15 +82,14 @@ class Sparse:
 
     def bounded(self):
         P = self.P
-        _native.check(self.L.pycllp_hip_sparse_solve_bounded(self.h, self.B, P(self.b), P(self.c), P(self.u), P(self.x), P(self.y),
-                                                             P(self.z), P(self.s), P(self.po), P(self.do), P(self.st), P(self.it),
+        _native.check(self.L.pycllp_hip_sparse_solve_bounded(self.h, self.B, P(self.b), P(self.c), P(self.u),
+                                                             *(P(self.out[k]) for k in BOUNDED_RESULTS),
                                                              ctypes.byref(self.o), None), "pycllp_hip_sparse_solve_bounded")
 
     def plain(self):
         P = self.P
-        _native.check(self.L.pycllp_hip_sparse_solve(self.h, self.B, P(self.b), P(self.c), P(self.x), P(self.y), P(self.z),
-                                                     P(self.po), P(self.do), P(self.st), P(self.it), ctypes.byref(self.o), None),
-                      "pycllp_hip_sparse_solve")
+        _native.check(self.L.pycllp_hip_sparse_solve(self.h, self.B, P(self.b), P(self.c), *(P(self.out[k]) for k in RESULTS),
+                                                     ctypes.byref(self.o), None), "pycllp_hip_sparse_solve")
 
     def info(self):
         g, bl, lds, k = (ctypes.c_int() for _ in range(4))
@@ -111,9 +97,9 @@ class Sparse:
         return dict(grid=g.value, block=bl.value, lds_bytes=lds.value, kernel={1: "tables", 2: "dense image"}.get(k.value, k.value))
 
     def results(self):
-        st, it = self.st.cpu().numpy(), self.it.cpu().numpy()
+        st, it = self.out["status"].cpu().numpy(), self.out["iters"].cpu().numpy()
         return dict(optimal=int((st == 0).sum()), statuses={int(k): int(v) for k, v in zip(*np.unique(st, return_counts=True))},
-                    mean_iters=round(float(it.mean()), 2)), self.po.cpu().numpy()
+                    mean_iters=round(float(it.mean()), 2)), self.out["pobj"].cpu().numpy()
 
     def free(self):
         self.L.pycllp_hip_sparse_free(self.h)
@@ -124,7 +110,7 @@ def native(name, glp, runs, expand=True, plain=False):
     S = Sparse(blp)
     t_nat, ts_nat = timed(S.bounded, runs)
     res, pobj_nat = S.results()
-    st_nat = S.st.cpu().numpy()
+    st_nat = S.out["status"].cpu().numpy()
     out = dict(workload=name, B=S.B, rows=glp.nrows, cols=glp.ncols, native_m=blp.nrows, native_N=blp.ncols,
                native_ms=round(t_nat, 3), native_Mlps=round(S.B / t_nat / 1e3, 3), native=res, native_launch=S.info(),
                native_runs_ms=[round(v, 3) for v in ts_nat])
@@ -172,10 +158,7 @@ def main():
                                workload(32, 32, 32, 288, args.B, 2, density=0.03), args.runs, expand=False))]
     for ln in lines:
         print(ln, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    write_lines(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -20,7 +20,6 @@ Device-resident: everything is on the GPU before timing; each path is warmed up,
 synchronise, median of --runs.  A library without the new entry (a build of the parent commit) serves --paths b only.
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -35,7 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from pycllp_amd import _native  # noqa: E402
 from pycllp_amd.lp import GeneralLP, SparseMatrix  # noqa: E402
-from time_bounded_perA import stats, timed  # noqa: E402
+from timing import bounded_outputs, require_entry, stats, timed, write_lines  # noqa: E402
 
 ENTRY = "pycllp_hip_sparse_solve_batch_bounded"
 
@@ -83,10 +82,7 @@ def measure(name, glp, Bb, runs, paths):
         A0.sum_duplicates(); A0.sort_indices()
         h = Handle(A0, dev, None)
         b, c, u = t(blp.b), t(blp.c), t(blp.u)
-        f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)   # noqa: E731
-        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)     # noqa: E731
-        rc = dict(x=f64(B, blp.ncols), y=f64(B, blp.nrows), z=f64(B, blp.ncols), s=f64(B, blp.ncols), pobj=f64(B), dobj=f64(B),
-                  status=i32(B), iters=i32(B))
+        rc = bounded_outputs(B, blp.nrows, blp.ncols, dev)
         o = solve_opts({})
         tc, tsc = timed(lambda: h.solve_bounded(None, b, c, u, rc, o), runs)
         ic = h.launch_info()
@@ -124,19 +120,13 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     paths = set(args.paths.split(","))
-    if not hasattr(ctypes.CDLL(_native.LIB_PATH), ENTRY):  # a build of the parent commit: (b) only
-        if paths != {"b"}:
-            raise SystemExit("%s has no %s: it serves --paths b only" % (_native.LIB_PATH, ENTRY))
-        _native.SIGNATURES = tuple(s for s in _native.SIGNATURES if s[0] != ENTRY)
+    require_entry(ENTRY, paths)
     lines = []
     for name, shape, seed, density in (("96x288 (32 eq, 32 ranged, 32 le) at 3 %, finite u, per-problem values", (32, 32, 32, 288), 2, 0.03),
                                        ("48x128 (16 eq, 16 ranged, 16 le) at 10 %, finite u, per-problem values", (16, 16, 16, 128), 3, 0.10)):
         lines.append(json.dumps(measure(name, workload(*shape, args.B, seed, density), min(args.Bb, args.B), args.runs, paths)))
         print(lines[-1], flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    write_lines(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -16,7 +16,6 @@ a synchronise, median of --runs.
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -25,20 +24,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from pycllp_amd import problems  # noqa: E402
 from pycllp_amd.lp import EqualityLP, SparseMatrix, StandardLP  # noqa: E402
 from pycllp_amd.solvers import solver_registry  # noqa: E402
-
-
-def timed(fn, runs):
-    fn(); torch.cuda.synchronize()                        # warm-up (and kernel load)
-    ts = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), ts
+from timing import timed, write_lines  # noqa: E402
 
 
 def waves(info):
@@ -114,10 +105,7 @@ def main():
         m, n = map(int, s.split("x"))
         lines.append(json.dumps(measure(m, n, args.B, args.runs)))
         print(lines[-1], flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    write_lines(lines, args.out)
 
 
 if __name__ == "__main__":
