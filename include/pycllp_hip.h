@@ -332,6 +332,47 @@ int pycllp_hip_sparse_variant_info(const pycllp_hip_sparse *handle, int *mb, int
 int pycllp_hip_sparse_plan_info(const pycllp_hip_sparse *handle, int *wgpc, int *bnc, int *factor_in_lds, int *a_in_lds);
 void pycllp_hip_sparse_free(pycllp_hip_sparse *handle);
 
+/* ---- GeneralLP batches to and from the bounded equality form, on the device ----
+ * B LPs  optimise c'x + f  s.t.  a <= A x <= b,  l <= x <= u  with one shared A [m, n] become the LPs  max c^'x^ + f^  s.t.
+ * [+-A | I] x^ = b^,  0 <= x^ <= u^  that pycllp_hip_dense_solve_bounded / pycllp_hip_sparse_solve_bounded take, and their
+ * solutions the GeneralLP's: GeneralLP.to_bounded_equality_form and BoundedMap.general of pycllp_amd/lp.py as two kernels.  No
+ * handle.  The plan that is one for the batch comes from the caller (GeneralLP.bounded_structure, lp.bounded_rowmap):
+ *   rowmap_dev [m] i32   for row i of the LP: k + 1 where it is row k of the bounded form with +A (b finite in every LP),
+ *                        -(k + 1) where it is row k with -A (b = +inf, a finite in every LP), 0 where it is dropped (neither
+ *                        bound finite in any LP); k = 0 .. mk-1 in the order of the rows.  N = n + mk columns, slacks last.
+ *   Adata_dev f64 [nnz], Aindptr_dev i32 [m+1], Aindices_dev i32 [nnz]   CSR of the ORIGINAL A; a row's terms are summed in
+ *                        the order they stand in (SparseMatrix.csr_term_order: that of the coordinate lists, so the sums carry
+ *                        the host's bits).  With nnz = 0 the two [nnz] arrays may be NULL.
+ * pycllp_hip_general_to_bounded:  a_dev, b_dev [B,m], c_dev, l_dev, u_dev [B,n], f_dev [B]  (l_dev, f_dev may be NULL = 0;
+ * a non-finite a means "no lower bound") ->
+ *   bh_dev [B,mk]        b - A l for a + row, -(a - A l) for a - row; A l = the sequential sum of the separately rounded products
+ *   ch_dev [B,N]         [c | 0]
+ *   uh_dev [B,N]         u - l where u is finite, else +inf; the slack of a + row (b - A l) - (a - A l) where a is finite, else
+ *                        +inf; the slack of a - row +inf.  0 = fixed (l == u, an equality row's slack)
+ *   fh_dev [B]           f + c'l (summed in an order of the kernel's own: not the host's bits, to rounding)
+ *   invalid_dev [B] i32  0, or the first check LP k fails: 1 a non-finite l, 2 u < l, 3 a > b with a finite, 4 a row whose finite
+ *                        bounds do not match rowmap (+: b finite; -: b = +inf and a finite; dropped: neither finite), 5 a
+ *                        non-finite c or f.  Such an LP is replaced by a harmless one -- b^ = A^ 1 (row sums, slack included),
+ *                        c^ = 0, u^ = +inf, f^ = 0: x^ = 1 is feasible and optimal -- so that no solve kernel meets a NaN.
+ * pycllp_hip_general_from_bounded:  xh_dev, zh_dev, sh_dev [B,N], yh_dev [B,mk] as a bounded solve entry wrote them, l_dev (may
+ * be NULL = 0), fh_dev and invalid_dev as above ->
+ *   x_dev [B,n] = l + x^;  y_dev [B,m] = +-y^ by rowmap, 0 for a dropped row;  z_dev, s_dev [B,n] (optional) the first n columns
+ *   of z^, s^ (zh_dev / sh_dev may be NULL, then z_dev / s_dev must be);  pobj_dev, dobj_dev [B] (optional, IN/OUT) += f^;
+ *   status_dev, iters_dev (optional) [B] i32 IN/OUT: left as the solve wrote them, except that an LP with invalid != 0 gets
+ *   status PYCLLP_STATUS_NUMERICAL, iters 0 and quiet NaNs in x, y, z, s, pobj, dobj.
+ * Both: PYCLLP_E_BADARG for a NULL required pointer, m, n or mk < 1, mk > m, B < 0 or nnz < 0, PYCLLP_E_UNSUPPORTED for
+ * m > 256 or n + mk > 1280 (beyond every bounded solve entry), all before any HIP call; B = 0 returns 0 and launches nothing.
+ * One launch each, asynchronous on `stream`; alignment and footprint as stated at the top. */
+int pycllp_hip_general_to_bounded(int m, int n, int mk, long B, const int *rowmap_dev, int nnz, const double *Adata_dev,
+                                  const int *Aindptr_dev, const int *Aindices_dev, const double *a_dev, const double *b_dev,
+                                  const double *c_dev, const double *l_dev, const double *u_dev, const double *f_dev,
+                                  double *bh_dev, double *ch_dev, double *uh_dev, double *fh_dev, int *invalid_dev, void *stream);
+int pycllp_hip_general_from_bounded(int m, int n, int mk, long B, const int *rowmap_dev, const double *l_dev,
+                                    const double *fh_dev, const int *invalid_dev, const double *xh_dev, const double *yh_dev,
+                                    const double *zh_dev, const double *sh_dev, double *x_dev, double *y_dev, double *z_dev,
+                                    double *s_dev, double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
+                                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

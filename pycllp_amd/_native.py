@@ -62,6 +62,10 @@ SIGNATURES = (
     ("pycllp_hip_sparse_launch_info", [_p] + [_ip] * 4, _i), ("pycllp_hip_sparse_variant_info", [_p] + [_ip] * 2, _i),
     ("pycllp_hip_sparse_plan_info", [_p] + [_ip] * 4, _i),
     ("pycllp_hip_sparse_free", [_p], None),
+    # m, n, mk, B, rowmap, nnz, A's CSR (3), a, b, c, l, u, f, then b^, c^, u^, f^, invalid, stream
+    ("pycllp_hip_general_to_bounded", [_i, _i, _i, _l, _p, _i] + [_p] * 14 + [_p], _i),
+    # m, n, mk, B, rowmap, l, f^, invalid, x^, y^, z^, s^, then x, y, z, s, pobj, dobj, status, iters, stream
+    ("pycllp_hip_general_from_bounded", [_i, _i, _i, _l] + [_p] * 16 + [_p], _i),
 )
 EXPORTS = tuple(name for name, _, _ in SIGNATURES)
 

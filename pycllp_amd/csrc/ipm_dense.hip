@@ -25,6 +25,7 @@
 // OpenCL kernel, Nocedal-Wright diagonal guard, |r|-driven iterative refinement, NaN guard.
 #include "wreg.h"
 #include "big.h"
+#include "host_error.h"
 #include <mutex>
 
 // ------------------------------------------------------------------------------------------------
@@ -768,6 +769,9 @@ static int entry_err(int code, const char* entry, const char* what) {
     snprintf(g_err, sizeof(g_err), "%s: %s", entry, what);
     return code;
 }
+
+int pycllp_entry_error(int code, const char* entry, const char* what) { return entry_err(code, entry, what); }   // host_error.h
+int pycllp_runtime_error(int code, const char* what) { return set_err(code, what); }
 
 // The argument checks that open the five restricted entries (pycllp_hip_dense_solve_bounded, _dense_solve_batch,
 // _dense_solve_batch_bounded, _sparse_solve_bounded, _sparse_solve_batch_bounded), in their order: the handle and B with the

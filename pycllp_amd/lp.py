@@ -91,6 +91,15 @@ class SparseMatrix(object):
     def todense(self, problem=0):
         return np.asarray(self.tocoo(problem).todense())
 
+    def csr_term_order(self, problem=0):
+        """(data f64 [nnz], indptr i32 [nrows + 1], indices i32 [nnz]): the CSR arrays with the terms of a row in the order of
+        the coordinate lists (a stable sort by row; duplicates stay apart) -- the order in which a product with this matrix sums
+        them on the host, and what ``pycllp_hip_general_to_bounded`` takes."""
+        order = np.argsort(self._rows, kind="stable")
+        indptr = np.concatenate([[0], np.cumsum(np.bincount(self._rows, minlength=self.nrows))])
+        return (np.ascontiguousarray(self.data[problem][order], dtype=np.float64), indptr.astype(np.int32),
+                self._cols[order].astype(np.int32))
+
 
 class EqualityLP(object):
     """maximise c'x + f  subject to  A x = b, x >= 0   (``pycllp/lp.py:306-330``)."""
@@ -216,33 +225,24 @@ class GeneralLP(StandardLP):
         A2._shape = (bb.shape[1], n)
         return StandardLP(A2, bb, c, f)
 
-    def to_bounded_equality_form(self):
-        """(``BoundedEqualityLP``, ``BoundedMap``): the LP  max c^'x^ + f^  s.t.  A^ x^ = b^,  0 <= x^ <= u^  with the same
-        optimum, for the bounded kernel (``HipGeneralPrimalNormalSolver``).  Unlike ``to_standard_form`` it adds no row per upper
-        bound and no second row per ranged or equality row:
-          * x = l + x^:  b^ = b - A l,  a^ = a - A l,  f^ = f + c'l;
-          * one sign per row for the whole batch: b finite for every LP keeps +A (its slack gets the upper bound b^ - a^, +inf
-            where a is not finite, 0 for an equality row); b = +inf and a finite for every LP keeps -A with right-hand side
-            -a^ and an unbounded slack; a row without either bound in every LP is dropped; any other mix raises ``ValueError``;
-          * A^ = [+-A | I]: one +1 slack column per kept row, slacks last;  u^_j = u_j - l_j for the columns, +inf for none.
-        u^ = 0 marks a fixed variable (a column with l == u, the slack of an equality row).  A non-finite ``a`` of either sign
-        means "no lower bound" (the reference stores +inf there, this package -inf)."""
+    def check_bounds(self):
+        """The ``ValueError``s of ``to_bounded_equality_form`` about single bounds: l = -inf, u < l, a > b."""
         if np.isneginf(self.l).any():
             raise ValueError('Lower bounds (l) contains -inf.')
         if (self.u < self.l).any():
             raise ValueError('Upper bounds (u) below lower bounds (l).')
-        afin0 = np.isfinite(self.a)
-        if (afin0 & (self.a > self.b)).any():
+        if (np.isfinite(self.a) & (self.a > self.b)).any():
             raise ValueError('Row lower bounds (a) above row upper bounds (b).')
-        m, n, B = self.nrows, self.ncols, self.nproblems
+
+    def bounded_structure(self):
+        """(A^, keep, sign): the part of ``to_bounded_equality_form`` that is one for the whole batch -- which rows are kept
+        (``keep``: their indices; a row without a bound in every LP is dropped), with which sign (``sign``: +1.0 where b is
+        finite for every LP, -1.0 where b = +inf and a is finite for every LP; any other mix raises ``ValueError``) and the
+        matrix A^ = [+-A | I] as a ``SparseMatrix``.  It reads only which bounds are finite and A: a few reductions and work
+        proportional to nnz, no product with l."""
+        m, n = self.nrows, self.ncols
         rows, cols, data = self.A._rows, self.A._cols, self.A.data
-        l = self.l
-        # A l for every LP in one product: per-problem values (data [B, nnz]) or one shared set (data [1, nnz])
-        S = sp.csr_matrix((np.ones(rows.size), (np.arange(rows.size), rows)), shape=(rows.size, m))
-        Al = np.asarray((S.T @ (data * l[:, cols]).T).T)
-        bh, ah = self.b - Al, self.a - Al
-        f = self.f + (self.c * l).sum(axis=1)
-        bfin, afin = np.isfinite(self.b), afin0
+        bfin, afin = np.isfinite(self.b), np.isfinite(self.a)
         plus = bfin.all(axis=0)
         minus = ~bfin.any(axis=0) & afin.all(axis=0)
         drop = ~bfin.any(axis=0) & ~afin.any(axis=0)
@@ -260,9 +260,33 @@ class GeneralLP(StandardLP):
         A2 = SparseMatrix(np.concatenate([newrow[rows[sel]], np.arange(mk)]), np.concatenate([cols[sel], n + np.arange(mk)]),
                           np.concatenate([rsign * data[:, sel], np.ones((data.shape[0], mk))], axis=1))
         A2._shape = (mk, n + mk)
-        b2 = np.where(plus[keep], bh[:, keep], -ah[:, keep])
+        return A2, keep, sign
+
+    def to_bounded_equality_form(self):
+        """(``BoundedEqualityLP``, ``BoundedMap``): the LP  max c^'x^ + f^  s.t.  A^ x^ = b^,  0 <= x^ <= u^  with the same
+        optimum, for the bounded kernel (``HipGeneralPrimalNormalSolver``).  Unlike ``to_standard_form`` it adds no row per upper
+        bound and no second row per ranged or equality row:
+          * x = l + x^:  b^ = b - A l,  a^ = a - A l,  f^ = f + c'l;
+          * one sign per row for the whole batch: b finite for every LP keeps +A (its slack gets the upper bound b^ - a^, +inf
+            where a is not finite, 0 for an equality row); b = +inf and a finite for every LP keeps -A with right-hand side
+            -a^ and an unbounded slack; a row without either bound in every LP is dropped; any other mix raises ``ValueError``;
+          * A^ = [+-A | I]: one +1 slack column per kept row, slacks last;  u^_j = u_j - l_j for the columns, +inf for none.
+        u^ = 0 marks a fixed variable (a column with l == u, the slack of an equality row).  A non-finite ``a`` of either sign
+        means "no lower bound" (the reference stores +inf there, this package -inf)."""
+        self.check_bounds()
+        m, n, B = self.nrows, self.ncols, self.nproblems
+        rows, cols, data = self.A._rows, self.A._cols, self.A.data
+        l = self.l
+        # A l for every LP in one product: per-problem values (data [B, nnz]) or one shared set (data [1, nnz])
+        S = sp.csr_matrix((np.ones(rows.size), (np.arange(rows.size), rows)), shape=(rows.size, m))
+        Al = np.asarray((S.T @ (data * l[:, cols]).T).T)
+        bh, ah = self.b - Al, self.a - Al
+        f = self.f + (self.c * l).sum(axis=1)
+        A2, keep, sign = self.bounded_structure()
+        plus, mk = sign > 0, keep.size
+        b2 = np.where(plus, bh[:, keep], -ah[:, keep])
         with np.errstate(invalid="ignore"):
-            us = np.where(plus[keep], np.where(np.isfinite(ah[:, keep]), bh[:, keep] - ah[:, keep], np.inf), np.inf)
+            us = np.where(plus, np.where(np.isfinite(ah[:, keep]), bh[:, keep] - ah[:, keep], np.inf), np.inf)
         u2 = np.concatenate([np.where(np.isfinite(self.u), self.u - l, np.inf), us], axis=1)
         c2 = np.concatenate([self.c, np.zeros((B, mk))], axis=1)
         return BoundedEqualityLP(A2, b2, c2, f, u2), BoundedMap(l.copy(), keep, sign, m)
@@ -274,6 +298,14 @@ class BoundedEqualityLP(EqualityLP):
     def __init__(self, A=None, b=None, c=None, f=None, u=None):
         super(BoundedEqualityLP, self).__init__(A=A, b=b, c=c, f=f)
         self.u = np.full(self.c.shape, np.inf) if u is None else np.array(u, dtype=np.float64).reshape(self.c.shape)
+
+
+def bounded_rowmap(keep, sign, m):
+    """``keep`` and ``sign`` of ``GeneralLP.bounded_structure()`` as the one array the device conversion takes (i32 [m]): for
+    row i of the GeneralLP k + 1 where it is row k of the bounded form with +A, -(k + 1) where with -A, 0 where it is dropped."""
+    rowmap = np.zeros(m, dtype=np.int32)
+    rowmap[keep] = np.where(np.asarray(sign) > 0, 1, -1) * (np.arange(len(keep)) + 1)
+    return rowmap
 
 
 class BoundedMap(object):

@@ -10,13 +10,21 @@ library takes.  ``kernel`` tells which path served the last ``solve``: ``'bounde
 ``hip_sparse_general_primal_normal`` is the same plugin on the bounded one-LP-per-wavefront kernel
 (``pycllp_hip_sparse_solve_bounded``, csrc/ipm_wreg_bounded.inc): any shared A^ with m' <= 128 kept rows and N <= 512 columns
 that a variant of that kernel covers (``kernel == 'bounded wave'``), sparse or dense, the expansion for the rest.
+
+On the native path the batch is converted ON THE DEVICE (``DeviceConversion``: ``pycllp_hip_general_to_bounded`` before the solve,
+``pycllp_hip_general_from_bounded`` behind it, csrc/general_form.hip): the host only classifies the rows
+(``GeneralLP.bounded_structure``), ``solve(lp)`` uploads a, b, c, l, u and downloads results of the original size, and
+``solve_device`` is the same chain on tensors, in the ORIGINAL variables.
 """
+import contextlib
+import ctypes
+
 import numpy as np
 import torch
 
 from . import BaseGeneralSolver
 from .. import _native
-from ..lp import GeneralLP, SparseMatrix
+from ..lp import GeneralLP, SparseMatrix, bounded_rowmap
 from .hip import (DeviceArrays, Handle, HipDensePrimalNormalSolver, _require_gpu, autoscale_wanted, bounded_outputs,
                   plugin_options, solve_opts)
 
@@ -55,6 +63,49 @@ def download_bounded(out, blp, bmap, device):
     return dict(x=xo, y=yo, z=zo, s=so, status=r["status"], iters=r["iters"], primal_obj=r["pobj"] + f, dual_obj=r["dobj"] + f)
 
 
+class DeviceConversion(object):
+    """The plan of ``GeneralLP.bounded_structure()`` on ``device`` -- the row map and the CSR of the ORIGINAL shared A, terms in
+    the order of its coordinate lists -- and the two entries that work by it.  The calls take contiguous float64 CUDA tensors
+    and the stream to queue on (None: torch's current stream on ``device``); nothing is synchronised."""
+
+    def __init__(self, glp, keep, sign, device):
+        self.m, self.n, self.mk, self.device = glp.nrows, glp.ncols, len(keep), device
+        data, indptr, indices = glp.A.csr_term_order()
+        self.nnz = int(data.size)
+        self.rowmap, self.data, self.indptr, self.indices = (
+            torch.as_tensor(v, device=device) for v in (bounded_rowmap(keep, sign, self.m), data, indptr, indices))
+
+    def _call(self, name, stream, sizes, arrays):
+        st = ctypes.c_void_p((stream if stream is not None else torch.cuda.current_stream(self.device)).cuda_stream)
+        args = [ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in arrays]     # (None: NULL)
+        with torch.cuda.device(self.device):
+            _native.check(getattr(_native.lib(), name)(*sizes, *args, st), name)
+
+    def to_bounded(self, stream, a, b, c, l, u, f=None):
+        """a, b [B, m], c, l, u [B, n], f [B] (l, f: None = 0) -> dict b [B, m'], c, u [B, N], f [B], invalid [B] (i32)."""
+        B, N = int(a.shape[0]), self.n + self.mk
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)     # noqa: E731
+        cv = dict(b=new(B, self.mk), c=new(B, N), u=new(B, N), f=new(B), invalid=torch.empty(B, dtype=torch.int32, device=self.device))
+        if B:
+            self._call("pycllp_hip_general_to_bounded", stream, (self.m, self.n, self.mk, B),
+                       (self.rowmap, self.nnz, self.data, self.indptr, self.indices, a, b, c, l, u, f,
+                        cv["b"], cv["c"], cv["u"], cv["f"], cv["invalid"]))
+        return cv
+
+    def from_bounded(self, stream, l, f, invalid, out):
+        """The outputs ``out`` of a bounded solve (``bounded_outputs``) -> dict of ``RESULTS`` in the GeneralLP's variables plus
+        ``invalid``; ``primal_obj``, ``dual_obj``, ``status`` and ``iters`` are ``out``'s own tensors, updated in place."""
+        B = int(out["x"].shape[0])
+        new = lambda cols: torch.empty((B, cols), dtype=torch.float64, device=self.device)     # noqa: E731
+        res = dict(x=new(self.n), y=new(self.m), z=new(self.n), s=new(self.n), status=out["status"], iters=out["iters"],
+                   primal_obj=out["pobj"], dual_obj=out["dobj"], invalid=invalid)
+        if B:
+            self._call("pycllp_hip_general_from_bounded", stream, (self.m, self.n, self.mk, B),
+                       (self.rowmap, l, f, invalid, out["x"], out["y"], out["z"], out["s"], res["x"], res["y"], res["z"],
+                        res["s"], out["pobj"], out["dobj"], out["status"], out["iters"]))
+        return res
+
+
 class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
     """``glp.init(s); glp.solve(s)`` on a ``GeneralLP``; results in the ORIGINAL variables: ``x [B, n]``, ``y [B, m]`` (one
     per row of the LP, 0 for a row without bounds), ``z`` / ``s [B, n]`` (duals of x >= l / x <= u), ``status``, ``iters``,
@@ -82,48 +133,88 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
         self.device, self.stream = device, stream
         self._handle = None
         self._key = None
+        self._conv = None
+        self._keepalive = None
         self.kernel = None
 
     @staticmethod
     def native_fits(glp, blp):
+        """``blp``: the bounded form, or its matrix alone (``GeneralLP.bounded_structure``)."""
         return glp.A.nproblems == 1 and 1 <= blp.nrows <= NATIVE_MAX_ROWS and glp.ncols <= NATIVE_MAX_COLS
 
     @staticmethod
-    def _bounded_matrix(blp):
+    def _bounded_matrix(Ah):
         """(A^ as the handle of the native kernel takes it -- dense --, a key that tells whether A^ changed)."""
-        A = np.ascontiguousarray(blp.A.todense(), dtype=np.float64)
+        A = np.ascontiguousarray(Ah.todense(), dtype=np.float64)
         return A, (A.shape, A.tobytes())
 
-    def _ensure_handle(self, blp):
-        """A handle for A^ (re-made when A^ changed since the last one); False if the library declines it."""
-        A, key = self._bounded_matrix(blp)
+    def _ensure_handle(self, glp, Ah, keep, sign):
+        """A handle for A^ and the device conversion's plan beside it (both re-made when A, or which rows are kept with which
+        sign, changed since the last ones); False if the library declines A^."""
+        A, key = self._bounded_matrix(Ah)
+        key = (key, keep.tobytes(), sign.tobytes(), glp.A._rows.tobytes(), glp.A._cols.tobytes(), glp.A.data.tobytes())
         if self._handle is not None and self._key == key:
             return True
-        self._handle = self._key = None
+        self._handle = self._key = self._conv = None
         try:
             self._handle = Handle(A, self.device, self.stream)
         except NotImplementedError:
             return False
+        self._conv = DeviceConversion(glp, keep, sign, self.device)
         self._key = key
         return True
+
+    def _on_stream(self):
+        """Context in which torch's own work (allocations, the band test) is queued on the stream the entries are given."""
+        return torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
 
     # -- plugin API ------------------------------------------------------------------------------
     def init(self, lp, verbose=0):
         self.device = _require_gpu(self.device)
         glp = as_general(lp)
-        blp, _ = glp.to_bounded_equality_form()
-        if self.native_fits(glp, blp):
-            self._ensure_handle(blp)
+        glp.check_bounds()
+        Ah, keep, sign = glp.bounded_structure()
+        if not (self.native_fits(glp, Ah) and self._ensure_handle(glp, Ah, keep, sign)):
+            self._handle = self._key = self._conv = None
         self.m, self.n = glp.nrows, glp.ncols
+
+    def solve_device(self, a, b, c, l, u, f=None, **options):
+        """Device-resident entry, in the ORIGINAL variables: a, b [B, m], c, l, u [B, n], f [B] (torch CUDA tensors, or numpy
+        arrays, which are uploaded; ``l`` and ``f`` may be None = 0) -> dict of CUDA tensors: ``RESULTS`` and ``invalid`` (i32
+        [B]: 0, or the check of ``pycllp_hip_general_to_bounded`` the LP failed; such an LP has status 3 and NaN results).
+        Conversion, bounded solve and back-conversion are queued on the solver's stream and nothing waits for them; the kernel's
+        verdict stands (no look at the data: ``autoscale='auto'`` and ``hsd='auto'`` count as off).  ``options``: fields of
+        ``pycllp_hip_opts`` for this call."""
+        if self._handle is None or self._conv is None:
+            raise RuntimeError("solve_device() needs init() on an LP the %s kernel serves (after init() the LP takes the "
+                               "expansion)" % self._native_kernel)
+        cv = self._conv
+        with self._on_stream():
+            a, b, c, u = (self._dev(v) for v in (a, b, c, u))
+            l, f = (None if v is None else self._dev(v) for v in (l, f))
+            B = int(a.shape[0]) if a.dim() == 2 else -1
+            if (tuple(a.shape) != (B, cv.m) or tuple(b.shape) != (B, cv.m) or any(tuple(v.shape) != (B, cv.n) for v in (c, u))
+                    or (l is not None and tuple(l.shape) != (B, cv.n)) or (f is not None and tuple(f.shape) != (B,))):
+                raise ValueError("a and b must be [B,%d], c, l and u [B,%d] and f [B] with equal B" % (cv.m, cv.n))
+            o = solve_opts(self.options, 0, **options)
+            bl = cv.to_bounded(self.stream, a, b, c, l, u, f)
+            out = bounded_outputs(B, cv.mk, cv.n + cv.mk, self.device)
+            if B:
+                self._handle.solve_bounded(self.stream, bl["b"], bl["c"], bl["u"], out, o)
+            res = cv.from_bounded(self.stream, l, bl["f"], bl["invalid"], out)
+        self._keepalive = (a, b, c, l, u, f, bl, out)
+        self.kernel = self._native_kernel
+        return res
 
     def solve(self, lp, verbose=0):
         glp = as_general(lp)
         if glp.nrows != self.m or glp.ncols != self.n:
             raise ValueError("LP shape changed since init(): (%d,%d) vs (%d,%d)" % (glp.nrows, glp.ncols, self.m, self.n))
-        blp, bmap = glp.to_bounded_equality_form()
+        glp.check_bounds()
+        Ah, keep, sign = glp.bounded_structure()
         res = None
-        if self.native_fits(glp, blp) and self._ensure_handle(blp):
-            res = self._solve_bounded(blp, bmap)
+        if self.native_fits(glp, Ah) and self._ensure_handle(glp, Ah, keep, sign):
+            res = self._solve_native(glp)
         if res is None:
             self.kernel = "expanded"
             res = self.solve_expanded(glp)
@@ -147,17 +238,26 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
         """``Handle.launch_info()`` of the native kernel's last launch (None when no handle serves the LP)."""
         return None if self._handle is None else self._handle.launch_info()
 
-    def _solve_bounded(self, blp, bmap):
-        """One upload, one launch of the bounded kernel, one download; None if the library declines A^ (PYCLLP_E_UNSUPPORTED)."""
-        wanted = self.autoscale == "auto" and autoscale_wanted(blp.b, blp.c, blp.u)
-        o = solve_opts(self.options, _native.FLAG_AUTOSCALE if wanted else 0)
-        b, c, u = (torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64, device=self.device) for v in (blp.b, blp.c, blp.u))
-        out = bounded_outputs(blp.nproblems, blp.nrows, blp.ncols, self.device)
-        try:
-            self._handle.solve_bounded(self.stream, b, c, u, out, o)
-        except NotImplementedError:
-            return None
-        return download_bounded(out, blp, bmap, self.device)
+    def _solve_native(self, glp):
+        """One upload of a, b, c, l, u; conversion, bounded kernel and back-conversion on the device; one download of the results
+        in the GeneralLP's variables.  None if the library declines A^ (PYCLLP_E_UNSUPPORTED).  ``autoscale='auto'`` is decided
+        from the device's b^, c^, u^ (``autoscale_wanted``: a comparison of maxima, the answer the host's arrays give); the
+        objectives' offset f + c'l is the host's sum, so every result carries the bits of the host conversion."""
+        cv, B = self._conv, glp.nproblems
+        offset = np.broadcast_to(glp.f, (B,)) + (glp.c * glp.l).sum(axis=1)
+        with self._on_stream():
+            a, b, c, l, u, fh = (self._dev(np.ascontiguousarray(v)) for v in (glp.a, glp.b, glp.c, glp.l, glp.u, offset))
+            bl = cv.to_bounded(self.stream, a, b, c, l, u)
+            wanted = self.autoscale == "auto" and autoscale_wanted(bl["b"], bl["c"], bl["u"])
+            o = solve_opts(self.options, _native.FLAG_AUTOSCALE if wanted else 0)
+            out = bounded_outputs(B, cv.mk, cv.n + cv.mk, self.device)
+            try:
+                self._handle.solve_bounded(self.stream, bl["b"], bl["c"], bl["u"], out, o)
+            except NotImplementedError:
+                return None
+            res = cv.from_bounded(self.stream, l, fh, bl["invalid"], out)
+            torch.cuda.synchronize(self.device)
+            return {k: res[k].cpu().numpy() for k in RESULTS}
 
     def solve_expanded(self, glp):
         """Solve ``glp`` through ``to_standard_form().to_equality_form()`` on ``HipDensePrimalNormalSolver`` and map the results
@@ -221,8 +321,8 @@ class HipSparseGeneralPrimalNormalSolver(HipGeneralPrimalNormalSolver):
         return glp.A.nproblems == 1 and 1 <= blp.nrows <= WAVE_MAX_ROWS and blp.ncols <= WAVE_MAX_COLS
 
     @staticmethod
-    def _bounded_matrix(blp):
-        A = blp.A.tocsr()
+    def _bounded_matrix(Ah):
+        A = Ah.tocsr()
         A.sum_duplicates(); A.eliminate_zeros(); A.sort_indices()
         return A, (A.shape, A.data.tobytes(), A.indptr.tobytes(), A.indices.tobytes())
 

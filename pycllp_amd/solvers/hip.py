@@ -62,10 +62,16 @@ def autoscale_wanted(b, c, u=None):
     """The ``autoscale='auto'`` rule: True when, for any LP of the batch, max|b| or max|c| lies outside [0.1, 10] -- the
     start x = z = y = 1 and the unit floors of the tolerances (eps (1 + |b|)) are tuned to data of order 1 (DESIGN.md section
     2, scaling caveat: decades away from 1 cost 40-170 iterations and objective accuracy).  numpy arrays or torch tensors.
-    ``u`` (numpy, optional): upper bounds of a bounded LP; max of the finite positive u of an LP outside the band counts too (an
+    ``u`` (optional): upper bounds of a bounded LP; max of the finite positive u of an LP outside the band counts too (an
     LP without one -- no bounds, or only fixed variables -- is left out of that test)."""
     lo, hi = AUTOSCALE_BAND
-    if u is not None:
+    if isinstance(u, torch.Tensor):
+        if u.numel():
+            fin = torch.isfinite(u) & (u > 0)
+            mx = torch.where(fin, u.abs(), torch.zeros((), dtype=u.dtype, device=u.device)).amax(dim=-1)
+            if bool((fin.any(dim=-1) & ((mx < lo) | (mx > hi))).any()):
+                return True
+    elif u is not None:
         u = np.asarray(u, dtype=np.float64)
         fin = np.isfinite(u) & (u > 0)
         has = fin.any(axis=-1)
