@@ -65,6 +65,14 @@ extern "C" {
 #define PYCLLP_STATUS_NUMERICAL 3
 #define PYCLLP_STATUS_DUAL_INFEASIBLE 4
 #define PYCLLP_STATUS_ITERATION_LIMIT 5
+/* Non-finite data.  An LP with a non-finite entry (NaN, +Inf, -Inf) in its b, its c, its own values of A (the entries with
+ * per-problem matrices) or its warm start (PYCLLP_FLAG_WARM_START: x, y, z) ends with PYCLLP_STATUS_NUMERICAL, and so does
+ * an LP whose arithmetic stops being finite on the way (data many decades away from 1 without PYCLLP_FLAG_AUTOSCALE).  Every
+ * output of such an LP is written (the one exception stated at the top aside): its x, y, z (and s) hold the last finite
+ * iterate or non-finite values, its objectives are unspecified, its iteration count is that of the iteration that noticed.
+ * No other LP of the batch is affected: each carries the bits it has in the same call without the bad LP.  u is read as
+ * "> 0 or fixed", as everywhere: a NaN or a negative upper bound fixes its variable at 0 and is no error.
+ * tests/test_nonfinite.py pins this for every kernel family. */
 
 #define PYCLLP_E_BADARG (-1)      /* NULL pointer / non-positive size                     */
 #define PYCLLP_E_UNSUPPORTED (-2) /* (m, n) outside what the compiled kernels cover        */

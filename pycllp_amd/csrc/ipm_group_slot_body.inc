@@ -145,6 +145,9 @@
                 for (int q = 0; q < NCG; q++) cm = fmax(cm, (!BD || act(q)) ? fabs(c[q]) : 0.0);   // (c = 0 where !ok)
                 double sb = grp_max<MP>(fabs(b)), sc = grp_max<MP>(cm);
                 sb = (sb > 0.0) ? sb : 1.0; sc = (sc > 0.0) ? sc : 1.0;
+                // BD: sb = inf -- an Inf in b: the LP ends NUMERICAL at iteration 0 either way -- is no scale factor: u / inf = 0
+                // would turn every column into a fixed one, for finalize's scale factors and stores too
+                if constexpr (BD) sb = (sb < HUGE_VAL) ? sb : 1.0;
                 if (fresh) {
                     b = b / sb;
 #pragma unroll

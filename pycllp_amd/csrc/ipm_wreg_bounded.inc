@@ -84,7 +84,9 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
 #pragma unroll
             for (int r2 = 0; r2 < MR; r2++) bm = fmax(bm, okr[r2] ? fabs(bg[lp * m + lane + 64 * r2]) : 0.0);
             sb = wmax(bm); sc = wmax(cm);
-            sb = uni((sb > 0.0) ? sb : 1.0); sc = uni((sc > 0.0) ? sc : 1.0);
+            // (sb = inf -- an Inf in b: the LP ends NUMERICAL at iteration 0 either way -- is no scale factor: u / inf = 0 would turn
+            // every column into a fixed one, at the store too, where y, z and s depend on which columns take part)
+            sb = uni((sb > 0.0 && sb < HUGE_VAL) ? sb : 1.0); sc = uni((sc > 0.0) ? sc : 1.0);
         }
         // ---- start: z = s = y = 1, x = min(1, u/2), t = u - x (tau = 0); norms for the tolerances ----
         double c2 = 0.0, u2 = 0.0, nbc = 0.0;

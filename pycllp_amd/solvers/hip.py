@@ -63,7 +63,9 @@ def autoscale_wanted(b, c, u=None):
     start x = z = y = 1 and the unit floors of the tolerances (eps (1 + |b|)) are tuned to data of order 1 (DESIGN.md section
     2, scaling caveat: decades away from 1 cost 40-170 iterations and objective accuracy).  numpy arrays or torch tensors.
     ``u`` (optional): upper bounds of a bounded LP; max of the finite positive u of an LP outside the band counts too (an
-    LP without one -- no bounds, or only fixed variables -- is left out of that test)."""
+    LP without one -- no bounds, or only fixed variables -- is left out of that test).  An LP whose max|b| or max|c| is not finite
+    (a NaN or an Inf in its data) is left out as well: it ends with PYCLLP_STATUS_NUMERICAL whatever the scaling and must not
+    decide the arithmetic of the others."""
     lo, hi = AUTOSCALE_BAND
     if isinstance(u, torch.Tensor):
         if u.numel():
@@ -83,14 +85,14 @@ def autoscale_wanted(b, c, u=None):
             if v.numel() == 0:
                 continue
             mx = v.abs().amax(dim=-1)
-            if bool(((mx < lo) | (mx > hi)).any()):
+            if bool((((mx < lo) | (mx > hi)) & torch.isfinite(mx)).any()):
                 return True
         else:
             v = np.asarray(v)
             if v.size == 0:
                 continue
             mx = np.abs(v).max(axis=-1)
-            if ((mx < lo) | (mx > hi)).any():
+            if (((mx < lo) | (mx > hi)) & np.isfinite(mx)).any():
                 return True
     return False
 
@@ -475,7 +477,7 @@ class HipDensePrimalNormalSolver(DeviceArrays, BaseSolver):
                         if speculative:
                             for v in (st["db"][lo:hi], st["dc"][lo:hi]):
                                 mx = v.abs().amax(dim=-1)
-                                tests.append(((mx < lo_band) | (mx > hi_band)).any())
+                                tests.append((((mx < lo_band) | (mx > hi_band)) & torch.isfinite(mx)).any())
                 part = {k: buf[k][lo:hi] for k in RESULTS}
                 self._launch(st["db"][lo:hi], st["dc"][lo:hi], part, o, row0=lo)
                 done = compute.record_event()

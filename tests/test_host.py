@@ -284,3 +284,39 @@ def test_sparse_generator_terminates_on_narrow_matrices():
     from pycllp_amd import problems
     A, b, c = problems.random_sparse_arrays(7, 2, 3, density=1.0, seed=1)
     assert A.shape == (7, 2) and (np.diff(A.indptr) == 2).all() and b.shape == (3, 7) and c.shape == (3, 2)
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf], ids=["nan", "+inf", "-inf"])
+@pytest.mark.parametrize("array", ["b", "c"])
+def test_autoscale_auto_leaves_lps_with_non_finite_data_out_of_the_band_test(array, bad):
+    """``autoscale_wanted``: an LP whose max|b| or max|c| is not finite ends with status 3 whatever the scaling and must not
+    decide the arithmetic of the others -- in an in-band batch the answer stays False, in an out-of-band batch True; numpy
+    and torch arguments agree (the rule ``_solve_host`` applies on the device is the torch one)."""
+    from pycllp_amd.solvers.hip import autoscale_wanted
+    rs = np.random.RandomState(3)
+    b, c = 0.5 + rs.rand(7, 5), 0.5 + rs.rand(7, 9)
+    u = np.where(rs.rand(7, 9) < 0.5, np.inf, 1.0 + rs.rand(7, 9))
+    both = lambda b_, c_, u_=None: (autoscale_wanted(b_, c_, u_),
+                                    autoscale_wanted(torch.as_tensor(b_), torch.as_tensor(c_), None if u_ is None else torch.as_tensor(u_)))
+    assert both(b, c) == (False, False) and both(b, c, u) == (False, False)
+    sick = dict(b=b.copy(), c=c.copy())
+    sick[array][2, 1] = bad
+    assert both(sick["b"], sick["c"]) == (False, False)
+    assert both(sick["b"], sick["c"], u) == (False, False)
+    # the same entry in an out-of-band batch: another LP's data decides, as without the entry
+    for far in (dict(b=b * 1e3, c=c), dict(b=b, c=c * 1e-3)):
+        assert both(far["b"], far["c"]) == (True, True)
+        sick = dict(b=far["b"].copy(), c=far["c"].copy())
+        sick[array][2, 1] = bad
+        assert both(sick["b"], sick["c"]) == (True, True)
+    # ... and where the sick LP is the only one out of band, the batch stays on the reference's arithmetic
+    lone = dict(b=b.copy(), c=c.copy())
+    lone[array][2] *= 1e3
+    assert both(lone["b"], lone["c"]) == (True, True)
+    lone[array][2, 1] = bad
+    assert both(lone["b"], lone["c"]) == (False, False)
+    # upper bounds: u = +inf is "no bound", a NaN or a negative u is "not > 0" (fixed): neither counts, as before
+    u2 = u.copy()
+    u2[0, 0], u2[1, 1] = np.nan, -1.0
+    assert both(b, c, u2) == (False, False)
+    assert both(b, c, np.where(np.isfinite(u), u * 1e3, u)) == (True, True)
