@@ -97,7 +97,14 @@ extern "C" {
                                     (gamma_affine / gamma)^3 from how far it gets, the corrector with the second-order term.  Same
                                     optimum to the same tolerance in ~27 % fewer iterations at r = 0.9, ~45 % fewer at r = 0.99
                                     (45-50 % on config 5's structure).  An option: the default path stays the reference's rule.
-                                    Not with PYCLLP_FLAG_HSD.  oracle/ipm_dense_ref.c ipm_one_pc is its restatement.          */
+                                    Not with PYCLLP_FLAG_HSD.  oracle/ipm_dense_ref.c ipm_one_pc is its restatement.
+                                    The workgroup-per-LP block kernel has no such step: with PYCLLP_FLAG_BLOCK_KERNEL the option is
+                                    refused (PYCLLP_E_UNSUPPORTED), and an LP that the wavefront-per-LP kernel DEFERS to it during a
+                                    predictor-corrector solve -- the Nocedal-Wright guard would have bitten, or every LP with
+                                    PYCLLP_FLAG_FORCE_GUARD_PATH -- is solved from its start again on the reference's plain rule:
+                                    the same optimum and statuses, the plain rule's iterates and iteration count for that LP.
+                                    The lane-group and large-LP kernels keep the step under their guard.
+                                    tests/test_option_pairs.py pins this.                                                     */
 #define PYCLLP_FLAG_NO_SLACK_PATH 16 /* do not use the slack-aware kernel even when the last m columns of A are the
                                         identity (diagnostic: results must agree to rounding)                    */
 #define PYCLLP_FLAG_FORCE_GUARD_PATH 4 /* diagnostic: always run the guarded (cold) LDL' path of the group

@@ -71,32 +71,37 @@ def test_table_holds_every_family_and_kind():
         assert tj.inputs(c.key).nproblems == (tj.B_BIG if small else 13 if c.family == "block" and c.where else tj.B), c.id
 
 
+def assert_point_is_served_first(c):
+    """The point of case ``c`` is first covered by the shape, or has the plan, that ``c.where`` names."""
+    bounded = c.kind == "bounded"
+    P = tj.problem(c.key, bounded)
+    m, N = P.A[0].shape
+    A = sp.csr_matrix(P.A[0])
+    if c.family in ("slack", "group"):
+        assert P.tail == (c.family == "slack") and (c.flags & tj.NO_SLACK) == (0 if P.tail else tj.NO_SLACK), c.id
+        assert tkv.first_covering(c.family, tkv.GROUP_SHAPES, m, N) == c.where, c.id
+    elif c.family == "tables":
+        assert tkv.first_covering("tables", tkv.WAVE_TAB_SHAPES, m, N) == c.where, c.id
+        assert not tkv.tables_cannot_fit(m, N, P.tail, c.where, bounded) or A.nnz < 0.25 * m * N, c.id
+    elif c.family == "image":
+        assert tkv.first_covering("image", tkv.WAVE_DA_SHAPES, m, N) == c.where, c.id
+        assert tkv.image_waves(m, N, P.tail, c.where, bounded) >= 1 and tkv.tables_cannot_fit(m, N, P.tail, c.where, bounded)
+    elif c.family == "block" and c.where is not None:
+        plan = twp.block_plan(m, N, A.nnz, pa=c.kind.startswith("pa"))
+        assert plan[0] == c.where[1] and (m, N) == c.where[5:7], c.id
+        assert plan[1] == (c.where[1] != "l2")                                       # a_in_lds 1 and 0
+        assert (c.flags == tj.BLOCK) or twp.default_is_block(m, N), c.id
+    elif c.family == "block":
+        assert c.flags == tj.BLOCK and m <= twp.BLK_MAX_M and N <= twp.BLK_MAX_N
+    else:
+        cell, gram = c.where[1], c.where[2]
+        assert twp.reachable(m, N) and twp.big_plan((m + 15) // 16, N)[0] == cell, c.id
+        assert twp.gram_is_dense(A, P.tail) == (gram == "mfma"), c.id
+
+
 def test_every_point_is_served_first_by_the_shape_or_plan_named():
     for c in tj.CASES:
-        bounded = c.kind == "bounded"
-        P = tj.problem(c.key, bounded)
-        m, N = P.A[0].shape
-        A = sp.csr_matrix(P.A[0])
-        if c.family in ("slack", "group"):
-            assert P.tail == (c.family == "slack") and (c.flags & tj.NO_SLACK) == (0 if P.tail else tj.NO_SLACK), c.id
-            assert tkv.first_covering(c.family, tkv.GROUP_SHAPES, m, N) == c.where, c.id
-        elif c.family == "tables":
-            assert tkv.first_covering("tables", tkv.WAVE_TAB_SHAPES, m, N) == c.where, c.id
-            assert not tkv.tables_cannot_fit(m, N, P.tail, c.where, bounded) or A.nnz < 0.25 * m * N, c.id
-        elif c.family == "image":
-            assert tkv.first_covering("image", tkv.WAVE_DA_SHAPES, m, N) == c.where, c.id
-            assert tkv.image_waves(m, N, P.tail, c.where, bounded) >= 1 and tkv.tables_cannot_fit(m, N, P.tail, c.where, bounded)
-        elif c.family == "block" and c.where is not None:
-            plan = twp.block_plan(m, N, A.nnz, pa=c.kind.startswith("pa"))
-            assert plan[0] == c.where[1] and (m, N) == c.where[5:7], c.id
-            assert plan[1] == (c.where[1] != "l2")                                       # a_in_lds 1 and 0
-            assert (c.flags == tj.BLOCK) or twp.default_is_block(m, N), c.id
-        elif c.family == "block":
-            assert c.flags == tj.BLOCK and m <= twp.BLK_MAX_M and N <= twp.BLK_MAX_N
-        else:
-            cell, gram = c.where[1], c.where[2]
-            assert twp.reachable(m, N) and twp.big_plan((m + 15) // 16, N)[0] == cell, c.id
-            assert twp.gram_is_dense(A, P.tail) == (gram == "mfma"), c.id
+        assert_point_is_served_first(c)
     # 32 x 64 runs on the (32, 96) kernel (4x4x4 tiles), 20 x 30 on padded rows and columns
     where = {c.point: c.where for c in tj.CASES if c.family == "slack" and c.kind == "plain" and c.mode == "cold"}
     assert where == {"32x64": (32, 96), "16x32": (16, 48), "20x30": (32, 64)}

@@ -36,7 +36,8 @@ QUANTITIES = ("x", "y", "z", "pobj", "dobj")
 # dense-A lane-group kernel stores c'x, b'y of the point it stores (tests/test_dense_batch.py test_trajectory).
 STORES_ITS_OWN_OBJECTIVES = ("perA",)
 
-# family, kind, point label, mode ('cold', 'warm', 'autoscale', 'degenerate'), the k ladder, input key (see ``inputs``), what
+# family, kind, point label, mode ('cold', 'warm', 'autoscale', 'degenerate'; the pair rows of tests/pair_cases.py also
+# 'warm+autoscale', see ``modes``), the k ladder, input key (see ``inputs``), what
 # must serve it (lane groups and wave kernel: the compiled shape; block and large-LP kernel: the case of
 # test_workgroup_kernel_plans.py whose plan it is), extra solver flags, explicit margin {k: bound} with its cause
 Case = collections.namedtuple("Case", "id family kind point mode ks key where flags margin cause")
@@ -163,6 +164,24 @@ def warm_point(nb, m, N):
     return 0.5 + rs.rand(nb, N), rs.randn(nb, m), 0.5 + rs.rand(nb, N)
 
 
+def modes(case):
+    """The start and scaling options of a case: the subset of {'warm', 'autoscale'} its mode names -- one of them, or both
+    joined by '+' (tests/pair_cases.py)."""
+    return frozenset(case.mode.split("+")) & {"warm", "autoscale"}
+
+
+def start_point(case, P):
+    """x0, y0, z0 of a warm case: ``warm_point``, and under autoscale that point scaled with the data -- x0 max|b_k|,
+    y0 max|c_k|, z0 max|c_k| per LP -- so that after the solver's division the start is the well-conditioned ``warm_point``
+    itself and the three divisions are what the case tests."""
+    nb, (m, N) = P.b.shape[0], P.A[0].shape
+    x0, y0, z0 = warm_point(nb, m, N)
+    if "autoscale" in modes(case):
+        sb, sc = np.abs(P.b).max(axis=1, keepdims=True), np.abs(P.c).max(axis=1, keepdims=True)
+        x0, y0, z0 = x0 * sb, y0 * sc, z0 * sc
+    return x0, y0, z0
+
+
 def probe_entry(P):
     """(row, column) of the entry of A the 'must bite' test scales: the last structural entry (before an identity tail) of the
     last row that has one -- the edge of a ragged case.  Entries below 1e-3 max|A| do not count (the noise of a degenerate
@@ -178,11 +197,12 @@ def probe_entry(P):
 
 
 # ---- the reference --------------------------------------------------------------------------------------------------------
-def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, **opts):
+def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, start=None, **opts):
     """The reference's results after k iterations: dict(x, y, z[, s], pobj, dobj, status, iters, nrefs, aty).  ``perm``: seed of
     a row-and-column permutation under which the LPs are solved (results mapped back); ``r_scale``: factor on the step
     fraction r; ``a_scale``: factor on ``probe_entry`` of A; ``opts``: further fields of the oracle's options (``r``: the step
-    fraction ``r_scale`` multiplies, default 0.9)."""
+    fraction ``r_scale`` multiplies, default 0.9); ``start``: (x0, y0, z0) a warm case starts from in place
+    of ``start_point``."""
     from oracle import port
     bounded = case.kind == "bounded"
     P = problem(case.key, bounded)
@@ -211,10 +231,10 @@ def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, **opts):
         r = bounded_twin.solve(As[0], b, c, P.u[:, cols], max_iter=k, r=r_frac, **opts)
         r["nrefs"] = np.zeros(nb, dtype=np.int32)
     else:
-        flags = ORACLE_FLAGS[case.kind] | (AUTOSCALE if case.mode == "autoscale" else 0)
+        flags = ORACLE_FLAGS[case.kind] | (AUTOSCALE if "autoscale" in modes(case) else 0)
+        x0, y0, z0 = (start_point(case, P) if start is None else start) if "warm" in modes(case) else (None,) * 3
         start = {}
-        if case.mode == "warm":
-            x0, y0, z0 = warm_point(nb, m, N)
+        if x0 is not None:
             start, flags = dict(x0=x0[:, cols], y0=y0[:, rows], z0=z0[:, cols]), flags | WARM
         opts = dict(opts, max_iter=k, r=r_frac, flags=flags)
         if P.shared:
@@ -314,13 +334,14 @@ def assert_served(case, info, lp, solver):
 
 def solver_options(case):
     kind = case.kind
-    return dict(hsd=kind.endswith("hsd"), predcorr=kind.endswith("pc"), autoscale=case.mode == "autoscale",
+    return dict(hsd=kind.endswith("hsd"), predcorr=kind.endswith("pc"), autoscale="autoscale" in modes(case),
                 **({"flags": case.flags} if case.flags else {}))
 
 
-def kernel_results(case, ks=None, **opts):
+def kernel_results(case, ks=None, seen=None, **opts):
     """{k: results of the kernel after k iterations} in the layout of ``run_reference``; every launch asserts what served it.
-    ``ks``: the iteration limits (default the case's ladder); ``opts``: further fields of ``pycllp_hip_opts``."""
+    ``ks``: the iteration limits (default the case's ladder); ``seen``: a list that receives ``launch_info()`` of every launch;
+    ``opts``: further fields of ``pycllp_hip_opts``."""
     import torch
     from pycllp_amd.solvers import solver_registry
     lp = inputs(case.key)
@@ -334,6 +355,8 @@ def kernel_results(case, ks=None, **opts):
             lp.init(s)
             lp.solve(s)
             assert_served(case, s.launch_info(), lp, s)
+            if seen is not None:
+                seen.append(s.launch_info())
             out[k] = dict(x=s.x, y=s.y, z=s.z, s=s.s, pobj=s.primal_obj, dobj=s.dual_obj, status=s.status, iters=s.iters)
         return out
     P = problem(case.key, False)
@@ -343,17 +366,18 @@ def kernel_results(case, ks=None, **opts):
     lp.init(s)
     if not P.shared:
         lp.solve(s)                                        # uploads the per-problem values of A (one iteration)
-    m, N = P.A[0].shape
-    nb = lp.nproblems
+    warm = "warm" in modes(case)
     for k in ks:
-        if case.mode == "warm":
+        if warm:
             if "set0" not in s.buffers:
                 s.solve_device(lp.b, lp.c, max_iter=1)     # allocates the result buffers a warm start reads
-            for q, v in zip(("x", "y", "z"), warm_point(nb, m, N)):
+            for q, v in zip(("x", "y", "z"), start_point(case, P)):
                 s.buffers["set0"][q].copy_(torch.as_tensor(v, device="cuda:0"))
-        g = s.solve_device(lp.b, lp.c, warm_start=case.mode == "warm", max_iter=k, **opts)
+        g = s.solve_device(lp.b, lp.c, warm_start=warm, max_iter=k, **opts)
         torch.cuda.synchronize()
         assert_served(case, s.launch_info(), lp, s)
+        if seen is not None:
+            seen.append(s.launch_info())
         out[k] = {q: g[q].cpu().numpy() for q in ("x", "y", "z", "pobj", "dobj", "status", "iters")}
         out[k]["aty"] = a_transpose_y(P, out[k]["y"])
     return out
