@@ -179,6 +179,9 @@ struct GWave {
     const double* Aimg;   // LDS: row-major A, row stride AS
     static constexpr bool COLB = MP == 32 && NP <= 96;   // (at NP = 128 the sixteen registers are not to spare)
     static constexpr bool ROWB = COLB && SL;     // (the variants without the identity tail carry one more N-vector register each: no room)
+    // The sweep stores L column by column and carries the first solve's right-hand side (factor_dpp_fwd) where that is free:
+    // the (32, 128) shapes have neither the address registers nor room for the carried values (10-19 registers spilt with them).
+    static constexpr bool CARRY = COLB || MP == 16;
     unsigned rb[ROWB ? 16 : 1];   // ... and of the sixteen 16-byte pairs of the lane's own ROW (load_own_row), swizzle included
     unsigned xb[COLB ? 16 : 1];   // MP = 32: LDS byte address of slab entry (row c, column gl), c < 16, swizzle included: entry (k, gl) of the
                           // factor's column layout is at xb[k & 15] + 256 (k & 16).  Kernel-lifetime values (16 registers, which the kernel
@@ -435,8 +438,8 @@ struct GWave {
     // the FP64 cycles saved: 9.3 M instead of 10.2 M LPs/s.  Also tried: that update as ONE product on the matrix cores (raw and
     // scaled column halves collected in two LDS tiles, 4 MFMAs per LP, result back through a third tile): correct, 9.6 M --
     // three more wave-level round trips per factorisation outweigh 1.6 k FP64 cycles with only two waves per SIMD.)
-    // L ends up in W (W[j] = L[gl][j], 0 on and above the diagonal) and is written to the slab once, at the
-    // end, in the layout the substitution reads.  Arithmetic: u_i u_k / D_j as fma(-(u_i / D_j), u_k, .).
+    // L ends up in W (W[j] = L[gl][j], 0 on and above the diagonal) and is written to the slab column by column, as
+    // each becomes final, in the layout the substitution reads.  Arithmetic: u_i u_k / D_j as fma(-(u_i / D_j), u_k, .).
     // top row's value of u in both DPP rows of a 32-lane group (gfx950 v_permlane16_swap: [0] = rows (0, 0, 2, 2))
     __device__ __forceinline__ static double top_row_of(double u) {
         const int lo = __double2loint(u), hi = __double2hiint(u);
@@ -449,9 +452,53 @@ struct GWave {
     // software-pipelining the next pivot's chain into column j's updates (6.314 against 6.26 ms per 65 536 LPs: with two waves
     // per SIMD the other wave already hides that latency, profiles/r03/dense_factor_pipelined.txt), and handing the top DPP
     // row's entries to the bottom row through LDS instead of v_permlane16_swap (6.02-6.09 against 5.94 ms).
+    //
+    // The sweep can take NR right-hand sides along (factor_dpp_fwd): forward substitution is elimination applied to one more
+    // column, and its step j, r -= L[.][j] * (r of lane j), needs only the multiplier l that column j has just formed -- the
+    // FMA of step j of subst15_up with the same operands, issued where the sweep waits on its pivot chain instead of in three
+    // serial chains behind the factor's round trip through the slab (31 column loads and their wait go away).  Per lane the
+    // floating-point operations and their order are those of forward(); the rows a step writes are chosen by the DPP row_mask,
+    // so EXEC is not touched and lanes on and above a pivot still execute r -= 0 * r_j as they do there.
+    //   MP = 16: step j follows column j, j = 0 .. 14.
+    //   MP = 32: the top DPP row's steps follow columns 0 .. 14; its finished values then cross to the bottom row (one
+    //   ds_swizzle, issued after column 14) for the 16 accumulate steps of dot16_bcast, the subtraction and the bottom row's 15
+    //   steps.  These 32 dependent operations are dealt two to a column over columns 16 .. 31, one behind the pivot's broadcast
+    //   and one behind its reciprocal, so that none of their latency stands in front of a pivot: the step of column c runs
+    //   inside column 17 + c / 2, on the W[c] that the lane still holds, and only the last one (c = 30) follows column 31.
+    // Column j of L goes to the slab as soon as it is final, in the layout the substitution reads; one wave_lds_sync() follows the
+    // last column.  The stores are plain C++ stores between the sweep's asm volatile statements.  Those have no memory clobber, so
+    // nothing in the language keeps a store next to its column: the scheduler treats a volatile asm as a barrier for memory
+    // operations, and the shipped code has one ds_write_b64 behind every column (llvm-objdump -d of the library's gfx950 code object).  Correctness
+    // does not depend on it -- a store that sank would still precede the final sync -- only the overlap does; check the
+    // disassembly after a compiler change.
     template <bool RELF = false>
     __device__ __forceinline__ bool factor_dpp(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
                                                const double* fl = nullptr) const {
+        return factor_sweep<RELF, 0>(W, beta2, floor_, live, rdiag, fl, nullptr);
+    }
+    // r <- L^-1 r for the NR right-hand sides r (lane = row) along with the factorisation; the caller goes on with backward()
+    template <bool RELF = false, int NR>
+    __device__ __forceinline__ bool factor_dpp_fwd(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
+                                                   double (&r)[NR], const double* fl = nullptr) const {
+        return factor_sweep<RELF, NR>(W, beta2, floor_, live, rdiag, fl, r);
+    }
+    // operation `op` (0 .. 31) of the bottom DPP row's part of the carried forward substitution, MP = 32 (see above)
+    template <int OP, int NR>
+    __device__ __forceinline__ static void fwd_bottom_op(const double (&W)[MP], double* r, const double* so, double* a) {
+        if constexpr (OP >= 0 && OP < 16) {
+#pragma unroll
+            for (int i = 0; i < NR; i++) dot_step<OP, 0xA>(a[i], so[i], W[OP]);      // a += L21[.][OP] * t1_OP (a stays 0 in the top row)
+        } else if constexpr (OP == 16) {
+#pragma unroll
+            for (int i = 0; i < NR; i++) r[i] -= a[i];                               // r2 -= L21 t1 (top row: r1 - 0)
+        } else if constexpr (OP > 16 && OP < 32) {
+#pragma unroll
+            for (int i = 0; i < NR; i++) fwd_step<OP - 17, 0xA>(r[i], W[OP - 1]);    // step of column OP - 1
+        }
+    }
+    template <bool RELF, int NR>
+    __device__ __forceinline__ bool factor_sweep(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
+                                                 const double* fl, double* r) const {
         rdiag = 1.0;
         // the sweep is a chain of dependent operations: s_setprio lets it go first when both waves of the SIMD are ready.
         // Measured: 6.82 -> 6.75 ms for the HSD kernel (RELF); for the plain kernel nothing alone (5.93-5.95 ms at levels 0, 2, 3),
@@ -459,8 +506,12 @@ struct GWave {
         // Gram product's MFMA loop instead costs 0.3-0.6 %.
         constexpr int PRIO_ = RELF ? PYCLLP_FACTOR_PRIO_HSD : PYCLLP_FACTOR_PRIO;
         if constexpr (PRIO_ != 0) __builtin_amdgcn_s_setprio(PRIO_);
-        const int go = ogl();      // unused, but this opaque copy shapes the register allocation of the (32, .) kernels
+        const int go = ogl();      // COLB: unused, but this opaque copy shapes the register allocation of the (32, .) kernels
         (void)go;
+        constexpr int NR1 = NR ? NR : 1;
+        double so[NR1], acc[NR1];  // MP = 32: the top row's finished values as the bottom row sees them / the L21 t1 accumulators
+#pragma unroll
+        for (int i = 0; i < NR1; i++) { so[i] = 0.0; acc[i] = 0.0; }
         double ymax = 0.0;         // running max of u^2 / D over the lanes below the pivots: the guard bites iff it exceeds beta^2
         static_for<0, MP>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
@@ -468,8 +519,13 @@ struct GWave {
             double src = u;        // the u whose lane j % 16 is the pivot row as seen from this lane's DPP row
             if constexpr (MP == 32 && j < 16) src = top_row_of(u);
             const double piv = bcast64<j % 16>(src);
+            if constexpr (NR > 0 && MP == 32 && j > 16) fwd_bottom_op<2 * (j - 16) - 1, NR>(W, r, so, acc);
             const double aD = RELF ? max_abs<false>(piv, fl[j]) : max_abs<true>(piv, floor_);
-            const double rD = fast_rcp(aD);
+            double rD = fast_rcp(aD);
+            if constexpr (NR > 0 && MP == 32 && j >= 16) {
+                asm volatile("" : "+v"(rD));   // behind the Newton steps, not between the maximum and the reciprocal
+                fwd_bottom_op<2 * (j - 16), NR>(W, r, so, acc);
+            }
             // lanes of every group with gl > j / the lane gl == j
             constexpr unsigned below32 = (j + 1 < 32) ? (0xFFFFFFFFu << ((j + 1) & 31)) : 0u;
             constexpr unsigned below16 = (j + 1 < 16) ? (((0xFFFFu << ((j + 1) & 15)) & 0xFFFFu) * 0x10001u) : 0u;
@@ -488,13 +544,21 @@ struct GWave {
                 chain_step_exec<j - 16, MB_, MB_, 1, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[16]), 0.0, rD, l, ymax, rdiag);
             }
             W[j] = l;
+            if constexpr (COLB) *(__attribute__((address_space(3))) double*)(size_t)(xb[j & 15] + 256u * (unsigned)(j & ~15)) = l;
+            else if constexpr (MP == 16) slab[G_::sidx(j, go)] = l;
+            if constexpr (NR > 0 && j < 15) {
+#pragma unroll
+                for (int i = 0; i < NR; i++) fwd_step<j, (MP == 32) ? 0x5 : 0xF>(r[i], l);
+                if constexpr (MP == 32 && j == 14) {
+#pragma unroll
+                    for (int i = 0; i < NR; i++) so[i] = swz_xor16_d(r[i]);
+                }
+            }
         });
+        if constexpr (NR > 0 && MP == 32) fwd_bottom_op<31, NR>(W, r, so, acc);
         const bool viol = live && (ymax > beta2);
         if constexpr (PRIO_ != 0) __builtin_amdgcn_s_setprio(0);
-        if constexpr (COLB) {
-#pragma unroll
-            for (int j = 0; j < MP; j++) *(__attribute__((address_space(3))) double*)(size_t)(xb[j & 15] + 256u * (unsigned)(j & ~15)) = W[j];
-        } else {
+        if constexpr (!CARRY) {    // (32, 128): the swizzled addresses are formed here, not held across the sweep
             const int g = ogl();
 #pragma unroll
             for (int j = 0; j < MP; j++) slab[G_::sidx(j, g)] = W[j];
@@ -541,10 +605,27 @@ struct GWave {
     // s <- (L D L')^-1 s for every group.  Substitution runs in 16x16 blocks so that every broadcast stays inside
     // a 16-lane DPP row (row_newbcast: 2 moves, no SGPR round trip); a 32-lane group does top block, the 16x16
     // off-diagonal product (operand fetched across the rows by one ds_swizzle) and bottom block.
+    // forward(s): s <- L^-1 s from the slab's column layout; backward(s, rdiag): s <- L^-T D^-1 s from its rows.  fwd_back is the
+    // whole solve, for callers that have no sweep to carry their right-hand side (refinement, the corrector, the guarded path);
+    // behind factor_dpp_fwd the caller runs back_after_sweep() on what the sweep returned: the row loads are then the first
+    // thing behind the sweep's final sync.  (s_setprio as before the split: the 16-row kernels leave the substitution's level on
+    // until the next sweep ends.)
     __device__ __forceinline__ double fwd_back(double s, double rdiag) const {
+        if constexpr (PYCLLP_SOLVE_PRIO != 0) __builtin_amdgcn_s_setprio(PYCLLP_SOLVE_PRIO);
+        forward(s);
+        backward(s, rdiag);
+        if constexpr (MP == 32 && PYCLLP_SOLVE_PRIO != 0) __builtin_amdgcn_s_setprio(0);
+        return s;
+    }
+    __device__ __forceinline__ double back_after_sweep(double s, double rdiag) const {
+        if constexpr (PYCLLP_SOLVE_PRIO != 0) __builtin_amdgcn_s_setprio(PYCLLP_SOLVE_PRIO);
+        backward(s, rdiag);
+        if constexpr (MP == 32 && PYCLLP_SOLVE_PRIO != 0) __builtin_amdgcn_s_setprio(0);
+        return s;
+    }
+    __device__ __forceinline__ void forward(double& s) const {
         // all factor entries a lane needs are fetched up front and pinned in registers: left to itself the
         // scheduler sinks each ds_read next to its FMA and every step of the serial chain pays an LDS round trip
-        if constexpr (PYCLLP_SOLVE_PRIO != 0) __builtin_amdgcn_s_setprio(PYCLLP_SOLVE_PRIO);
         double lf[MP];
         if constexpr (COLB) {
 #pragma unroll
@@ -567,6 +648,8 @@ struct GWave {
                 subst15_up(s, lf + 16);           // t2 = L22^-1 r2
             }
         }
+    }
+    __device__ __forceinline__ void backward(double& s, double rdiag) const {
         s *= rdiag;
         double lb[MP];
         load_own_row(lb);   // lb[i] = L[i][gl] for i > gl, else 0 (lb[0] is not used)
@@ -574,7 +657,6 @@ struct GWave {
         for (int i = 1; i < MP; i++) asm volatile("" : "+v"(lb[i]));
         if constexpr (MP == 16) {
             subst15_down(s, lb);
-            return s;
         } else {
             const bool top = gl < 16;
             if (!top) subst15_down(s, lb + 16);   // x2 = L22^-T s2
@@ -583,8 +665,6 @@ struct GWave {
                 s -= dot16_bcast(so, lb + 16);    // s1 -= L21^T x2
                 subst15_down(s, lb);              // x1 = L11^-T s1
             }
-            if constexpr (PYCLLP_SOLVE_PRIO != 0) __builtin_amdgcn_s_setprio(0);
-            return s;
         }
     }
 };
@@ -874,6 +954,12 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         const double rho = have_pred ? rho_pred : b - Ax;
         const double rhs = Adt - rho;
         double rdiag;
+        double fs[1] = {rhs};     // the first solve's right-hand side rides through the sweep: L^-1 rhs when it returns
+        // (the slack-aware (32, 96) predictor-corrector kernel alone has no registers for it: 10 -> 18 spilt; it keeps the plain sweep)
+        constexpr bool CARRY = GWave<MP, NP, SL>::CARRY && !(PC && SL && MP == 32 && NP == 96);
+        // `fused` is a run-time flag, not `if constexpr`: whether the guarded path replaces the factor is known only when the sweep
+        // returns, so both back_after_sweep() and the whole fwd_back() are inlined at the first solve of a carrying kernel
+        bool fused = CARRY;      // (wave-uniform) ... unless the guarded path replaced the factor
         {
             double W[MP];
             const int gd = w.ogl();
@@ -888,12 +974,15 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             const double beta2 = grp_max<MP>(fabs(diag));
             wave_lds_sync();
             STAMP(3)
-            const bool redo = w.factor_dpp(W, beta2, o.pivot_floor, live, rdiag);
+            bool redo;
+            if constexpr (CARRY) redo = w.factor_dpp_fwd(W, beta2, o.pivot_floor, live, rdiag, fs);
+            else redo = w.factor_dpp(W, beta2, o.pivot_floor, live, rdiag);
             if (redo || (o.flags & PYCLLP_FLAG_FORCE_GUARD_PATH)) {
                 // the Nocedal-Wright guard would have bitten somewhere: re-form M and factor with the guard applied
                 double Ax2, Adt2;
                 do_gram(Ax2, Adt2);
                 rdiag = w.factor_guarded_inplace(rowok, beta2, o.pivot_floor);
+                fused = false;    // the carried forward half belongs to the dropped factor
             }
             STAMP(4)
         }
@@ -901,7 +990,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         double rhs_c = rhs;
         if constexpr (PC) {
             // ---- predictor (mu = 0): dy_a, dx_a, dz_a; how far it gets; centering; the corrector's right-hand side ----
-            const double dya = w.fwd_back(rhs, rdiag);
+            const double dya = fused ? w.back_after_sweep(fs[0], rdiag) : w.fwd_back(rhs, rdiag);
             double wva[NCG], dxa[NCG], dza[NCG], dt[NCG];
             w.At_times(dya, wva);
             double tha = 0.0;
@@ -931,7 +1020,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             }
             rhs_c = w.A_times(dt) - rho;
         }
-        double dy = w.fwd_back(rhs_c, rdiag);
+        double dy = (!PC && fused) ? w.back_after_sweep(fs[0], rdiag) : w.fwd_back(rhs_c, rdiag);
         STAMP(5)
         double wv[NCG], dx[NCG], d[NCG];
         w.At_times(dy, wv);

@@ -75,7 +75,13 @@ struct GWaveH : GWave<MP, NP, SL> {
     }
 
     // (s, t) <- (L D L')^-1 (s, t): GWave::fwd_back for two right-hand sides, the two dependency chains interleaved
+    // (forward2 / backward2 are its halves: behind factor_dpp_fwd, which carries both right-hand sides through the sweep, the
+    // caller runs backward2 alone)
     __device__ __forceinline__ void fwd_back2(double& s, double& t, double rdiag) const {
+        forward2(s, t);
+        backward2(s, t, rdiag);
+    }
+    __device__ __forceinline__ void forward2(double& s, double& t) const {
         const int gl = this->gl;
         const int g = this->ogl();
         const double* slab = this->slab;
@@ -100,6 +106,9 @@ struct GWaveH : GWave<MP, NP, SL> {
                 subst15_up2(s, t, lf + 16);
             }
         }
+    }
+    __device__ __forceinline__ void backward2(double& s, double& t, double rdiag) const {
+        const int gl = this->gl;
         s *= rdiag; t *= rdiag;
         double lb[MP];
         this->load_own_row(lb);
@@ -389,6 +398,9 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         double pv = Adc - b;
         double qv = fma(-HSD_ETA, rho, Adr);
         double rdiag;
+        constexpr bool CARRY = GWave<MP, NP, SL>::CARRY;
+        double fr[2] = {pv, qv};   // both right-hand sides ride through the sweep (see ipm_group_kernel)
+        bool fused = CARRY;
         {
             double W[MP];
             const int go = w.ogl();
@@ -409,16 +421,20 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             fl[go] = myfloor;
             wave_lds_sync();
             // (a software-pipelined sweep paid 1.7 % here only while this kernel ran one wave per SIMD; see GWave::factor_dpp)
-            const bool redo = w.template factor_dpp<true>(W, beta2, 0.0, live, rdiag, fl);
+            bool redo;
+            if constexpr (CARRY) redo = w.template factor_dpp_fwd<true>(W, beta2, 0.0, live, rdiag, fr, fl);
+            else redo = w.template factor_dpp<true>(W, beta2, 0.0, live, rdiag, fl);
             if (redo || (o.flags & PYCLLP_FLAG_FORCE_GUARD_PATH)) {
                 double t1, t2;
                 do_gram(t1, t2);
                 fl[go] = myfloor;          // do_gram used the staging area
                 wave_lds_sync();
                 rdiag = w.factor_guarded_inplace(rowok, beta2, 0.0, fl);
+                fused = false;             // the carried forward halves belong to the dropped factor
             }
         }
-        w.fwd_back2(pv, qv, rdiag);
+        if (fused) { pv = fr[0]; qv = fr[1]; w.backward2(pv, qv, rdiag); }
+        else w.fwd_back2(pv, qv, rdiag);
         double ap[NCG], aq[NCG], dx[NCG], d[NCG], wv[NCG];
         w.At_times2(pv, qv, ap, aq);
         double dsum = 0.0, nsum = 0.0;

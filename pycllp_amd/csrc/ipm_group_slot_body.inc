@@ -341,6 +341,9 @@
 
         const double rhs = Adt - rho;
         double rdiag;
+        constexpr bool CARRY = GWave<MP, NP, SL>::CARRY;
+        double fs[1] = {rhs};     // the first solve's right-hand side rides through the sweep (see ipm_group_kernel)
+        bool fused = CARRY;
         {
             double W[MP];
             const int gd = w.ogl();
@@ -352,14 +355,17 @@
             double diag = rowok ? w.slab[G_::sidx(gd, gd)] : 0.0;
             const double beta2 = grp_max<MP>(fabs(diag));
             wave_lds_sync();
-            const bool redo = w.factor_dpp(W, beta2, o.pivot_floor, work, rdiag);
+            bool redo;
+            if constexpr (CARRY) redo = w.factor_dpp_fwd(W, beta2, o.pivot_floor, work, rdiag, fs);
+            else redo = w.factor_dpp(W, beta2, o.pivot_floor, work, rdiag);
             if (redo || (o.flags & PYCLLP_FLAG_FORCE_GUARD_PATH)) {
                 double Ax2, Adt2;
                 do_gram(Ax2, Adt2);
                 rdiag = w.factor_guarded_inplace(rowok, beta2, o.pivot_floor);
+                fused = false;    // the carried forward half belongs to the dropped factor
             }
         }
-        double dy = w.fwd_back(rhs, rdiag);
+        double dy = fused ? w.back_after_sweep(fs[0], rdiag) : w.fwd_back(rhs, rdiag);
         double wv[NCG], dx[NCG], d[NCG];
         w.At_times(dy, wv);
 #pragma unroll

@@ -408,6 +408,25 @@ __device__ __forceinline__ double dot16_bcast(double src, const double* l) {
     return a;
 }
 
+// ---- single steps of the above, for the forward substitution that GWave::factor_dpp_fwd carries through the LDL' sweep ----
+// Step K of subst15_up, s -= l * (s of lane K of the DPP row), written only in the DPP rows of RM (the DPP row_mask: no EXEC
+// switch; the other rows keep their s).  Same FMA, same operands as the step inside subst15_up.
+template <int K, int RM>
+__device__ __forceinline__ void fwd_step(double& s, double l) {
+    asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %0, -%1 row_newbcast:" DPP_STR(%2) " row_mask:" DPP_STR(%3) " bank_mask:0xf"
+                 : "+v"(s) : "v"(l), "n"(K), "n"(RM));
+}
+// Step K of dot16_bcast, a += l * (src of lane K of the DPP row), in the DPP rows of RM; the first step carries the s_nop
+template <int K, int RM>
+__device__ __forceinline__ void dot_step(double& a, double src, double l) {
+    if constexpr (K == 0)
+        asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:" DPP_STR(%3) " row_mask:" DPP_STR(%4) " bank_mask:0xf"
+                     : "+v"(a) : "v"(src), "v"(l), "n"(K), "n"(RM));
+    else
+        asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:" DPP_STR(%3) " row_mask:" DPP_STR(%4) " bank_mask:0xf"
+                     : "+v"(a) : "v"(src), "v"(l), "n"(K), "n"(RM));
+}
+
 // ---- cross-lane helpers ----------------------------------------------------------------------------------------
 // v[l] + v[l ^ 16], then + the other 32 lanes: the sum over the four 16-lane rows, identical in all of them
 __device__ __forceinline__ double quad_sum(double v) {
