@@ -388,6 +388,37 @@ int pycllp_hip_general_from_bounded(int m, int n, int mk, long B, const int *row
                                     double *s_dev, double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
                                     void *stream);
 
+/* ---- The same for LPs that each have their OWN values of A on one shared structure ----
+ * pycllp_hip_general_to_bounded_batch: B LPs  a <= A_k x <= b,  l <= x <= u  become the LPs  [+-A_k | I] x^ = b^,  0 <= x^ <= u^
+ * that pycllp_hip_dense_solve_batch_bounded / pycllp_hip_sparse_solve_batch_bounded take -- b^, c^, u^, f^, invalid as
+ * pycllp_hip_general_to_bounded writes them, and the matrix of every LP in the layout the solve entry wants.  A C caller's
+ * three steps: this entry, the solve entry on Ah_dev, bh_dev, ch_dev, uh_dev, then pycllp_hip_general_from_bounded (which
+ * needs no matrix).  rowmap_dev, a_dev .. f_dev, bh_dev .. invalid_dev, the checks 1 .. 5 and the sizes: as above.
+ *   Avals_dev f64 [B,nnz]   every LP's values in the order of the caller's coordinate lists (rows, cols); read as they are
+ *   Aindptr_dev i32 [m+1], Aindices_dev i32 [nnz]   the structure's CSR with a row's terms in the order of the coordinate lists
+ *                           (SparseMatrix.csr_term_order); Aorder_dev i32 [nnz]: the position in the coordinate lists of the
+ *                           q-th term of that order (a stable sort of rows).  (A_k l_k)_i starts at 0.0 and adds the separately
+ *                           rounded products Avals[k, Aorder[q]] * l[k, Aindices[q]] for q = Aindptr[i] .. Aindptr[i+1]-1 in
+ *                           turn: the host's bits.  With nnz = 0 the [nnz] arrays may be NULL.
+ *   gather_dev i32 [out_len]   the plan of ONE LP's matrix output (lp.bounded_gather_dense / lp.bounded_gather_csr): slot p of
+ *                           Ah_dev[k] holds +Avals[k, t] where gather[p] = t + 1, -Avals[k, t] where gather[p] = -(t + 1), 0.0
+ *                           where gather[p] = 0 and 1.0 where gather[p] = INT32_MAX (the one of a slack column).  An index
+ *                           outside 1 .. nnz yields 0.0.
+ *   Ah_dev f64 [B,out_len]  for pycllp_hip_dense_solve_batch_bounded: out_len = mk n, the kept rows of +-A_k as [mk, n]
+ *                           row-major (a_cols = n: no slack columns); for pycllp_hip_sparse_solve_batch_bounded: out_len =
+ *                           nnz of the handle's [+-A | I], its values in the handle's CSR order.
+ * An LP with a code gets b^ = A^_k 1 from its OWN values (the row's signed values summed in term order, plus 1.0), c^ = 0,
+ * u^ = +inf, f^ = 0; its matrix is written like every other LP's.  Non-finite values of A are not checked here: the solve
+ * kernels end such an LP with PYCLLP_STATUS_NUMERICAL.  PYCLLP_E_BADARG for a NULL required pointer, nnz < 0, out_len < 1, m, n
+ * or mk < 1, mk > m, B < 0; PYCLLP_E_UNSUPPORTED for m > 256, n + mk > 1280 or out_len > 256 * 1280; all before any HIP call;
+ * B = 0 returns 0 and launches nothing.  One launch, asynchronous on `stream`; alignment and footprint as stated at the top. */
+int pycllp_hip_general_to_bounded_batch(int m, int n, int mk, long B, const int *rowmap_dev, int nnz, const int *Aorder_dev,
+                                        const int *Aindptr_dev, const int *Aindices_dev, const double *Avals_dev, long out_len,
+                                        const int *gather_dev, const double *a_dev, const double *b_dev, const double *c_dev,
+                                        const double *l_dev, const double *u_dev, const double *f_dev, double *Ah_dev,
+                                        double *bh_dev, double *ch_dev, double *uh_dev, double *fh_dev, int *invalid_dev,
+                                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

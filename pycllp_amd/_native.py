@@ -66,6 +66,9 @@ SIGNATURES = (
     ("pycllp_hip_general_to_bounded", [_i, _i, _i, _l, _p, _i] + [_p] * 14 + [_p], _i),
     # m, n, mk, B, rowmap, l, f^, invalid, x^, y^, z^, s^, then x, y, z, s, pobj, dobj, status, iters, stream
     ("pycllp_hip_general_from_bounded", [_i, _i, _i, _l] + [_p] * 16 + [_p], _i),
+    # m, n, mk, B, rowmap, nnz, order, indptr, indices, A's values [B, nnz], out_len, gather, a, b, c, l, u, f, then A^ [B, out_len],
+    # b^, c^, u^, f^, invalid, stream
+    ("pycllp_hip_general_to_bounded_batch", [_i, _i, _i, _l, _p, _i] + [_p] * 4 + [_l] + [_p] * 13 + [_p], _i),
 )
 EXPORTS = tuple(name for name, _, _ in SIGNATURES)
 

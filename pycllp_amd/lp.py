@@ -91,11 +91,16 @@ class SparseMatrix(object):
     def todense(self, problem=0):
         return np.asarray(self.tocoo(problem).todense())
 
+    def term_order(self):
+        """i64 [nnz]: the position in the coordinate lists of the q-th term of ``csr_term_order`` (a stable sort by row) --
+        ``Aorder`` of ``pycllp_hip_general_to_bounded_batch``, which reads per-problem values ``data [B, nnz]`` as they are."""
+        return np.argsort(self._rows, kind="stable")
+
     def csr_term_order(self, problem=0):
         """(data f64 [nnz], indptr i32 [nrows + 1], indices i32 [nnz]): the CSR arrays with the terms of a row in the order of
         the coordinate lists (a stable sort by row; duplicates stay apart) -- the order in which a product with this matrix sums
         them on the host, and what ``pycllp_hip_general_to_bounded`` takes."""
-        order = np.argsort(self._rows, kind="stable")
+        order = self.term_order()
         indptr = np.concatenate([[0], np.cumsum(np.bincount(self._rows, minlength=self.nrows))])
         return (np.ascontiguousarray(self.data[problem][order], dtype=np.float64), indptr.astype(np.int32),
                 self._cols[order].astype(np.int32))
@@ -234,14 +239,17 @@ class GeneralLP(StandardLP):
         if (np.isfinite(self.a) & (self.a > self.b)).any():
             raise ValueError('Row lower bounds (a) above row upper bounds (b).')
 
-    def bounded_structure(self):
+    def bounded_structure(self, problem=None):
         """(A^, keep, sign): the part of ``to_bounded_equality_form`` that is one for the whole batch -- which rows are kept
         (``keep``: their indices; a row without a bound in every LP is dropped), with which sign (``sign``: +1.0 where b is
         finite for every LP, -1.0 where b = +inf and a is finite for every LP; any other mix raises ``ValueError``) and the
         matrix A^ = [+-A | I] as a ``SparseMatrix``.  It reads only which bounds are finite and A: a few reductions and work
-        proportional to nnz, no product with l."""
+        proportional to nnz, no product with l.  ``problem``: A^ with the values of that LP alone (what a handle is made from)
+        instead of every LP's -- for per-problem values of A the work stays O(nnz), with no signed ``[B, nnz]`` copy."""
         m, n = self.nrows, self.ncols
         rows, cols, data = self.A._rows, self.A._cols, self.A.data
+        if problem is not None and data.shape[0] > 1:
+            data = data[problem:problem + 1]
         bfin, afin = np.isfinite(self.b), np.isfinite(self.a)
         plus = bfin.all(axis=0)
         minus = ~bfin.any(axis=0) & afin.all(axis=0)
@@ -306,6 +314,45 @@ def bounded_rowmap(keep, sign, m):
     rowmap = np.zeros(m, dtype=np.int32)
     rowmap[keep] = np.where(np.asarray(sign) > 0, 1, -1) * (np.arange(len(keep)) + 1)
     return rowmap
+
+
+GATHER_ONE = np.iinfo(np.int32).max      # "this slot holds 1.0" in a gather plan
+
+
+def bounded_gather_coo(A, keep, sign):
+    """The values of ``bounded_structure()``'s A^, entry by entry of its coordinate lists, as a gather from ONE LP's values of
+    ``A`` (a ``SparseMatrix``; i32, one per entry of A^): t + 1 for +data[t], -(t + 1) for -data[t], ``GATHER_ONE`` for the 1.0
+    of a slack column.  O(nnz): the plans of ``pycllp_hip_general_to_bounded_batch`` are made from it."""
+    rows = np.asarray(A._rows)
+    rsign = np.zeros(A.nrows, dtype=np.int64)
+    rsign[keep] = np.where(np.asarray(sign) > 0, 1, -1)
+    t = np.flatnonzero(rsign[rows] != 0)
+    return np.concatenate([rsign[rows[t]] * (t + 1), np.full(len(keep), GATHER_ONE)]).astype(np.int32)
+
+
+def bounded_gather_dense(A, keep, sign):
+    """The gather plan (i32 [m' n]) of the dense ``[m', n]`` row-major image of the kept rows of +-A without the slack columns
+    (0: the slot holds 0.0) -- ``bounded_matrices`` of ``hip_general_batch_primal_normal`` for one LP.  None where two entries
+    of the structure share a (row, column): their sum is no gather."""
+    rows, cols, n = np.asarray(A._rows), np.asarray(A._cols), A.ncols
+    newrow = np.full(A.nrows, -1, dtype=np.int64)
+    newrow[keep] = np.arange(len(keep))
+    coo = bounded_gather_coo(A, keep, sign)
+    coo = coo[:coo.size - len(keep)]                 # (without the slack columns' ones)
+    t = np.abs(coo.astype(np.int64)) - 1
+    flat = newrow[rows[t]] * n + cols[t]
+    if np.unique(flat).size != flat.size:
+        return None
+    plan = np.zeros(len(keep) * n, dtype=np.int32)
+    plan[flat] = coo
+    return plan
+
+
+def bounded_gather_csr(A, keep, sign, perm):
+    """The gather plan (i32 [nnz of A^]) of the values of A^ = [+-A | I] in the CSR order ``perm`` of its structure
+    (``sparse_general_batch.csr_structure`` of ``bounded_structure()``'s A^) -- ``bounded_values`` of
+    ``hip_sparse_general_batch_primal_normal`` for one LP."""
+    return np.ascontiguousarray(bounded_gather_coo(A, keep, sign)[np.asarray(perm)])
 
 
 class BoundedMap(object):

@@ -14,10 +14,14 @@ that a variant of that kernel covers (``kernel == 'bounded wave'``), sparse or d
 On the native path the batch is converted ON THE DEVICE (``DeviceConversion``: ``pycllp_hip_general_to_bounded`` before the solve,
 ``pycllp_hip_general_from_bounded`` behind it, csrc/general_form.hip): the host only classifies the rows
 (``GeneralLP.bounded_structure``), ``solve(lp)`` uploads a, b, c, l, u and downloads results of the original size, and
-``solve_device`` is the same chain on tensors, in the ORIGINAL variables.
+``solve_device`` is the same chain on tensors, in the ORIGINAL variables.  Batches with per-problem values of A
+(``PerProblemBounded``, the mix-in of ``general_batch`` and ``sparse_general_batch``) go the same way through
+``BatchDeviceConversion`` (``pycllp_hip_general_to_bounded_batch``, csrc/general_form_pa.hip), which also writes every LP's
+matrix in the layout its solve entry takes; there the chain on tensors is ``solve_device_general``.
 """
 import contextlib
 import ctypes
+import types
 
 import numpy as np
 import torch
@@ -104,6 +108,33 @@ class DeviceConversion(object):
                        (self.rowmap, l, f, invalid, out["x"], out["y"], out["z"], out["s"], res["x"], res["y"], res["z"],
                         res["s"], out["pobj"], out["dobj"], out["status"], out["iters"]))
         return res
+
+
+class BatchDeviceConversion(DeviceConversion):
+    """``DeviceConversion`` for per-problem values of A: the row map, the structure's CSR in term order, the position of its
+    terms in the coordinate lists (``SparseMatrix.term_order``) and the gather plan ``gather`` of one LP's matrix output
+    (``lp.bounded_gather_dense`` / ``lp.bounded_gather_csr``) on ``device``; ``to_bounded`` takes the values ``[B, nnz]`` in the
+    order of the coordinate lists, as ``glp.A.data`` holds them."""
+
+    def __init__(self, glp, keep, sign, device, gather):
+        super(BatchDeviceConversion, self).__init__(glp, keep, sign, device)
+        self.data = None                                      # (no shared values)
+        self.out_len = int(gather.size)
+        self.order = torch.as_tensor(glp.A.term_order().astype(np.int32), device=device)
+        self.gather = torch.as_tensor(np.ascontiguousarray(gather, dtype=np.int32), device=device)
+
+    def to_bounded(self, stream, Adata, a, b, c, l, u, f=None):
+        """Adata [B, nnz], a, b [B, m], c, l, u [B, n], f [B] (l, f: None = 0) -> dict A [B, out_len], b [B, m'], c, u [B, N],
+        f [B], invalid [B] (i32)."""
+        B, N = int(a.shape[0]), self.n + self.mk
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)     # noqa: E731
+        cv = dict(A=new(B, self.out_len), b=new(B, self.mk), c=new(B, N), u=new(B, N), f=new(B),
+                  invalid=torch.empty(B, dtype=torch.int32, device=self.device))
+        if B:
+            self._call("pycllp_hip_general_to_bounded_batch", stream, (self.m, self.n, self.mk, B),
+                       (self.rowmap, self.nnz, self.order, self.indptr, self.indices, Adata, ctypes.c_long(self.out_len),
+                        self.gather, a, b, c, l, u, f, cv["A"], cv["b"], cv["c"], cv["u"], cv["f"], cv["invalid"]))
+        return cv
 
 
 class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
@@ -341,8 +372,14 @@ class PerProblemBounded(object):
     ``solve`` launch the one entry.  A subclass states ``_delegate_class``, ``native_fits``, ``_make_handle(blp)`` (the
     ``Handle`` of the bounded form; ``NotImplementedError`` where the library declines it), ``_values(blp)`` (the per-problem
     array as the entry takes it, numpy), ``_values_spec(B)`` (the shape that array must have, and the text that says so),
-    ``_call(A, b, c, u, out, o)`` (the ``Handle`` call) and ``_needs`` (what ``solve_device`` asks of ``init``);
-    ``_unchanged``, ``_solve_delegate`` and ``_solve_again`` where it differs."""
+    ``_call(A, b, c, u, out, o)`` (the ``Handle`` call), ``_gather(glp, keep, sign)`` (the plan of that array as a gather
+    from one LP's values, ``lp.bounded_gather_*``; None where it is none) and ``_needs`` (what ``solve_device`` asks of
+    ``init``); ``_unchanged``, ``_solve_delegate`` and ``_solve_again`` where it differs.
+
+    The batch is converted ON THE DEVICE (``BatchDeviceConversion``): ``init`` reads the batch-wide structure and LP 0's values
+    only, ``solve(lp)`` uploads ``A.data, a, b, c, l, u`` as they are and downloads results of the original size, and
+    ``solve_device_general`` is the same chain on tensors.  ``conversion`` says which conversion serves ``solve``: ``'device'``,
+    or ``'host'`` (``GeneralLP.to_bounded_equality_form`` and ``_values``) for a structure without a plan; None with a delegate."""
     _changed_what = "%d kept rows (%d at init), %d matrices"
 
     def __init__(self, *args, **kwargs):
@@ -350,6 +387,28 @@ class PerProblemBounded(object):
         self._delegate = None
         self._keepalive = None
         self.mk = None
+        self._conv_key = None
+        self.conversion = None
+
+    @staticmethod
+    def _form(glp):
+        """(the shape of the bounded form with LP 0's matrix -- ``A, nrows, ncols``: what ``native_fits``, ``_make_handle`` and
+        ``_unchanged`` read of a bounded LP --, keep, sign), from ``check_bounds`` and ``bounded_structure`` alone: the
+        ``ValueError``s of ``to_bounded_equality_form`` in their order, no product with l and no ``[B, nnz]`` copy."""
+        glp.check_bounds()
+        Ah, keep, sign = glp.bounded_structure(problem=0)
+        return types.SimpleNamespace(A=Ah, nrows=Ah.nrows, ncols=Ah.ncols), keep, sign
+
+    def _ensure_conversion(self, glp, keep, sign):
+        """The device conversion for the structure of ``glp`` and these kept rows and signs: re-made when one of them changed
+        since the last one; None where the structure has no gather plan."""
+        key = (keep.tobytes(), np.asarray(sign).tobytes(), glp.A._rows.tobytes(), glp.A._cols.tobytes())
+        if self._conv_key != key:
+            gather = self._gather(glp, keep, sign)
+            self._conv = None if gather is None else BatchDeviceConversion(glp, keep, sign, self.device, gather)
+            self._conv_key = key
+        self.conversion = "host" if self._conv is None else "device"
+        return self._conv
 
     def _make_delegate(self, glp):
         self._handle = None
@@ -362,9 +421,9 @@ class PerProblemBounded(object):
         """Fixes the shape of the bounded form (m' kept rows, N = n + m' columns) and makes the handle from it."""
         self.device = _require_gpu(self.device)
         glp = as_general(lp)
-        blp, _ = glp.to_bounded_equality_form()
+        blp, keep, sign = self._form(glp)
         self.m, self.n, self.mk = glp.nrows, glp.ncols, blp.nrows
-        self._handle = self._delegate = self._keepalive = None
+        self._handle = self._delegate = self._keepalive = self._conv = self._conv_key = self.conversion = None
         if self.native_fits(glp, blp):
             try:
                 self._handle = self._make_handle(blp)
@@ -372,6 +431,8 @@ class PerProblemBounded(object):
                 pass
         if self._handle is None:
             self._make_delegate(glp)
+        else:
+            self._ensure_conversion(glp, keep, sign)
 
     def solve_device(self, A_dev, b_dev, c_dev, u_dev, **options):
         """Device-resident entry, in the bounded form's variables: the per-problem array (``_values_spec``; the subclass says
@@ -381,6 +442,32 @@ class PerProblemBounded(object):
         if self._handle is None:
             raise RuntimeError("solve_device() needs init() on an LP the %s" % self._needs)
         return self._launch(self._dev(A_dev), self._dev(b_dev), self._dev(c_dev), self._dev(u_dev), 0, options)
+
+    def solve_device_general(self, Adata, a, b, c, l, u, f=None, **options):
+        """Device-resident entry, in the ORIGINAL variables: Adata [B, nnz] (every LP's values in the order of the coordinate
+        lists given to ``init``), a, b [B, m], c, l, u [B, n], f [B] (torch CUDA tensors, or numpy arrays, which are uploaded;
+        ``l`` and ``f`` may be None = 0) -> dict of CUDA tensors: ``RESULTS`` and ``invalid`` (i32 [B]: 0, or the check of
+        ``pycllp_hip_general_to_bounded_batch`` the LP failed; such an LP has status 3 and NaN results).  Conversion, bounded
+        solve and back-conversion are queued on the solver's stream and nothing waits for them; the kernel's verdict stands (no
+        look at the data: ``autoscale='auto'`` and ``hsd='auto'`` count as off).  ``options``: fields of ``pycllp_hip_opts``
+        for this call."""
+        if self._handle is None or self._conv is None:
+            raise RuntimeError("solve_device_general() needs init() on an LP the %s" % self._needs)
+        cv = self._conv
+        with self._on_stream():
+            Adata, a, b, c, u = (self._dev(v) for v in (Adata, a, b, c, u))
+            l, f = (None if v is None else self._dev(v) for v in (l, f))
+            B = int(a.shape[0]) if a.dim() == 2 else -1
+            if (tuple(Adata.shape) != (B, cv.nnz) or tuple(a.shape) != (B, cv.m) or tuple(b.shape) != (B, cv.m)
+                    or any(tuple(v.shape) != (B, cv.n) for v in (c, u)) or (l is not None and tuple(l.shape) != (B, cv.n))
+                    or (f is not None and tuple(f.shape) != (B,))):
+                raise ValueError("Adata must be [B,%d], a and b [B,%d], c, l and u [B,%d] and f [B] with equal B"
+                                 % (cv.nnz, cv.m, cv.n))
+            bl = cv.to_bounded(self.stream, Adata, a, b, c, l, u, f)
+            out = self._launch(bl["A"].view(self._values_spec(B)[0]), bl["b"], bl["c"], bl["u"], 0, options)
+            res = cv.from_bounded(self.stream, l, bl["f"], bl["invalid"], out)
+        self._keepalive = (Adata, a, b, c, l, u, f, bl, out)
+        return res
 
     def _launch(self, A, b, c, u, extra_flags, overrides):
         B, mk, N = int(b.shape[0]), self.mk, self.n + self.mk
@@ -416,11 +503,14 @@ class PerProblemBounded(object):
             raise ValueError("LP shape changed since init(): (%d,%d) vs (%d,%d)" % (glp.nrows, glp.ncols, self.m, self.n))
         res = None
         if self._delegate is None:
-            blp, bmap = glp.to_bounded_equality_form()
-            if not self._unchanged(glp, blp):
+            form, keep, sign = self._form(glp)
+            if not self._unchanged(glp, form):
                 raise ValueError("the bounded form changed since init(): " + self._changed_what
-                                 % (blp.nrows, self.mk, glp.A.nproblems))
-            res = self._solve_bounded(blp, bmap)
+                                 % (form.nrows, self.mk, glp.A.nproblems))
+            if self._ensure_conversion(glp, keep, sign) is not None:
+                res = self._solve_converted(glp)
+            else:
+                res = self._solve_bounded(*glp.to_bounded_equality_form())
             if res is None:                     # the entry answers PYCLLP_E_UNSUPPORTED
                 self._make_delegate(glp)
         if res is None:
@@ -438,8 +528,30 @@ class PerProblemBounded(object):
             setattr(self, k, res[k])
         return self.status
 
+    def _solve_converted(self, glp):
+        """One upload of A.data, a, b, c, l, u as they are; conversion, bounded kernel and back-conversion on the device; one
+        download of the results in the GeneralLP's variables.  None if the entry declines the handle (PYCLLP_E_UNSUPPORTED).
+        ``autoscale='auto'`` is decided from the device's b^, c^, u^ and the objectives' offset f + c'l is the host's sum, as in
+        ``HipGeneralPrimalNormalSolver._solve_native``: every result carries the bits of the host conversion."""
+        cv, B = self._conv, glp.nproblems
+        offset = np.broadcast_to(glp.f, (B,)) + (glp.c * glp.l).sum(axis=1)
+        with self._on_stream():
+            Adata, a, b, c, l, u, fh = (self._dev(np.ascontiguousarray(v))
+                                        for v in (glp.A.data, glp.a, glp.b, glp.c, glp.l, glp.u, offset))
+            bl = cv.to_bounded(self.stream, Adata, a, b, c, l, u)
+            wanted = self.autoscale == "auto" and autoscale_wanted(bl["b"], bl["c"], bl["u"])
+            try:
+                out = self._launch(bl["A"].view(self._values_spec(B)[0]), bl["b"], bl["c"], bl["u"],
+                                   _native.FLAG_AUTOSCALE if wanted else 0, {})
+            except NotImplementedError:
+                return None
+            res = cv.from_bounded(self.stream, l, fh, bl["invalid"], out)
+            torch.cuda.synchronize(self.device)
+            return {k: res[k].cpu().numpy() for k in RESULTS}
+
     def _solve_bounded(self, blp, bmap):
-        """One upload, one launch, one download; None if the entry declines the handle (PYCLLP_E_UNSUPPORTED)."""
+        """The same with the conversion on the host (a structure without a gather plan): one upload, one launch, one download;
+        None if the entry declines the handle (PYCLLP_E_UNSUPPORTED)."""
         wanted = self.autoscale == "auto" and autoscale_wanted(blp.b, blp.c, blp.u)
         A, b, c, u = (self._dev(np.ascontiguousarray(v)) for v in (self._values(blp), blp.b, blp.c, blp.u))
         try:

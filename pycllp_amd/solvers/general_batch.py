@@ -14,6 +14,7 @@ import numpy as np
 
 from .dense_batch import densify_batch
 from .general import NATIVE_MAX_COLS, NATIVE_MAX_ROWS, HipGeneralPrimalNormalSolver, PerProblemBounded
+from ..lp import bounded_gather_dense
 from .hip import BOUNDED_RESULTS, Handle
 
 OUTPUTS = BOUNDED_RESULTS      # of the entry, in the bounded form's variables
@@ -26,7 +27,8 @@ class HipGeneralBatchPrimalNormalSolver(PerProblemBounded, HipGeneralPrimalNorma
     ``hsd='auto'`` the LPs that do not end optimal on the kernel are solved again through the expansion
     (``solve_expanded``), every other LP keeps its bits; ``hsd=False``: the kernel's verdict stands.  ``solve_device`` takes
     A [B, m', n] (kept rows, signs applied, no slack columns: ``bounded_matrices``); the handle is made from LP 0's
-    ``[A^_0 | I]``."""
+    ``[A^_0 | I]``.  ``solve_device_general`` takes the LPs as they are (``PerProblemBounded``); ``conversion`` is ``'device'``, or
+    ``'host'`` for a structure with duplicate (row, column) entries."""
     name = 'hip_general_batch_primal_normal'
     _native_kernel = "bounded group per-problem"
     _delegate_class = HipGeneralPrimalNormalSolver
@@ -45,6 +47,11 @@ class HipGeneralBatchPrimalNormalSolver(PerProblemBounded, HipGeneralPrimalNorma
         return densify_batch(blp.A._rows, blp.A._cols, np.broadcast_to(data, (blp.nproblems, data.shape[1])), mk, n)
 
     _values = bounded_matrices
+
+    @staticmethod
+    def _gather(glp, keep, sign):
+        """None for a structure with duplicate (row, column) entries: ``densify_batch`` sums them, a gather cannot."""
+        return bounded_gather_dense(glp.A, keep, sign)
 
     def _make_handle(self, blp):
         A0 = np.ascontiguousarray(blp.A.todense(0), dtype=np.float64).reshape(blp.nrows, blp.ncols)

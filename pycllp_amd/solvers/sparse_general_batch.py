@@ -14,6 +14,7 @@ unchanged.  The machinery is ``general.PerProblemBounded``'s, shared with ``gene
 import numpy as np
 import scipy.sparse as sp
 
+from ..lp import bounded_gather_csr
 from .general import (WAVE_MAX_COLS, WAVE_MAX_ROWS, HipSparseGeneralPrimalNormalSolver, PerProblemBounded, expansion_rows,
                       subset)
 from .general_batch import OUTPUTS  # noqa: F401  (the keys solve_device returns)
@@ -41,7 +42,8 @@ class HipSparseGeneralBatchPrimalNormalSolver(PerProblemBounded, HipSparseGenera
     ``'bounded wave'`` / ``'expanded'``.  With ``hsd='auto'`` the LPs that do not end optimal on the kernel are solved again
     through the expansion (``solve_expanded``) where the library takes it for per-problem values; elsewhere the kernel's
     status stands, and every other LP keeps its bits.  ``solve_device`` takes Adata [B, nnz] (values of A^ in the handle's CSR
-    order, the slack columns' ones among them: ``bounded_values``); the handle is made from the structure of A^."""
+    order, the slack columns' ones among them: ``bounded_values``); the handle is made from the structure of A^.
+    ``solve_device_general`` takes the LPs as they are (``PerProblemBounded``); ``conversion`` is ``'device'``."""
     name = 'hip_sparse_general_batch_primal_normal'
     _native_kernel = "bounded wave per-problem"
     _delegate_class = HipSparseGeneralPrimalNormalSolver
@@ -62,6 +64,9 @@ class HipSparseGeneralBatchPrimalNormalSolver(PerProblemBounded, HipSparseGenera
         return np.ascontiguousarray(data[:, self._perm])
 
     _values = bounded_values
+
+    def _gather(self, glp, keep, sign):
+        return bounded_gather_csr(glp.A, keep, sign, self._perm)
 
     def init(self, lp, verbose=0):
         self._perm = None
