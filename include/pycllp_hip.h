@@ -84,6 +84,20 @@ extern "C" {
 #define PYCLLP_FLAG_AUTOSCALE 8 /* solve every LP with b/max|b| and c/max|c| and scale the results back: makes the
                                    unit-floored tolerances and the x=z=y=1 start scale invariant (not in the reference;
                                    not available with PYCLLP_FLAG_WAVE_KERNEL)                                       */
+#define PYCLLP_FLAG_AUTOSCALE_PER_LP 256 /* PYCLLP_FLAG_AUTOSCALE decided per LP, inside the kernels: an LP is solved exactly as
+                                   under PYCLLP_FLAG_AUTOSCALE (same divisions, same scale-back) if and only if it is OUT OF BAND
+                                   -- max|b|, max|c| over all n columns or, on the entries with upper bounds, the largest finite
+                                   positive u of the LP (an LP without one is left out of that test) is finite and lies outside
+                                   [0.1, 10]; 0.1 and 10 themselves are in band, b = 0 is out of band -- and with the scale
+                                   factors 1 otherwise.  Division and multiplication by 1.0 are exact: an in-band LP carries the
+                                   bits of the call without either flag, an out-of-band LP those of the call with
+                                   PYCLLP_FLAG_AUTOSCALE, whatever else is in the batch -- no caller-side band test, no
+                                   device-to-host sync.  (An LP with a NaN in b, c or u may get either verdict; it ends with
+                                   PYCLLP_STATUS_NUMERICAL under both.)  Every solve entry honours it where it honours
+                                   PYCLLP_FLAG_AUTOSCALE and refuses it where it refuses that flag, with the same code; both
+                                   flags together: PYCLLP_E_BADARG, before the handle is read.  The stand-alone Newton / LDL'
+                                   entries ignore both.  pycllp_amd.solvers.hip.autoscale_mask restates the rule
+                                   (DESIGN.md section 23).                                                                    */
 #define PYCLLP_FLAG_HSD 32 /* solve on the homogeneous self-dual embedding (the model of the reference's CPU solver,
                               pycllp/ipo/hsd.c:27-312, re-derived on the normal equations): infeasible
                               and unbounded LPs end with a certificate after ~12-15 iterations -- status 2 with (y, z):

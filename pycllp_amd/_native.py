@@ -15,6 +15,7 @@ FLAG_WARM_START, FLAG_WAVE_KERNEL, FLAG_FORCE_GUARD_PATH, FLAG_AUTOSCALE, FLAG_N
 FLAG_HSD = 32
 FLAG_BLOCK_KERNEL = 64
 FLAG_PREDCORR = 128
+FLAG_AUTOSCALE_PER_LP = 256
 
 
 class Opts(ctypes.Structure):

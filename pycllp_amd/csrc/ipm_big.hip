@@ -508,7 +508,13 @@ ipm_big_kernel(BigTab T, long B, const double* __restrict__ bg, const double* __
             for (int k = 0; k < BNC; k++) cm = fmax(cm, fabs(c[k]));
             sb = bmax((tid < m) ? fabs(bs[tid]) : 0.0, red, tid);
             sc = bmax(cm, red, tid);
-            sb = (sb > 0.0) ? sb : 1.0; sc = (sc > 0.0) ? sc : 1.0;
+            // (WGPC = 3, 168 registers: the flags through an opaque copy.  Read plainly, the test of the per-LP bit is hoisted
+            // out of the LP loop, and the SGPR that then lives through every iteration costs the iteration loop of <3, 3> two
+            // more reloads from scratch.  WGPC = 2: the plain read; the copy costs <2, 2> a spilled VGPR.)
+            int fl = o.flags;
+            if constexpr (WGPC == 3) fl = iopaque(fl);
+            const bool scaled = autoscale_lp(fl, sb, sc, 0.0);
+            sb = (scaled && sb > 0.0) ? sb : 1.0; sc = (scaled && sc > 0.0) ? sc : 1.0;
             if (tid < m) { bs[tid] = bs[tid] / sb; if (warm) ys[tid] = ys[tid] / sc; }
 #pragma unroll
             for (int k = 0; k < BNC; k++) {

@@ -303,7 +303,8 @@ ipm_block_kernel(BlockA A, long B, const double* __restrict__ bg, const double* 
             for (int q = 0; q < BLK_NC; q++) cm = fmax(cm, fabs(c[q]));
             sb = blk_max((tid < m) ? fabs(bs[tid]) : 0.0, red, tid);
             sc = blk_max(cm, red, tid);
-            sb = (sb > 0.0) ? sb : 1.0; sc = (sc > 0.0) ? sc : 1.0;
+            const bool scaled = autoscale_lp(o.flags, sb, sc, 0.0);   // (an LP the wave kernel deferred: the verdict it had there)
+            sb = (scaled && sb > 0.0) ? sb : 1.0; sc = (scaled && sc > 0.0) ? sc : 1.0;
             if (tid < m) { bs[tid] = bs[tid] / sb; if (warm) ys[tid] = ys[tid] / sc; }
 #pragma unroll
             for (int q = 0; q < BLK_NC; q++) {

@@ -703,6 +703,9 @@ static DevOpts to_dev(const pycllp_hip_opts* opts) {
     DevOpts o;
     o.eps = d.eps; o.delta = d.delta; o.r = d.r; o.pivot_floor = d.pivot_floor; o.refine_tol = d.refine_tol;
     o.max_iter = d.max_iter; o.flags = d.flags;
+    // PYCLLP_FLAG_AUTOSCALE_PER_LP reaches the kernels WITH PYCLLP_FLAG_AUTOSCALE (wave_common.h autoscale_lp): they test the
+    // flag they always tested for "the scaling code runs", and the new one only inside it
+    if (o.flags & PYCLLP_FLAG_AUTOSCALE_PER_LP) o.flags |= PYCLLP_FLAG_AUTOSCALE;
     // PYCLLP_MAX_REFINE_AUTO: the reference's cap of 5 passes (ldl.cl:645) on its own path; 20 on the homogeneous self-dual
     // variant, whose last systems are harder (with 5, LP 7557 of config 5's share stalls for 70-150 iterations)
     o.max_refine = d.max_refine >= 0 ? d.max_refine : ((d.flags & PYCLLP_FLAG_HSD) ? PYCLLP_MAX_REFINE_HSD : PYCLLP_MAX_REFINE_PLAIN);
@@ -773,6 +776,13 @@ static int entry_err(int code, const char* entry, const char* what) {
 int pycllp_entry_error(int code, const char* entry, const char* what) { return entry_err(code, entry, what); }   // host_error.h
 int pycllp_runtime_error(int code, const char* what) { return set_err(code, what); }
 
+// PYCLLP_FLAG_AUTOSCALE scales every LP, PYCLLP_FLAG_AUTOSCALE_PER_LP those out of band: every solve entry refuses the pair, right
+// after its handle / B check and before it reads the handle
+static const char* const kBothAutoscales = "PYCLLP_FLAG_AUTOSCALE and PYCLLP_FLAG_AUTOSCALE_PER_LP exclude each other";
+static bool both_autoscales(const pycllp_hip_opts* opts) {
+    return ((opts ? opts->flags : 0) & PYCLLP_AUTOSCALE_ANY) == PYCLLP_AUTOSCALE_ANY;
+}
+
 // The argument checks that open the five restricted entries (pycllp_hip_dense_solve_bounded, _dense_solve_batch,
 // _dense_solve_batch_bounded, _sparse_solve_bounded, _sparse_solve_batch_bounded), in their order: the handle and B with the
 // pointers the entry needs whatever B is (`always`), the flags it rejects (`rejected`, with the entry's sentence about them),
@@ -781,6 +791,7 @@ int pycllp_runtime_error(int code, const char* what) { return set_err(code, what
 static int check_restricted(const char* entry, const void* h, long B, bool always, const pycllp_hip_opts* opts, int rejected,
                             const char* rejected_what, bool with_lps) {
     if (!h || B < 0 || !always) return entry_err(PYCLLP_E_BADARG, entry, "bad argument");
+    if (both_autoscales(opts)) return entry_err(PYCLLP_E_BADARG, entry, kBothAutoscales);
     if ((opts ? opts->flags : 0) & rejected) return entry_err(PYCLLP_E_BADARG, entry, rejected_what);
     if (B > 0 && !with_lps) return entry_err(PYCLLP_E_BADARG, entry, "bad argument");
     return 0;
@@ -899,6 +910,7 @@ int pycllp_hip_dense_solve(pycllp_hip_dense* h, long B, const double* b_dev, con
                            double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev, int* status_dev,
                            int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
     if (!h || B < 0) return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve: bad argument");
+    if (both_autoscales(opts)) return entry_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve", kBothAutoscales);
     if (B == 0) return 0;  // empty batch: nothing to do (pointers may be NULL)
     if (!b_dev || !c_dev || !x_dev || !status_dev)
         return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve: bad argument");
@@ -914,8 +926,8 @@ int pycllp_hip_dense_solve(pycllp_hip_dense* h, long B, const double* b_dev, con
     DevOpts o = to_dev(opts);
     if ((o.flags & PYCLLP_FLAG_WARM_START) && (!y_dev || !z_dev))
         return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve: warm start needs y_dev and z_dev");
-    if ((o.flags & PYCLLP_FLAG_AUTOSCALE) && (o.flags & PYCLLP_FLAG_WAVE_KERNEL))
-        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve: PYCLLP_FLAG_AUTOSCALE is not available with PYCLLP_FLAG_WAVE_KERNEL");
+    if ((o.flags & PYCLLP_AUTOSCALE_ANY) && (o.flags & PYCLLP_FLAG_WAVE_KERNEL))
+        return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve: PYCLLP_FLAG_AUTOSCALE (and _PER_LP) is not available with PYCLLP_FLAG_WAVE_KERNEL");
     if ((o.flags & PYCLLP_FLAG_HSD) && (o.flags & PYCLLP_FLAG_WAVE_KERNEL))
         return set_err(PYCLLP_E_BADARG, "pycllp_hip_dense_solve: PYCLLP_FLAG_HSD is not available with PYCLLP_FLAG_WAVE_KERNEL");
     if ((o.flags & PYCLLP_FLAG_PREDCORR) && (o.flags & (PYCLLP_FLAG_HSD | PYCLLP_FLAG_WAVE_KERNEL)))
@@ -1250,6 +1262,7 @@ static int sparse_solve_impl(pycllp_hip_sparse* h, long B, const double* a_batch
                              double* x_dev, double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev, int* status_dev,
                              int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
     if (!h || B < 0) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve: bad argument");
+    if (both_autoscales(opts)) return entry_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve", kBothAutoscales);
     if (B == 0) return 0;
     if (!b_dev || !c_dev || !x_dev || !status_dev) return set_err(PYCLLP_E_BADARG, "pycllp_hip_sparse_solve: bad argument");
     DevOpts o = to_dev(opts);

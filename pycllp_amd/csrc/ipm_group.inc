@@ -772,7 +772,8 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
 #pragma unroll
                 for (int q = 0; q < NCG; q++) cm = fmax(cm, fabs(c[q]));
                 double sb = grp_max<MP>(fabs(b)), sc = grp_max<MP>(cm);
-                sb = (sb > 0.0) ? sb : 1.0; sc = (sc > 0.0) ? sc : 1.0;
+                const bool scaled = autoscale_lp(o.flags, sb, sc, 0.0);
+                sb = (scaled && sb > 0.0) ? sb : 1.0; sc = (scaled && sc > 0.0) ? sc : 1.0;
                 if (fresh) {
                     b = b / sb;
 #pragma unroll
@@ -831,7 +832,8 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 for (int q = 0; q < NCG; q++) cm = fmax(cm, ok[q] ? fabs(cg[lp * n + gcol(q, go)]) : 0.0);
                 sb = grp_max<MP>(rowok ? fabs(bg[lp * m + go]) : 0.0);
                 sc = grp_max<MP>(cm);
-                sb = (sb > 0.0) ? sb : 1.0; sc = (sc > 0.0) ? sc : 1.0;
+                const bool scaled = autoscale_lp(o.flags, sb, sc, 0.0);      // (the verdict of the load: the same maxima)
+                sb = (scaled && sb > 0.0) ? sb : 1.0; sc = (scaled && sc > 0.0) ? sc : 1.0;
             }
 #pragma unroll
             for (int q = 0; q < NCG; q++) {

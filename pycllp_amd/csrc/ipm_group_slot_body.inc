@@ -140,11 +140,18 @@
                 y = rowok ? 1.0 : 0.0;
             }
             if (autoscale) {   // solve the LP with b, u / max|b| and c / max|c| (PYCLLP_FLAG_AUTOSCALE); undone when storing
-                double cm = 0.0;
+                // the per-LP verdict (autoscale_lp) looks at max|c| over ALL columns and at the largest finite positive u
+                double cm = 0.0, ca = 0.0, um = 0.0;
 #pragma unroll
-                for (int q = 0; q < NCG; q++) cm = fmax(cm, (!BD || act(q)) ? fabs(c[q]) : 0.0);   // (c = 0 where !ok)
+                for (int q = 0; q < NCG; q++) {
+                    cm = fmax(cm, (!BD || act(q)) ? fabs(c[q]) : 0.0);   // (c = 0 where !ok)
+                    if constexpr (BD) { ca = fmax(ca, fabs(c[q])); um = fmax(um, bnd(q) ? u[q] : 0.0); }
+                }
                 double sb = grp_max<MP>(fabs(b)), sc = grp_max<MP>(cm);
-                sb = (sb > 0.0) ? sb : 1.0; sc = (sc > 0.0) ? sc : 1.0;
+                bool scaled;
+                if constexpr (BD) scaled = autoscale_lp(o.flags, sb, grp_max<MP>(ca), grp_max<MP>(um));
+                else scaled = autoscale_lp(o.flags, sb, sc, 0.0);
+                sb = (scaled && sb > 0.0) ? sb : 1.0; sc = (scaled && sc > 0.0) ? sc : 1.0;
                 // BD: sb = inf -- an Inf in b: the LP ends NUMERICAL at iteration 0 either way -- is no scale factor: u / inf = 0
                 // would turn every column into a fixed one, for finalize's scale factors and stores too
                 if constexpr (BD) sb = (sb < HUGE_VAL) ? sb : 1.0;
@@ -214,12 +221,22 @@
             int gro = grp;
             asm volatile("" : "+v"(gro));
             if (autoscale) {   // recover the scale factors from the inputs (cheaper than carrying them in registers)
-                double cm = 0.0;
+                double cm = 0.0, ca = 0.0, um = 0.0;
 #pragma unroll
-                for (int q = 0; q < NCG; q++) cm = fmax(cm, act(q) ? fabs(cg[lp * n + gcol(q, go)]) : 0.0);
+                for (int q = 0; q < NCG; q++) {
+                    const double cj = ok[q] ? fabs(cg[lp * n + gcol(q, go)]) : 0.0;
+                    cm = fmax(cm, act(q) ? cj : 0.0);
+                    if constexpr (BD) {   // (u[q] is the scaled bound: the verdict of the load came from the input)
+                        const double uj = ok[q] ? ug[lp * n + gcol(q, go)] : 0.0;
+                        ca = fmax(ca, cj); um = fmax(um, (uj > 0.0 && uj < HUGE_VAL) ? uj : 0.0);
+                    }
+                }
                 sb = grp_max<MP>(rowok ? fabs(bg[lp * m + go]) : 0.0);
                 sc = grp_max<MP>(cm);
-                sb = (sb > 0.0) ? sb : 1.0; sc = (sc > 0.0) ? sc : 1.0;
+                bool scaled;
+                if constexpr (BD) scaled = autoscale_lp(o.flags, sb, grp_max<MP>(ca), grp_max<MP>(um));
+                else scaled = autoscale_lp(o.flags, sb, sc, 0.0);
+                sb = (scaled && sb > 0.0) ? sb : 1.0; sc = (scaled && sc > 0.0) ? sc : 1.0;
             }
 #pragma unroll
             for (int q = 0; q < NCG; q++) {

@@ -74,19 +74,23 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
         // PYCLLP_FLAG_AUTOSCALE: b, u / max|b| and c / max|c| over the columns that take part (as the lane-group kernel)
         double sb = 1.0, sc = 1.0;
         if (autoscale) {
-            double cm = 0.0, bm = 0.0;
+            // (the per-LP verdict, autoscale_lp, looks at max|c| over ALL columns and at the largest finite positive u)
+            double cm = 0.0, bm = 0.0, ca = 0.0, um = 0.0;
 #pragma unroll
             for (int qq = 0; qq < NQ; qq++) {
                 const unsigned jo = w.coff(qq);
                 const double uj = buf_ld(ru, jo), cj = buf_ld(rc, jo);
                 cm = fmax(cm, uj > 0.0 ? fabs(cj) : 0.0);
+                ca = fmax(ca, fabs(cj));
+                um = fmax(um, (uj > 0.0 && uj < HUGE_VAL) ? uj : 0.0);
             }
 #pragma unroll
             for (int r2 = 0; r2 < MR; r2++) bm = fmax(bm, okr[r2] ? fabs(bg[lp * m + lane + 64 * r2]) : 0.0);
             sb = wmax(bm); sc = wmax(cm);
+            const bool scaled = autoscale_lp(o.flags, sb, wmax(ca), wmax(um));
             // (sb = inf -- an Inf in b: the LP ends NUMERICAL at iteration 0 either way -- is no scale factor: u / inf = 0 would turn
             // every column into a fixed one, at the store too, where y, z and s depend on which columns take part)
-            sb = uni((sb > 0.0 && sb < HUGE_VAL) ? sb : 1.0); sc = uni((sc > 0.0) ? sc : 1.0);
+            sb = uni((scaled && sb > 0.0 && sb < HUGE_VAL) ? sb : 1.0); sc = uni((scaled && sc > 0.0) ? sc : 1.0);
         }
         // ---- start: z = s = y = 1, x = min(1, u/2), t = u - x (tau = 0); norms for the tolerances ----
         double c2 = 0.0, u2 = 0.0, nbc = 0.0;

@@ -34,7 +34,7 @@ hsd_wreg_kernel(WregTab T, long B, const double* __restrict__ ag, const double* 
         if constexpr (PA) load_lp_values(w, ag, lp, T.nnz);
         const __amdgpu_buffer_rsrc_t rc = row_rsrc(cg + lp * n, n), rx = row_rsrc(xg + lp * n, n), rz = row_rsrc(zg ? zg + lp * n : nullptr, n);
         // x and z cross the loop's back edge in LDS (where load_lp parks them and where they wait during factor and solves), as in ipm_wreg_kernel
-        const LpStart s0 = load_lp<true>(w, okc, okr, lp, bg, yg, rc, rx, rz, warm, autoscale);
+        const LpStart s0 = load_lp<true>(w, okc, okr, lp, bg, yg, rc, rx, rz, warm, o.flags);
         const double sc = s0.sc;
         const double nbn = uni(sqrt(s0.nb2)), ncn = uni(sqrt(s0.nc2));
         const double tol_r = uni(o.eps * (1.0 + nbn)), tol_s = uni(o.eps * (1.0 + ncn));

@@ -34,7 +34,7 @@ ipm_wreg_kernel(WregTab T, long B, const double* __restrict__ ag, const double* 
     while (lp < B) {
         if constexpr (PA) load_lp_values(w, ag, lp, T.nnz);
         const __amdgpu_buffer_rsrc_t rc = row_rsrc(cg + lp * n, n), rx = row_rsrc(xg + lp * n, n), rz = row_rsrc(zg ? zg + lp * n : nullptr, n);
-        const LpStart s0 = load_lp<false>(w, okc, okr, lp, bg, yg, rc, rx, rz, warm, autoscale);
+        const LpStart s0 = load_lp<false>(w, okc, okr, lp, bg, yg, rc, rx, rz, warm, o.flags);
         const double sc = s0.sc, nb2 = s0.nb2, nc2 = s0.nc2;
         const double tol_r = uni(o.eps * (1.0 + sqrt(nb2))), tol_s = uni(o.eps * (1.0 + sqrt(nc2)));
         const double etol = uni(o.refine_tol * (1.0 + sqrt(nb2)));

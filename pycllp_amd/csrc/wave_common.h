@@ -56,6 +56,27 @@ __device__ __forceinline__ double readlane_d(double v, int srclane) {
 // every use instead of being hoisted out of a persistent loop into long-lived VGPRs
 __device__ __forceinline__ double sopaque(double v) { asm volatile("" : "+s"(v)); return v; }
 __device__ __forceinline__ int iopaque(int v) { asm volatile("" : "+s"(v)); return v; }
+// The two scaling options as the kernels see them (DevOpts::flags; to_dev in ipm_dense.hip): PYCLLP_FLAG_AUTOSCALE -- the scaling
+// code of an LP's load and store runs, as it always has -- and PYCLLP_FLAG_AUTOSCALE_PER_LP beside it -- that code takes a verdict
+// per LP.  (A caller sets one of the two; the entries refuse both and hand a caller's PER_LP on as the pair.)
+#define PYCLLP_AUTOSCALE_ANY (PYCLLP_FLAG_AUTOSCALE | PYCLLP_FLAG_AUTOSCALE_PER_LP)
+// The verdict for ONE LP, taken where the LP's raw maxima are known (load and, where the scale factors are recomputed from the
+// inputs, store): without PYCLLP_FLAG_AUTOSCALE_PER_LP every LP is scaled, with it an LP is scaled if and only if it is out of
+// band -- max|b| (mb), max|c| over all n columns (mc) or, where mu > 0, the largest finite positive u (mu; 0: none, or an entry
+// without bounds) outside [0.1, 10] and finite; the edges are in band.  A caller that gets false solves with sb = sc = 1:
+// x / 1.0 and x * 1.0 are exact, so the LP carries the bits of a launch without either flag.  The host's restatement is
+// autoscale_mask (solvers/hip.py).  The maxima come from fmax, which passes over a NaN: an LP with a NaN in its data may get
+// either verdict and ends with PYCLLP_STATUS_NUMERICAL under both.
+// The only f64 constant is 10, which every solve kernel holds anyway (the 10x-growth exits): an f64 literal needs a register
+// pair, which the compiler loads once, outside the persistent LP loop, and keeps through every iteration -- a new one costs the
+// largest wave kernels scratch.  So "mx < 0.1" is written 10 mx < 1, which is the same set of doubles: rounding is monotone,
+// fl(10 * 0.1) = 1 (0.1 is 0x3FB999999999999A, 10 times it 1 + 5.6e-17) and fl(10 * pred(0.1)) = 1 - 2^-53 < 1 (the exact
+// product is 1 - 8.3e-17, nearer to 1 - 2^-53 than to 1); an overflowing 10 mx is inf, not below 1.  And "finite" is written
+// mx * 0 == 0 (inf * 0 is NaN) for the same reason: isfinite() brings its own constants.
+__device__ __forceinline__ bool out_of_band(double mx) { return 10.0 * mx < 1.0 || (mx > 10.0 && mx * 0.0 == 0.0); }
+__device__ __forceinline__ bool autoscale_lp(int flags, double mb, double mc, double mu) {
+    return (flags & PYCLLP_FLAG_AUTOSCALE_PER_LP) == 0 || out_of_band(mb) || out_of_band(mc) || (mu > 0.0 && out_of_band(mu));
+}
 __device__ __forceinline__ double fast_rcp(double a) {
     double r = __builtin_amdgcn_rcp(a);
     r = fma(r, fma(-a, r, 1.0), r);

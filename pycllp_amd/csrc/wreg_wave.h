@@ -1103,13 +1103,15 @@ __device__ __forceinline__ long next_item(int* queue, int lane) {
 // Start of one LP in ipm_wreg_kernel and hsd_wreg_kernel (HSD): b and y into bs_() / ys_(), x and z parked (px, pz), every
 // lane in step behind the last store.  Cold start x = z = 1 and y = 1 (HSD: y = 0); PYCLLP_FLAG_WARM_START takes x, y, z
 // from the output arrays.  PYCLLP_FLAG_AUTOSCALE: the LP is solved with b / max|b| and c / max|c| (the same divisions as
-// ipm_block_kernel and the oracle), undone by store_lp.
+// ipm_block_kernel and the oracle), undone by store_lp; PYCLLP_FLAG_AUTOSCALE_PER_LP: that, or sb = sc = 1, by autoscale_lp's
+// verdict on the LP (``flags``: the options' flags).
 struct LpStart { double sb, sc, nb2, nc2, g0; };      // the two scales, ||b||^2, ||c||^2, x'z of a warm start (HSD only)
 template <bool HSD, int MB, int NQ, bool DA, bool PA>
 __device__ __forceinline__ LpStart load_lp(WReg<MB, NQ, DA, PA>& w, const bool (&okc)[NQ], const bool (&okr)[WGeo<MB>::MR], long lp,
                                            const double* bg, const double* yg, __amdgpu_buffer_rsrc_t rc, __amdgpu_buffer_rsrc_t rx,
-                                           __amdgpu_buffer_rsrc_t rz, bool warm, bool autoscale) {
+                                           __amdgpu_buffer_rsrc_t rz, bool warm, int flags) {
     constexpr int MR = WGeo<MB>::MR, MP = WGeo<MB>::MP;
+    const bool autoscale = (flags & PYCLLP_FLAG_AUTOSCALE) != 0;
     const int& lane = w.lane;
     const int m = w.m;
     double x[NQ], z[NQ];
@@ -1122,7 +1124,8 @@ __device__ __forceinline__ LpStart load_lp(WReg<MB, NQ, DA, PA>& w, const bool (
 #pragma unroll
         for (int r2 = 0; r2 < MR; r2++) bm = fmax(bm, okr[r2] ? fabs(bg[lp * m + lane + 64 * r2]) : 0.0);
         sb = wmax(bm); sc = wmax(cm);
-        sb = uni((sb > 0.0) ? sb : 1.0); sc = uni((sc > 0.0) ? sc : 1.0);
+        const bool scaled = autoscale_lp(flags, sb, sc, 0.0);
+        sb = uni((scaled && sb > 0.0) ? sb : 1.0); sc = uni((scaled && sc > 0.0) ? sc : 1.0);
     }
 #pragma unroll
     for (int qq = 0; qq < NQ; qq++) {

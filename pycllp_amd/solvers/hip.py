@@ -97,6 +97,48 @@ def autoscale_wanted(b, c, u=None):
     return False
 
 
+def autoscale_mask(b, c, u=None):
+    """The ``autoscale='per_lp'`` rule, the specification of what the kernels decide under PYCLLP_FLAG_AUTOSCALE_PER_LP: bool
+    [B], True where the LP is OUT OF BAND and is solved scaled -- ``autoscale_wanted`` applied to that LP alone.  Out of band:
+    max|b|, or max|c| over all n columns, is finite and < 0.1 or > 10 (the edges are in band; b = 0 is out of band), or --
+    ``u`` given -- the largest finite positive u of the LP is (an LP without one is left out of that test).  A non-finite
+    maximum (a NaN or an Inf in the row) triggers nothing by itself.  b [B, m], c [B, n], u [B, n] (a single LP may come as
+    vectors): numpy arrays give a numpy array, torch tensors a tensor on their device; an array without columns says False.
+    ``autoscale_wanted(b, c, u) == bool(autoscale_mask(b, c, u).any())``."""
+    lo, hi = AUTOSCALE_BAND
+    use_torch = any(isinstance(v, torch.Tensor) for v in (b, c, u))
+
+    def rows(v):
+        if use_torch:
+            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v, dtype=np.float64))
+        else:
+            v = np.asarray(v, dtype=np.float64)
+        return v.reshape(1, -1) if v.ndim == 1 else v
+
+    def part(v, bounds):
+        v = rows(v)
+        xp = torch if use_torch else np
+        if v.shape[-1] == 0:
+            return (torch.zeros(tuple(v.shape[:-1]), dtype=torch.bool, device=v.device) if use_torch
+                    else np.zeros(v.shape[:-1], dtype=bool))
+        if bounds:
+            fin = xp.isfinite(v) & (v > 0)
+            mx = xp.where(fin, v, xp.zeros_like(v))
+            mx = mx.amax(dim=-1) if use_torch else mx.max(axis=-1)
+            return fin.any(-1) & ((mx < lo) | (mx > hi))
+        mx = v.abs().amax(dim=-1) if use_torch else np.abs(v).max(axis=-1)
+        return ((mx < lo) | (mx > hi)) & xp.isfinite(mx)
+
+    mask = part(b, False)
+    if use_torch:
+        parts = [part(c, False)] + ([part(u, True)] if u is not None else [])
+        for q in parts:
+            mask = mask | q.to(mask.device)
+        return mask
+    mask = mask | part(c, False)
+    return mask | part(u, True) if u is not None else mask
+
+
 def warm_lifted(x, lift=1e-3):
     """The start point ``warm_start=True`` makes of a previous x (or z): max(x, lift * max(1, |x|_inf)) per LP (numpy)."""
     x = np.asarray(x, dtype=np.float64)
@@ -111,8 +153,10 @@ def _require_gpu(device):
 
 def plugin_options(options, hsd="auto", autoscale="auto", predcorr=False, warm_start=False, warm_lift=1e-3):
     """(hsd, autoscale, warm_start, warm_lift, options) of a solver plugin's constructor arguments: ``hsd`` and ``autoscale``
-    as True, False or 'auto' (FLAG_HSD / FLAG_AUTOSCALE in ``flags`` switch them on), ``options`` -- fields of
-    ``pycllp_hip_opts`` -- with the flags of hsd=True, autoscale=True and predcorr merged into ``flags``, names validated."""
+    as True, False or 'auto' (FLAG_HSD / FLAG_AUTOSCALE in ``flags`` switch them on), ``autoscale`` also as 'per_lp'
+    (FLAG_AUTOSCALE_PER_LP, likewise: the kernels decide for every LP by itself, ``autoscale_mask``), ``options`` -- fields of
+    ``pycllp_hip_opts`` -- with the flags of hsd=True, autoscale=True or 'per_lp' and predcorr merged into ``flags``, names
+    validated.  Every launch of a plugin takes its flags from ``options``, so 'per_lp' reaches all of them."""
     if isinstance(hsd, str):
         if hsd != "auto":
             raise ValueError("hsd must be True, False or 'auto'")
@@ -123,17 +167,24 @@ def plugin_options(options, hsd="auto", autoscale="auto", predcorr=False, warm_s
     if predcorr and hsd is True:
         raise ValueError("predcorr is an option of the reference's path; it cannot be combined with hsd=True")
     if isinstance(autoscale, str):
-        if autoscale != "auto":
-            raise ValueError("autoscale must be True, False or 'auto'")
+        if autoscale not in ("auto", "per_lp"):
+            raise ValueError("autoscale must be True, False, 'auto' or 'per_lp'")
     else:
         autoscale = bool(autoscale)
     options = dict(options)
     flags = int(options.get("flags", 0))
-    if flags & _native.FLAG_AUTOSCALE:
+    if flags & _native.FLAG_AUTOSCALE_PER_LP:
+        if flags & _native.FLAG_AUTOSCALE or autoscale is True:
+            raise ValueError("autoscale: FLAG_AUTOSCALE (True) and FLAG_AUTOSCALE_PER_LP ('per_lp') exclude each other")
+        autoscale = "per_lp"
+    elif flags & _native.FLAG_AUTOSCALE:
+        if autoscale == "per_lp":
+            raise ValueError("autoscale: FLAG_AUTOSCALE (True) and FLAG_AUTOSCALE_PER_LP ('per_lp') exclude each other")
         autoscale = True
     if flags & _native.FLAG_HSD:
         hsd = True
     implied = ((_native.FLAG_PREDCORR if predcorr else 0) | (_native.FLAG_AUTOSCALE if autoscale is True else 0)
+               | (_native.FLAG_AUTOSCALE_PER_LP if autoscale == "per_lp" else 0)
                | (_native.FLAG_HSD if hsd is True else 0))
     if implied:
         options["flags"] = flags | implied
@@ -308,7 +359,11 @@ class HipDensePrimalNormalSolver(DeviceArrays, BaseSolver):
         scales the results back: for b or c orders of magnitude away from 1.  ``autoscale="auto"`` (default) switches it on
         in ``solve(lp)`` for a batch in which some LP has max|b| or max|c| outside [0.1, 10] (``autoscale_wanted``) and
         leaves a batch inside that band -- the reference's test and benchmark regime -- on the reference's arithmetic bit
-        for bit; ``solve_device`` (asynchronous, no look at the data) treats "auto" as off.
+        for bit; ``solve_device`` (asynchronous, no look at the data) treats "auto" as off.  ``autoscale="per_lp"``
+        (PYCLLP_FLAG_AUTOSCALE_PER_LP) leaves the decision to the kernels, LP by LP (``autoscale_mask``): an LP outside the band
+        is solved as under ``autoscale=True``, every other one on the reference's arithmetic, bit for bit and whatever else
+        is in the batch.  The flag goes with every launch -- ``solve_device`` and the hsd='auto' re-solves included -- and
+        ``solve(lp)`` needs no band test: the host pipeline runs once, without the speculative pass of "auto".
         ``predcorr=True`` (PYCLLP_FLAG_PREDCORR, not in the reference's kernel): Mehrotra's predictor-corrector step on the same
         Gram / LDL' machinery -- one factorisation and two solves per iteration, the same optimum in ~27 % fewer iterations at
         the reference's step fraction r = 0.9 and ~45 % fewer at r = 0.99; the default stays the reference's rule.  With the
