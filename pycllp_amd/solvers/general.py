@@ -16,8 +16,9 @@ On the native path the batch is converted ON THE DEVICE (``DeviceConversion``: `
 (``GeneralLP.bounded_structure``), ``solve(lp)`` uploads a, b, c, l, u and downloads results of the original size, and
 ``solve_device`` is the same chain on tensors, in the ORIGINAL variables.  Batches with per-problem values of A
 (``PerProblemBounded``, the mix-in of ``general_batch`` and ``sparse_general_batch``) go the same way through
-``BatchDeviceConversion`` (``pycllp_hip_general_to_bounded_batch``, csrc/general_form_pa.hip), which also writes every LP's
-matrix in the layout its solve entry takes; there the chain on tensors is ``solve_device_general``.
+``BatchDeviceConversion`` (``pycllp_hip_general_to_bounded_batch``, the same unit), which also writes every LP's matrix in the
+layout its solve entry takes; there the chain on tensors is ``solve_device_general``.  Both go through one text,
+``_solve_on_device`` and ``_solve_native`` of the shared-A plugin; a plugin states how it launches (``_launch_converted``).
 """
 import contextlib
 import ctypes
@@ -71,6 +72,7 @@ class DeviceConversion(object):
     """The plan of ``GeneralLP.bounded_structure()`` on ``device`` -- the row map and the CSR of the ORIGINAL shared A, terms in
     the order of its coordinate lists -- and the two entries that work by it.  The calls take contiguous float64 CUDA tensors
     and the stream to queue on (None: torch's current stream on ``device``); nothing is synchronised."""
+    per_problem = False       # to_bounded takes no Adata in front of a
 
     def __init__(self, glp, keep, sign, device):
         self.m, self.n, self.mk, self.device = glp.nrows, glp.ncols, len(keep), device
@@ -85,15 +87,20 @@ class DeviceConversion(object):
         with torch.cuda.device(self.device):
             _native.check(getattr(_native.lib(), name)(*sizes, *args, st), name)
 
-    def to_bounded(self, stream, a, b, c, l, u, f=None):
+    def _matrix(self, Adata, new, B):
+        """(the entry that converts, its matrix arguments between ``nnz`` and ``a``, its matrix outputs in front of b^ by key)."""
+        return "pycllp_hip_general_to_bounded", (self.data, self.indptr, self.indices), {}
+
+    def to_bounded(self, stream, a, b, c, l, u, f=None, Adata=None):
         """a, b [B, m], c, l, u [B, n], f [B] (l, f: None = 0) -> dict b [B, m'], c, u [B, N], f [B], invalid [B] (i32)."""
         B, N = int(a.shape[0]), self.n + self.mk
         new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)     # noqa: E731
-        cv = dict(b=new(B, self.mk), c=new(B, N), u=new(B, N), f=new(B), invalid=torch.empty(B, dtype=torch.int32, device=self.device))
+        entry, matrix, outputs = self._matrix(Adata, new, B)
+        cv = dict(outputs, b=new(B, self.mk), c=new(B, N), u=new(B, N), f=new(B),
+                  invalid=torch.empty(B, dtype=torch.int32, device=self.device))
         if B:
-            self._call("pycllp_hip_general_to_bounded", stream, (self.m, self.n, self.mk, B),
-                       (self.rowmap, self.nnz, self.data, self.indptr, self.indices, a, b, c, l, u, f,
-                        cv["b"], cv["c"], cv["u"], cv["f"], cv["invalid"]))
+            self._call(entry, stream, (self.m, self.n, self.mk, B),
+                       (self.rowmap, self.nnz, *matrix, a, b, c, l, u, f, *cv.values()))     # (cv: in the entries' order)
         return cv
 
     def from_bounded(self, stream, l, f, invalid, out):
@@ -115,6 +122,7 @@ class BatchDeviceConversion(DeviceConversion):
     terms in the coordinate lists (``SparseMatrix.term_order``) and the gather plan ``gather`` of one LP's matrix output
     (``lp.bounded_gather_dense`` / ``lp.bounded_gather_csr``) on ``device``; ``to_bounded`` takes the values ``[B, nnz]`` in the
     order of the coordinate lists, as ``glp.A.data`` holds them."""
+    per_problem = True
 
     def __init__(self, glp, keep, sign, device, gather):
         super(BatchDeviceConversion, self).__init__(glp, keep, sign, device)
@@ -123,18 +131,14 @@ class BatchDeviceConversion(DeviceConversion):
         self.order = torch.as_tensor(glp.A.term_order().astype(np.int32), device=device)
         self.gather = torch.as_tensor(np.ascontiguousarray(gather, dtype=np.int32), device=device)
 
+    def _matrix(self, Adata, new, B):
+        return ("pycllp_hip_general_to_bounded_batch",
+                (self.order, self.indptr, self.indices, Adata, ctypes.c_long(self.out_len), self.gather), dict(A=new(B, self.out_len)))
+
     def to_bounded(self, stream, Adata, a, b, c, l, u, f=None):
         """Adata [B, nnz], a, b [B, m], c, l, u [B, n], f [B] (l, f: None = 0) -> dict A [B, out_len], b [B, m'], c, u [B, N],
         f [B], invalid [B] (i32)."""
-        B, N = int(a.shape[0]), self.n + self.mk
-        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)     # noqa: E731
-        cv = dict(A=new(B, self.out_len), b=new(B, self.mk), c=new(B, N), u=new(B, N), f=new(B),
-                  invalid=torch.empty(B, dtype=torch.int32, device=self.device))
-        if B:
-            self._call("pycllp_hip_general_to_bounded_batch", stream, (self.m, self.n, self.mk, B),
-                       (self.rowmap, self.nnz, self.order, self.indptr, self.indices, Adata, ctypes.c_long(self.out_len),
-                        self.gather, a, b, c, l, u, f, cv["A"], cv["b"], cv["c"], cv["u"], cv["f"], cv["invalid"]))
-        return cv
+        return super(BatchDeviceConversion, self).to_bounded(stream, a, b, c, l, u, f, Adata)
 
 
 class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
@@ -219,23 +223,39 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
         if self._handle is None or self._conv is None:
             raise RuntimeError("solve_device() needs init() on an LP the %s kernel serves (after init() the LP takes the "
                                "expansion)" % self._native_kernel)
+        return self._solve_on_device(None, a, b, c, l, u, f, options)
+
+    def _solve_on_device(self, Adata, a, b, c, l, u, f, options):
+        """The device-resident chain of ``solve_device`` (``Adata`` None) and ``solve_device_general``: upload what is numpy,
+        check the shapes against the conversion's plan, convert, launch (``_launch_converted``), convert back; the inputs and
+        everything between stay alive until the next call."""
         cv = self._conv
         with self._on_stream():
+            mat = () if Adata is None else (self._dev(Adata),)
             a, b, c, u = (self._dev(v) for v in (a, b, c, u))
             l, f = (None if v is None else self._dev(v) for v in (l, f))
             B = int(a.shape[0]) if a.dim() == 2 else -1
-            if (tuple(a.shape) != (B, cv.m) or tuple(b.shape) != (B, cv.m) or any(tuple(v.shape) != (B, cv.n) for v in (c, u))
-                    or (l is not None and tuple(l.shape) != (B, cv.n)) or (f is not None and tuple(f.shape) != (B,))):
-                raise ValueError("a and b must be [B,%d], c, l and u [B,%d] and f [B] with equal B" % (cv.m, cv.n))
-            o = solve_opts(self.options, 0, **options)
-            bl = cv.to_bounded(self.stream, a, b, c, l, u, f)
-            out = bounded_outputs(B, cv.mk, cv.n + cv.mk, self.device)
-            if B:
-                self._handle.solve_bounded(self.stream, bl["b"], bl["c"], bl["u"], out, o)
+            if (any(tuple(v.shape) != (B, cv.nnz) for v in mat) or tuple(a.shape) != (B, cv.m) or tuple(b.shape) != (B, cv.m)
+                    or any(tuple(v.shape) != (B, cv.n) for v in (c, u)) or (l is not None and tuple(l.shape) != (B, cv.n))
+                    or (f is not None and tuple(f.shape) != (B,))):
+                raise ValueError(("Adata must be [B,%d], a and b " % cv.nnz if mat else "a and b must be ")
+                                 + "[B,%d], c, l and u [B,%d] and f [B] with equal B" % (cv.m, cv.n))
+            bl = cv.to_bounded(self.stream, *mat, a, b, c, l, u, f)
+            out = self._launch_converted(bl, B, 0, options)
             res = cv.from_bounded(self.stream, l, bl["f"], bl["invalid"], out)
-        self._keepalive = (a, b, c, l, u, f, bl, out)
+        self._keepalive = mat + (a, b, c, l, u, f, bl, out)
         self.kernel = self._native_kernel
         return res
+
+    def _launch_converted(self, bl, B, extra_flags, overrides):
+        """The bounded solve of the B LPs that ``to_bounded`` left in ``bl``, queued on the solver's stream -> its outputs
+        (``bounded_outputs``).  ``NotImplementedError`` where the library declines."""
+        cv = self._conv
+        o = solve_opts(self.options, extra_flags, **overrides)
+        out = bounded_outputs(B, cv.mk, cv.n + cv.mk, self.device)
+        if B:
+            self._handle.solve_bounded(self.stream, bl["b"], bl["c"], bl["u"], out, o)
+        return out
 
     def solve(self, lp, verbose=0):
         glp = as_general(lp)
@@ -248,15 +268,19 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
             res = self._solve_native(glp)
         if res is None:
             self.kernel = "expanded"
-            res = self.solve_expanded(glp)
-        else:
-            self.kernel = self._native_kernel
-            if self.hsd == "auto":
-                idx = self._redo(glp, np.flatnonzero(res["status"] != 0))
-                if idx.size:
-                    r2 = self.solve_expanded(subset(glp, idx))
-                    for k in RESULTS:
-                        res[k][idx] = r2[k]
+            return self._finish(glp, self.solve_expanded(glp), redo=False)
+        self.kernel = self._native_kernel
+        return self._finish(glp, res)
+
+    def _finish(self, glp, res, redo=True):
+        """The tail of ``solve``: with ``hsd='auto'`` the LPs of a native solve that did not end optimal are solved again
+        (``_redo`` picks them, ``_solve_again`` solves them), then ``res`` becomes the result attributes."""
+        if redo and self.hsd == "auto":
+            idx = self._redo(glp, np.flatnonzero(res["status"] != 0))
+            r2 = self._solve_again(subset(glp, idx)) if idx.size else None
+            if r2 is not None:
+                for k in RESULTS:
+                    res[k][idx] = r2[k]
         for k in RESULTS:
             setattr(self, k, res[k])
         return self.status
@@ -265,28 +289,32 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
         """The LPs among ``idx`` (not optimal on the native kernel) that ``hsd='auto'`` solves again through the expansion."""
         return idx
 
+    def _solve_again(self, glp):
+        """``solve_expanded`` for the LPs that ``hsd='auto'`` solves again; None: the kernel's status stands."""
+        return self.solve_expanded(glp)
+
     def launch_info(self):
         """``Handle.launch_info()`` of the native kernel's last launch (None when no handle serves the LP)."""
         return None if self._handle is None else self._handle.launch_info()
 
     def _solve_native(self, glp):
-        """One upload of a, b, c, l, u; conversion, bounded kernel and back-conversion on the device; one download of the results
-        in the GeneralLP's variables.  None if the library declines A^ (PYCLLP_E_UNSUPPORTED).  ``autoscale='auto'`` is decided
-        from the device's b^, c^, u^ (``autoscale_wanted``: a comparison of maxima, the answer the host's arrays give); the
-        objectives' offset f + c'l is the host's sum, so every result carries the bits of the host conversion."""
+        """One upload of a, b, c, l, u (and of A.data as it is, where the conversion takes per-problem values); conversion,
+        bounded kernel and back-conversion on the device; one download of the results in the GeneralLP's variables.  None if the
+        library declines A^ or the handle (PYCLLP_E_UNSUPPORTED).  ``autoscale='auto'`` is decided from the device's b^, c^, u^
+        (``autoscale_wanted``: a comparison of maxima, the answer the host's arrays give); the objectives' offset f + c'l is the
+        host's sum, so every result carries the bits of the host conversion."""
         cv, B = self._conv, glp.nproblems
         offset = np.broadcast_to(glp.f, (B,)) + (glp.c * glp.l).sum(axis=1)
+        host = ((glp.A.data,) if cv.per_problem else ()) + (glp.a, glp.b, glp.c, glp.l, glp.u, offset)
         with self._on_stream():
-            a, b, c, l, u, fh = (self._dev(np.ascontiguousarray(v)) for v in (glp.a, glp.b, glp.c, glp.l, glp.u, offset))
-            bl = cv.to_bounded(self.stream, a, b, c, l, u)
+            *args, fh = (self._dev(np.ascontiguousarray(v)) for v in host)
+            bl = cv.to_bounded(self.stream, *args)
             wanted = self.autoscale == "auto" and autoscale_wanted(bl["b"], bl["c"], bl["u"])
-            o = solve_opts(self.options, _native.FLAG_AUTOSCALE if wanted else 0)
-            out = bounded_outputs(B, cv.mk, cv.n + cv.mk, self.device)
             try:
-                self._handle.solve_bounded(self.stream, bl["b"], bl["c"], bl["u"], out, o)
+                out = self._launch_converted(bl, B, _native.FLAG_AUTOSCALE if wanted else 0, {})
             except NotImplementedError:
                 return None
-            res = cv.from_bounded(self.stream, l, fh, bl["invalid"], out)
+            res = cv.from_bounded(self.stream, args[-2], fh, bl["invalid"], out)      # (args[-2]: l)
             torch.cuda.synchronize(self.device)
             return {k: res[k].cpu().numpy() for k in RESULTS}
 
@@ -453,21 +481,10 @@ class PerProblemBounded(object):
         for this call."""
         if self._handle is None or self._conv is None:
             raise RuntimeError("solve_device_general() needs init() on an LP the %s" % self._needs)
-        cv = self._conv
-        with self._on_stream():
-            Adata, a, b, c, u = (self._dev(v) for v in (Adata, a, b, c, u))
-            l, f = (None if v is None else self._dev(v) for v in (l, f))
-            B = int(a.shape[0]) if a.dim() == 2 else -1
-            if (tuple(Adata.shape) != (B, cv.nnz) or tuple(a.shape) != (B, cv.m) or tuple(b.shape) != (B, cv.m)
-                    or any(tuple(v.shape) != (B, cv.n) for v in (c, u)) or (l is not None and tuple(l.shape) != (B, cv.n))
-                    or (f is not None and tuple(f.shape) != (B,))):
-                raise ValueError("Adata must be [B,%d], a and b [B,%d], c, l and u [B,%d] and f [B] with equal B"
-                                 % (cv.nnz, cv.m, cv.n))
-            bl = cv.to_bounded(self.stream, Adata, a, b, c, l, u, f)
-            out = self._launch(bl["A"].view(self._values_spec(B)[0]), bl["b"], bl["c"], bl["u"], 0, options)
-            res = cv.from_bounded(self.stream, l, bl["f"], bl["invalid"], out)
-        self._keepalive = (Adata, a, b, c, l, u, f, bl, out)
-        return res
+        return self._solve_on_device(Adata, a, b, c, l, u, f, options)
+
+    def _launch_converted(self, bl, B, extra_flags, overrides):
+        return self._launch(bl["A"].view(self._values_spec(B)[0]), bl["b"], bl["c"], bl["u"], extra_flags, overrides)
 
     def _launch(self, A, b, c, u, extra_flags, overrides):
         B, mk, N = int(b.shape[0]), self.mk, self.n + self.mk
@@ -491,10 +508,6 @@ class PerProblemBounded(object):
         self._delegate.solve(glp, verbose=verbose)
         self.kernel = self._delegate.kernel
 
-    def _solve_again(self, glp):
-        """``solve_expanded`` for the LPs that ``hsd='auto'`` solves again; None: the kernel's status stands."""
-        return self.solve_expanded(glp)
-
     def solve(self, lp, verbose=0):
         if self._delegate is None and self._handle is None:
             raise RuntimeError("solve() called before init()")
@@ -508,49 +521,18 @@ class PerProblemBounded(object):
                 raise ValueError("the bounded form changed since init(): " + self._changed_what
                                  % (form.nrows, self.mk, glp.A.nproblems))
             if self._ensure_conversion(glp, keep, sign) is not None:
-                res = self._solve_converted(glp)
+                res = self._solve_native(glp)
             else:
                 res = self._solve_bounded(*glp.to_bounded_equality_form())
             if res is None:                     # the entry answers PYCLLP_E_UNSUPPORTED
                 self._make_delegate(glp)
         if res is None:
             self._solve_delegate(glp, verbose)
-            for k in RESULTS:
-                setattr(self, k, getattr(self._delegate, k))
-            return self.status
-        if self.hsd == "auto":
-            idx = self._redo(glp, np.flatnonzero(res["status"] != 0))
-            r2 = self._solve_again(subset(glp, idx)) if idx.size else None
-            if r2 is not None:
-                for k in RESULTS:
-                    res[k][idx] = r2[k]
-        for k in RESULTS:
-            setattr(self, k, res[k])
-        return self.status
-
-    def _solve_converted(self, glp):
-        """One upload of A.data, a, b, c, l, u as they are; conversion, bounded kernel and back-conversion on the device; one
-        download of the results in the GeneralLP's variables.  None if the entry declines the handle (PYCLLP_E_UNSUPPORTED).
-        ``autoscale='auto'`` is decided from the device's b^, c^, u^ and the objectives' offset f + c'l is the host's sum, as in
-        ``HipGeneralPrimalNormalSolver._solve_native``: every result carries the bits of the host conversion."""
-        cv, B = self._conv, glp.nproblems
-        offset = np.broadcast_to(glp.f, (B,)) + (glp.c * glp.l).sum(axis=1)
-        with self._on_stream():
-            Adata, a, b, c, l, u, fh = (self._dev(np.ascontiguousarray(v))
-                                        for v in (glp.A.data, glp.a, glp.b, glp.c, glp.l, glp.u, offset))
-            bl = cv.to_bounded(self.stream, Adata, a, b, c, l, u)
-            wanted = self.autoscale == "auto" and autoscale_wanted(bl["b"], bl["c"], bl["u"])
-            try:
-                out = self._launch(bl["A"].view(self._values_spec(B)[0]), bl["b"], bl["c"], bl["u"],
-                                   _native.FLAG_AUTOSCALE if wanted else 0, {})
-            except NotImplementedError:
-                return None
-            res = cv.from_bounded(self.stream, l, fh, bl["invalid"], out)
-            torch.cuda.synchronize(self.device)
-            return {k: res[k].cpu().numpy() for k in RESULTS}
+            return self._finish(glp, {k: getattr(self._delegate, k) for k in RESULTS}, redo=False)
+        return self._finish(glp, res)
 
     def _solve_bounded(self, blp, bmap):
-        """The same with the conversion on the host (a structure without a gather plan): one upload, one launch, one download;
+        """``_solve_native`` with the conversion on the host (a structure without a gather plan): one upload, one launch, one download;
         None if the entry declines the handle (PYCLLP_E_UNSUPPORTED)."""
         wanted = self.autoscale == "auto" and autoscale_wanted(blp.b, blp.c, blp.u)
         A, b, c, u = (self._dev(np.ascontiguousarray(v)) for v in (self._values(blp), blp.b, blp.c, blp.u))

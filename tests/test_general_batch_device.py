@@ -13,21 +13,15 @@ import torch
 import footprint as fp
 import general_batch_cases as gbc
 import sparse_general_batch_cases as sgbc
+from general_device_cases import (DEV, KINDS5, RESULTS, P, assert_same_results, dev, fake_solution, fh_bound, frozen,
+                                  same_bits)
 from pycllp_amd import _native
 from pycllp_amd.lp import (GATHER_ONE, GeneralLP, SparseMatrix, bounded_gather_csr, bounded_gather_dense, bounded_rowmap)
 from test_general_solver import make_general
 
 ENTRY = "pycllp_hip_general_to_bounded_batch"
-KINDS5 = ["le", "eq", "rng", "ge", "free"]            # every kind of row: '+' rows, a '-' row, a dropped row
-CHUNK = 256                                           # kChunk of csrc/general_form_pa.hip: terms of an LP staged in LDS at a time
-TILE_BYTES = 32 * 1024                                # kTileBytes there
-RESULTS = ("x", "y", "z", "s", "status", "iters", "primal_obj", "dual_obj")
-
-
-def frozen(glp):
-    for v in (glp.a, glp.b, glp.c, glp.l, glp.u, glp.f, glp.A.data):
-        v.setflags(write=False)
-    return glp
+CHUNK = 256                                           # kChunk of csrc/general_form.hip: terms of an LP staged in LDS at a time
+TILE_BYTES = 32 * 1024                                # kBatchTileBytes there
 
 
 def shuffled(glp, seed):
@@ -61,7 +55,7 @@ def case(name):
 
 
 def tile_lps(glp):
-    """G of csrc/general_form_pa.hip: the LPs of one workgroup's tile."""
+    """G of the batch kernel of csrc/general_form.hip: the LPs of one workgroup's tile."""
     per_lp = 8 * ((glp.ncols | 1) + 3 * (glp.nrows | 1) + (min(glp.A.nnzeros, CHUNK) | 1))
     return min(64, TILE_BYTES // per_lp, glp.nproblems)
 
@@ -94,14 +88,6 @@ def gathered(plan, data):
     g = plan.astype(np.int64)
     v = data[:, np.clip(np.abs(g) - 1, 0, max(data.shape[1] - 1, 0))]
     return np.where(g == GATHER_ONE, 1.0, np.where(g == 0, 0.0, np.where(g > 0, v, -v)))
-
-
-def bits(v):
-    return np.ascontiguousarray(v, dtype=np.float64).view(np.int64)
-
-
-def same_bits(got, want, what):
-    assert got.shape == want.shape and np.array_equal(bits(got), bits(want)), what
 
 
 # ---- CPU -----------------------------------------------------------------------------------------------------------------------
@@ -141,7 +127,6 @@ def test_duplicate_entries_have_no_dense_plan():
     assert s._ensure_conversion(glp, keep, sign) is None and s.conversion == "host"
 
 
-P = ctypes.c_void_p(8)         # a fake non-NULL device pointer: every check comes before any HIP call
 ARRAYS = ("rowmap", "nnz", "Aorder", "Aindptr", "Aindices", "Avals", "out_len", "gather", "a", "b", "c", "l", "u", "f",
           "Ah", "bh", "ch", "uh", "fh", "invalid")
 REQUIRED = tuple(k for k in ARRAYS if k not in ("nnz", "out_len", "l", "f"))
@@ -175,34 +160,10 @@ def test_symbol_is_declared_and_exported():
 
 
 # ---- GPU: the conversion ---------------------------------------------------------------------------------------------------------
-DEV = "cuda:0"
-
-
 def conversion(glp, kind):
     from pycllp_amd.solvers.general import BatchDeviceConversion
     plan, keep, sign = plan_of(glp, kind)
     return BatchDeviceConversion(glp, keep, sign, torch.device(DEV), plan)
-
-
-def dev(v):
-    return None if v is None else torch.as_tensor(np.ascontiguousarray(v), device=DEV)
-
-
-def fh_bound(glp):
-    """2 (n + 1) 2^-53 sum |c_j l_j|: the rounding bound of a dot product of n terms, for two orders of summation."""
-    return 2 * (glp.ncols + 1) * 2.0 ** -53 * np.abs(glp.c * glp.l).sum(axis=1)
-
-
-def fake_solution(blp, seed):
-    """Arrays with the shapes of a bounded solve's outputs (the back-conversion does no arithmetic that needs a real one)."""
-    rng = np.random.default_rng(seed)
-    B, mk, N = blp.nproblems, blp.nrows, blp.ncols
-    r = dict(x=rng.uniform(0, 2, (B, N)), y=rng.uniform(-1, 1, (B, mk)), z=rng.uniform(0, 1, (B, N)), s=rng.uniform(0, 1, (B, N)),
-             pobj=rng.uniform(-5, 5, B), dobj=rng.uniform(-5, 5, B), status=rng.integers(0, 6, B).astype(np.int32),
-             iters=rng.integers(1, 200, B).astype(np.int32))
-    r["x"][:, ::3] = 0.0
-    r["y"][:, ::2] *= 0.0                                           # signed zeros among them
-    return r
 
 
 @pytest.mark.gpu
@@ -361,15 +322,6 @@ def parent_arithmetic(plugin, glp, init_lp=None):
     r = {k: v.cpu().numpy() for k, v in out.items()}
     x, y, z, sl = bmap.general(r["x"], r["y"], r["z"], r["s"])
     return dict(x=x, y=y, z=z, s=sl, status=r["status"], iters=r["iters"], primal_obj=r["pobj"] + blp.f, dual_obj=r["dobj"] + blp.f)
-
-
-def assert_same_results(got, want, keys):
-    for k in keys:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        if g.dtype == np.float64:
-            same_bits(g, w, k)
-        else:
-            assert np.array_equal(g, w), k
 
 
 @pytest.mark.gpu

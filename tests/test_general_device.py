@@ -11,19 +11,14 @@ import pytest
 import torch
 
 import footprint as fp
+from general_device_cases import (DEV, KINDS5, RESULTS, P, assert_same_results, dev, fake_solution, fh_bound, frozen,
+                                  same_bits)
 from pycllp_amd import _native
 from pycllp_amd.lp import GeneralLP, SparseMatrix, bounded_rowmap
 from test_general_solver import check_kkt, make_general
 from test_sparse_general_solver import make_sparse_general
 
 TO, FROM = "pycllp_hip_general_to_bounded", "pycllp_hip_general_from_bounded"
-KINDS5 = ["le", "eq", "rng", "ge", "free"]            # every kind of row
-
-
-def frozen(glp):
-    for v in (glp.a, glp.b, glp.c, glp.l, glp.u, glp.f, glp.A.data):
-        v.setflags(write=False)
-    return glp
 
 
 @functools.lru_cache(maxsize=None)
@@ -41,14 +36,6 @@ def case(name):
         g = make_general(5, 7, 3, seed=405, mixed_u=True, kinds=KINDS5, fixed=2)
         return frozen(GeneralLP(g.A, g.b, g.c, a=g.a, l=np.zeros_like(g.l), u=g.u - g.l, f=g.f))
     raise KeyError(name)
-
-
-def bits(v):
-    return np.ascontiguousarray(v, dtype=np.float64).view(np.int64)
-
-
-def same_bits(got, want, what):
-    assert got.shape == want.shape and np.array_equal(bits(got), bits(want)), what
 
 
 # ---- CPU -----------------------------------------------------------------------------------------------------------------------
@@ -85,7 +72,6 @@ def test_bounded_structure_raises_the_mixed_row_error():
     assert str(e1.value) == str(e2.value) and "Can not keep row 0" in str(e1.value)
 
 
-P = ctypes.c_void_p(8)         # a fake non-NULL device pointer: every check comes before any HIP call
 TO_ARRAYS = ("rowmap", "nnz", "Adata", "Aindptr", "Aindices", "a", "b", "c", "l", "u", "f", "bh", "ch", "uh", "fh", "invalid")
 FROM_ARRAYS = ("rowmap", "l", "fh", "invalid", "xh", "yh", "zh", "sh", "x", "y", "z", "s", "pobj", "dobj", "status", "iters")
 REQUIRED = {TO: ("rowmap", "Adata", "Aindptr", "Aindices", "a", "b", "c", "u", "bh", "ch", "uh", "fh", "invalid"),
@@ -120,34 +106,10 @@ def test_entries_refuse_bad_arguments_without_gpu(entry):
 
 
 # ---- GPU: the conversion ---------------------------------------------------------------------------------------------------------
-DEV = "cuda:0"
-
-
 def conversion(glp):
     from pycllp_amd.solvers.general import DeviceConversion
     Ah, keep, sign = glp.bounded_structure()
     return DeviceConversion(glp, keep, sign, torch.device(DEV))
-
-
-def dev(v):
-    return None if v is None else torch.as_tensor(np.ascontiguousarray(v), device=DEV)
-
-
-def fh_bound(glp):
-    """2 (n + 1) 2^-53 sum |c_j l_j|: the rounding bound of a dot product of n terms, for two orders of summation."""
-    return 2 * (glp.ncols + 1) * 2.0 ** -53 * np.abs(glp.c * glp.l).sum(axis=1)
-
-
-def fake_solution(blp, seed):
-    """Arrays with the shapes of a bounded solve's outputs (the back-conversion does no arithmetic that needs a real one)."""
-    rng = np.random.default_rng(seed)
-    B, mk, N = blp.nproblems, blp.nrows, blp.ncols
-    r = dict(x=rng.uniform(0, 2, (B, N)), y=rng.uniform(-1, 1, (B, mk)), z=rng.uniform(0, 1, (B, N)), s=rng.uniform(0, 1, (B, N)),
-             pobj=rng.uniform(-5, 5, B), dobj=rng.uniform(-5, 5, B), status=rng.integers(0, 6, B).astype(np.int32),
-             iters=rng.integers(1, 200, B).astype(np.int32))
-    r["x"][:, ::3] = 0.0
-    r["y"][:, ::2] *= 0.0                                           # signed zeros among them
-    return r
 
 
 @pytest.mark.gpu
@@ -295,9 +257,6 @@ def test_invalid_lps_get_their_code_a_harmless_lp_and_nan_results():
 
 
 # ---- GPU: the plugins ------------------------------------------------------------------------------------------------------------
-RESULTS = ("x", "y", "z", "s", "status", "iters", "primal_obj", "dual_obj")
-
-
 def row_scaled(g, scale):
     """The LPs of ``g`` with row i of A and its bounds times scale[i] (> 0): the same feasible set."""
     A = g.A.todense() * scale[:, None]
@@ -343,15 +302,6 @@ def parent_arithmetic(plugin_class, glp):
     r = {k: v.cpu().numpy() for k, v in out.items()}
     x, y, z, s = bmap.general(r["x"], r["y"], r["z"], r["s"])
     return dict(x=x, y=y, z=z, s=s, status=r["status"], iters=r["iters"], primal_obj=r["pobj"] + blp.f, dual_obj=r["dobj"] + blp.f)
-
-
-def assert_same_results(got, want, keys):
-    for k in keys:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        if g.dtype == np.float64:
-            same_bits(g, w, k)
-        else:
-            assert np.array_equal(g, w), k
 
 
 @pytest.mark.gpu
