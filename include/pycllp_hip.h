@@ -26,6 +26,8 @@
  * non-zeros on).  An LP whose LDL' would need the Nocedal-Wright guard there -- every LP with PYCLLP_FLAG_FORCE_GUARD_PATH --
  * has no guarded kernel to go to: it ends PYCLLP_STATUS_NUMERICAL and its status is ALL that is written; its x, y, z, pobj,
  * dobj and iters keep what the caller's arrays held.  Read them only where status != PYCLLP_STATUS_NUMERICAL on that entry.
+ * The same holds for pycllp_hip_dense_solve_batch beyond the lane-group kernels (m > 32 or n > 128: the wavefront-per-LP
+ * kernel with a dense image per wave), for the same reason.
  * A call that returns a negative PYCLLP_E_* code has written nothing.  tests/test_memory_footprint.py pins all of this.
  * Return value: 0 on success, a negative PYCLLP_E_* code for argument errors, or a positive
  * hipError_t for runtime failures (pycllp_hip_last_error() gives the text).
@@ -205,10 +207,20 @@ int pycllp_hip_dense_solve_bounded(pycllp_hip_dense *handle, long B, const doubl
  * The other arguments, the status codes and the outputs as pycllp_hip_dense_solve, except that at the iteration limit pobj
  * and dobj are those of the x, y returned (as pycllp_hip_dense_solve_bounded).
  * Options: PYCLLP_FLAG_AUTOSCALE, PYCLLP_FLAG_FORCE_GUARD_PATH and PYCLLP_FLAG_NO_SLACK_PATH apply.
+ * Beyond the lane-group kernels (m > 32 or n > 128), up to m = 128 and n = 256: the wavefront-per-LP kernel with a dense
+ * image PER WAVE (one LP per wavefront; the wave copies its LP's m x a_cols matrix from A_dev into its own LDS area when it
+ * takes the LP).  The image counts against the LDS, so the range ends where not even one wave fits 160 KB: e.g. (128, 256)
+ * with an identity tail runs (1 wave per workgroup), (64, 128) without one runs, (80, 256) without one and (113, 257) do
+ * not.  At the iteration limit pobj and dobj are, as with pycllp_hip_dense_solve, those of the iterate before the last step.
+ * PYCLLP_FLAG_AUTOSCALE and _AUTOSCALE_PER_LP apply; an LP whose factorisation would have needed the Nocedal-Wright
+ * guard -- every LP under PYCLLP_FLAG_FORCE_GUARD_PATH -- ends PYCLLP_STATUS_NUMERICAL with status its only output.
+ * pycllp_hip_dense_launch_info / _variant_info / _kernel_kind report the launch as a wave kernel on a dense image: (MB, NQ),
+ * block = 64 x waves per workgroup, the plan's LDS bytes.
  * Returns PYCLLP_E_BADARG for any of the flags HSD, PREDCORR, WARM_START, WAVE_KERNEL or an a_cols other than the above, and
- * PYCLLP_E_UNSUPPORTED for a handle beyond the lane-group kernels (m > 32 or n > 128: use pycllp_hip_sparse_solve_batch);
- * all before any HIP call.  Uses the handle's launch-queue ring; pycllp_hip_dense_launch_info / _variant_info report the
- * launch as they do for the other lane-group kernels.  Asynchronous on `stream`. */
+ * PYCLLP_E_UNSUPPORTED for a handle beyond both ranges (m > 128, n > 256, or a shape whose image leaves no room for a wave:
+ * use pycllp_hip_sparse_solve_batch); all before any HIP call.  Uses the handle's launch-queue ring;
+ * pycllp_hip_dense_launch_info / _variant_info report the launch as they do for the other lane-group kernels.  Asynchronous
+ * on `stream`. */
 int pycllp_hip_dense_solve_batch(pycllp_hip_dense *handle, long B, const double *A_dev, long a_cols,
                                  const double *b_dev, const double *c_dev, double *x_dev, double *y_dev, double *z_dev,
                                  double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,

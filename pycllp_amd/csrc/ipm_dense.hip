@@ -733,6 +733,9 @@ struct pycllp_hip_sparse {
     bool wreg_bd_tried = false;   // pycllp_hip_sparse_solve_bounded (under info_mu)
     WregPlan* wreg_bdpa = nullptr;   // the plan of the bounded wave kernel on per-problem values (structure tables; the LP's values, t
     bool wreg_bdpa_tried = false;    // and s behind every wave area), built by the first pycllp_hip_sparse_solve_batch_bounded
+    WregPlan* wreg_dapa[2] = {nullptr, nullptr};   // the plans of the wave kernel on per-problem DENSE matrices (an image per wave): [0] with the
+    bool wreg_dapa_tried[2] = {false, false};      // identity tail implied, [1] with every column in the image (PYCLLP_FLAG_NO_SLACK_PATH); built by the
+                                                   // first pycllp_hip_dense_solve_batch on a handle beyond the lane-group kernels
     int max_lds = 0;
     std::vector<double> host_val; std::vector<int> host_ptr, host_col;   // host CSR copy (what a PA plan is built from)
 };
@@ -995,6 +998,10 @@ static int dense_solve_batch_impl(const char* entry, pycllp_hip_dense* h, long B
     return 0;
 }
 
+static int dense_solve_batch_wave(pycllp_hip_dense* hd, long B, const double* A_dev, long a_cols, const double* b_dev,
+                                  const double* c_dev, double* x_dev, double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev,
+                                  int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream);
+
 int pycllp_hip_dense_solve_batch(pycllp_hip_dense* h, long B, const double* A_dev, long a_cols, const double* b_dev,
                                  const double* c_dev, double* x_dev, double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev,
                                  int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
@@ -1002,9 +1009,9 @@ int pycllp_hip_dense_solve_batch(pycllp_hip_dense* h, long B, const double* A_de
                                     "HSD, PREDCORR, WARM_START and WAVE_KERNEL are not available with per-problem matrices",
                                     A_dev && b_dev && c_dev && x_dev && status_dev);
     if (rc != 0) return rc;
-    if (h->sp)
-        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch: per-problem dense matrices stop at m = 32, n = 128 "
-                                             "(beyond: pycllp_hip_sparse_solve_batch)");
+    if (h->sp)      // beyond the lane-group kernels: the wave kernel with an image per wave, where a variant and an LDS plan cover the LP
+        return dense_solve_batch_wave(h, B, A_dev, a_cols, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev,
+                                      iters_dev, opts, stream);
     const bool sl = h->variant_sl >= 0 && !((opts ? opts->flags : 0) & PYCLLP_FLAG_NO_SLACK_PATH);
     return dense_solve_batch_impl("pycllp_hip_dense_solve_batch", h, B, sl, A_dev, a_cols, b_dev, c_dev, nullptr, x_dev, y_dev,
                                   z_dev, nullptr, pobj_dev, dobj_dev, status_dev, iters_dev, opts, stream);
@@ -1248,6 +1255,52 @@ int pycllp_hip_sparse_init(int m, int n, int nnz, const double* Adata_dev, const
 __global__ void deferred_to_numerical_kernel(const int* __restrict__ worklist, int* __restrict__ status) {
     const int n = worklist[0];
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) status[worklist[1 + i]] = PYCLLP_STATUS_NUMERICAL;
+}
+
+// The body of pycllp_hip_dense_solve_batch for a handle beyond the lane-group kernels, behind its argument checks: the wave
+// kernel on per-problem dense matrices (ipm_wreg_dapa.hip), on the plan for the implied identity tail or, with
+// PYCLLP_FLAG_NO_SLACK_PATH, the one with every column in the image -- each built on first use.  Where no variant or LDS plan
+// covers the LP (every handle of the large-LP kernel included) the entry declines as it always did.  An LP the kernel defers
+// (the guard would have bitten; every LP under PYCLLP_FLAG_FORCE_GUARD_PATH) ends PYCLLP_STATUS_NUMERICAL with status its only
+// output: the block kernel reads per-problem values in CSR order, which the dense [m, a_cols] layout is not.
+static int dense_solve_batch_wave(pycllp_hip_dense* hd, long B, const double* A_dev, long a_cols, const double* b_dev,
+                                  const double* c_dev, double* x_dev, double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev,
+                                  int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
+    static const char* const kStops = "pycllp_hip_dense_solve_batch: per-problem dense matrices stop at m = 32, n = 128 "
+                                      "(beyond: pycllp_hip_sparse_solve_batch)";
+    pycllp_hip_sparse* h = hd->sp;
+    if (h->big) return set_err(PYCLLP_E_UNSUPPORTED, kStops);
+    hipStream_t st = (hipStream_t)stream;
+    const int keep = ((opts ? opts->flags : 0) & PYCLLP_FLAG_NO_SLACK_PATH) ? 1 : 0;
+    const int rc = lazy_plan(h, &h->wreg_dapa[keep], &h->wreg_dapa_tried[keep], "wreg_plan_create_dense_pa", [&](WregPlan** wp) {
+        return wreg_plan_create_dense_pa(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(),
+                                         h->host_col.data(), h->max_lds, keep, st, wp);
+    });
+    if (rc != 0) return rc;
+    WregPlan* plan = h->wreg_dapa[keep];
+    if (!plan) return set_err(PYCLLP_E_UNSUPPORTED, kStops);
+    const int nd = wreg_image_cols(plan);
+    if (a_cols != (long)nd) {
+        snprintf(g_err, sizeof(g_err), "%s: a_cols = %ld, expected %d (%s)", "pycllp_hip_dense_solve_batch", a_cols, nd,
+                 nd != h->desc.n ? "the columns before the identity tail" : "every column");
+        return PYCLLP_E_BADARG;
+    }
+    if (B == 0) return 0;
+    DevOpts o = to_dev(opts);
+    int* worklist = nullptr;
+    int grid = 0;
+    HIP_TRY(hipMallocAsync((void**)&worklist, sizeof(int) * (size_t)(B + 1), st));
+    hipError_t e = h->ring.run(st, [&](int* qw) {
+        return wreg_launch_solve(plan, B, A_dev, b_dev, c_dev, x_dev, y_dev, z_dev, pobj_dev, dobj_dev, status_dev, iters_dev, qw,
+                                 worklist, o, h->num_cu, st, &grid);
+    });
+    if (e != hipSuccess) { (void)hipFreeAsync(worklist, st); return set_err((int)e, "ipm_wreg_kernel (per-problem dense A) launch"); }
+    hipLaunchKernelGGL(deferred_to_numerical_kernel, dim3(64), dim3(256), 0, st, worklist, status_dev);
+    e = hipGetLastError();
+    const hipError_t e2 = hipFreeAsync(worklist, st); if (e == hipSuccess) e = e2;
+    record_launch(h, plan, grid);
+    if (e != hipSuccess) return set_err((int)e, "deferred_to_numerical_kernel launch");
+    return 0;
 }
 
 // which kernels of the sparse path implement the predictor-corrector step
@@ -1538,6 +1591,8 @@ void pycllp_hip_sparse_free(pycllp_hip_sparse* h) {
     wreg_plan_free(h->wreg_pa);
     wreg_plan_free(h->wreg_bd);
     wreg_plan_free(h->wreg_bdpa);
+    wreg_plan_free(h->wreg_dapa[0]);
+    wreg_plan_free(h->wreg_dapa[1]);
     big_plan_free(h->big);
     delete h;
 }

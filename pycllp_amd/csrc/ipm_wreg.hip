@@ -1,6 +1,6 @@
 // ipm_wreg.hip -- host side of the register-resident one-LP-per-wavefront kernels (wreg_wave.h): the plan of one constraint
 // matrix (term tables or dense image, LDS layout), the choice of a launcher from the tables of the kernel units
-// (ipm_wreg_{tab,da,pa,pc,pcda,pcpa,bd,bdpa}.hip), grid sizing and the wreg_launch_* entry points of wreg.h.  The only kernels
+// (ipm_wreg_{tab,da,pa,dapa,pc,pcda,pcpa,bd,bdpa}.hip), grid sizing and the wreg_launch_* entry points of wreg.h.  The only kernels
 // compiled here are the two that have no table: the stand-alone LDL' solve and the selftest of the cross-lane primitives.
 #include "wreg_wave.h"
 
@@ -103,6 +103,8 @@ size_t put(std::vector<char>& host, const std::vector<T>& v) {
 
 // the launcher table of a plan's kind; pc: its predictor-corrector kernels (plans of the bounded kernel have none)
 static const WVariants& table_of(bool da, bool pa, bool bd, bool pc = false) {
+    static const WVariants none = { nullptr, 0 };
+    if (da && pa) return (bd || pc) ? none : kWDAPA;      // per-problem dense matrices: the plain kernel only
     if (bd) return pa ? kWBDPA : (da ? kWBDDA : kWBD);
     if (pc) return pa ? kWPCPA : (da ? kWPCDA : kWPC);
     return pa ? kWPA : (da ? kWDA : kWTab);
@@ -119,14 +121,16 @@ static const WVariant* first_covering(const WVariants& t, int m, int n) {
 // hip_dense_primal_normal hands over beyond m = 32.  The last m columns are kept out of the image when they are the
 // identity (equality form of a StandardLP).  Fewer than four waves per workgroup when that is what lets the image fit.
 // bd: the plan of the bounded kernel (its variants; t and s behind every wave area)
+// dpa: the plan of the kernel on per-problem dense matrices (wreg_plan_create_dense_pa: an image per wave, no device copy);
+// keep_tail (dpa only): an identity tail stays in the image
 static int wreg_plan_create_dense(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
-                                  bool bd, hipStream_t st, WregPlan** out) {
-    const WVariant* v = first_covering(table_of(true, false, bd), m, n);
+                                  bool bd, hipStream_t st, WregPlan** out, bool dpa = false, bool keep_tail = false) {
+    const WVariant* v = first_covering(table_of(true, dpa, bd), m, n);
     if (!v) return 1;
     const int MB = v->mb, NQ = v->nq;
     const int MP = 16 * MB;
     // identity tail?
-    bool sl = n > m;
+    bool sl = n > m && !keep_tail;
     std::vector<int> tail_cnt(sl ? m : 0, 0);
     for (int i = 0; i < m && sl; i++)
         for (int e = ptr[i]; e < ptr[i + 1]; e++)
@@ -138,6 +142,21 @@ static int wreg_plan_create_dense(int m, int n, int nnz, const double* val, cons
     memset(&T, 0, sizeof(T));
     T.m = m; T.n = n; T.nnz = nnz; T.nd = nd; T.as = AS; T.img_rows = R;
     T.wave_doubles = stage_d(NQ) + 64 * NQ + 5 * MP + MB * WL + (bd ? 2 * 64 * NQ : 0);
+    if (dpa) {
+        // the image behind every wave area; nothing in front of the waves
+        T.pa = 1;
+        T.wave_doubles += R * AS;
+        int wp = 0;
+        for (int w = 4; w >= 1; w--)
+            if (sizeof(double) * (size_t)w * T.wave_doubles <= (size_t)max_lds) { wp = w; break; }
+        if (!wp) { delete P; return 1; }
+        T.wpb = wp; T.o_img = 0; T.o_wave = 0;
+        T.lds_bytes = (int)(sizeof(double) * (size_t)wp * T.wave_doubles);
+        P->dev_blob = nullptr;
+        P->mb = MB; P->nq = NQ; P->da = true; P->pa = true;
+        *out = P;
+        return 0;
+    }
     const size_t img_bytes = sizeof(double) * (size_t)R * AS;
     int wpb = 0;
     for (int w = 4; w >= 1; w--)
@@ -175,6 +194,11 @@ int wreg_plan_create_bounded(int m, int n, int nnz, const double* val, const int
     const int rc = wreg_plan_create_tables(m, n, nnz, val, ptr, col, max_lds, false, true, st, out);
     if (rc != 1) return rc;
     return wreg_plan_create_dense(m, n, nnz, val, ptr, col, max_lds, true, st, out);
+}
+
+int wreg_plan_create_dense_pa(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
+                              int keep_tail, hipStream_t st, WregPlan** out) {
+    return wreg_plan_create_dense(m, n, nnz, val, ptr, col, max_lds, false, st, out, true, keep_tail != 0);
 }
 
 int wreg_plan_create_bounded_pa(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
@@ -377,6 +401,7 @@ void wreg_plan_free(WregPlan* p) {
 int wreg_lds_bytes(const WregPlan* p) { return p ? p->tab.lds_bytes : 0; }
 int wreg_block_threads(const WregPlan* p) { return p ? 64 * p->tab.wpb : 0; }
 int wreg_variant(const WregPlan* p) { return p ? (p->da ? 2 : 1) : 0; }
+int wreg_image_cols(const WregPlan* p) { return (p && p->da) ? p->tab.nd : 0; }
 void wreg_shape(const WregPlan* p, int* mb, int* nq) {
     if (mb) *mb = p ? p->mb : 0;
     if (nq) *nq = p ? p->nq : 0;
@@ -416,6 +441,7 @@ hipError_t wreg_launch_solve(WregPlan* p, long B, const double* a_batch, const d
         if (!pc) return hipErrorNotSupported;
         fn = pc->solve;
     }
+    if (!fn) return hipErrorNotSupported;      // (a kind without that kernel: per-problem dense matrices have the plain one only)
     return fn(p->tab, B, a_batch, b, c, x, y, z, pobj, dobj, status, iters, qhead, defer, o, grid, st);
 }
 

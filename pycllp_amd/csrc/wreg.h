@@ -5,7 +5,7 @@
 #define PYCLLP_WREG_H
 #include "wave_common.h"
 
-// ---- shared between the host unit (ipm_wreg.hip) and the eight units the wave kernels are compiled in (ipm_wreg_*.hip) ----
+// ---- shared between the host unit (ipm_wreg.hip) and the nine units the wave kernels are compiled in (ipm_wreg_*.hip) ----
 constexpr int MAX_NQ = 8;
 constexpr int META_COFF = MAX_NQ, META_SEG = 2 * MAX_NQ, META_N = META_SEG + 16;
 
@@ -68,6 +68,8 @@ struct WregTab {
     // columns are the identity, column nd + i = e_i, or there are none), as = nd rounded up to 8, + 1
     int nd, as, img_rows, o_img, wpb;
     const double* img;
+    // dense variant on per-problem matrices (DA && PA, pa != 0): no device copy (img null) -- every wavefront keeps the image
+    // of ITS LP behind its wave area (wave_doubles includes img_rows x as) and fills it from a_batch [B, m, nd] per LP
 };
 
 
@@ -87,6 +89,9 @@ typedef hipError_t (*wbpsolve_fn)(const WregTab&, long, const double*, const dou
 // dense image; every table below is derived from one of them.
 #define WREG_TAB_SHAPES(X) X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 6) X(6, 6) X(7, 6) X(8, 4) X(8, 6) X(8, 8)
 #define WREG_DA_SHAPES(X)  X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4) X(8, 6)
+// ... and the dense-image shapes of the kernel on per-problem dense matrices (kWDAPA): the list above without (8, 6), whose
+// instantiation does not stay free of scratch (28 bytes, like the shared-A kernel of that shape) -- DESIGN.md sections 10, 24
+#define WREG_DAPA_SHAPES(X) X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4)
 
 // The launchers of one (MB, NQ) of one kernel kind; a launcher the kind does not have is null.
 struct WVariant { int mb, nq; wsolve_fn solve, solve_hsd; wnewton_fn newton; wbsolve_fn solve_bounded; wbpsolve_fn solve_bounded_pa; };
@@ -96,6 +101,7 @@ struct WVariants { const WVariant* v; int n; };
 extern const WVariants kWTab;      // ipm_wreg_tab.hip:  term tables (plain, HSD, Newton)
 extern const WVariants kWDA;       // ipm_wreg_da.hip:   dense image (plain, HSD, Newton)
 extern const WVariants kWPA;       // ipm_wreg_pa.hip:   per-problem A on structure tables (plain, HSD)
+extern const WVariants kWDAPA;     // ipm_wreg_dapa.hip: per-problem dense A, a dense image per wave (plain)
 extern const WVariants kWPC;       // ipm_wreg_pc.hip:   predictor-corrector kernels of kWTab's kind
 extern const WVariants kWPCDA;     // ipm_wreg_pcda.hip: ... of kWDA's kind
 extern const WVariants kWPCPA;     // ipm_wreg_pcpa.hip: ... of kWPA's kind
@@ -121,12 +127,20 @@ int wreg_plan_create_bounded(int m, int n, int nnz, const double* val, const int
 // no variant covers (m, n), when nnz >= 65535 or when not even one wave fits.  `val` is not read.
 int wreg_plan_create_bounded_pa(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
                                 hipStream_t st, WregPlan** out);
+// The plan of the wave kernel on per-problem DENSE matrices (kWDAPA): the geometry of wreg_plan_create's dense plan (identity
+// tail detection on the CSR arrays given, R, AS, first covering variant) with no device copy of an image -- the image sits
+// behind every wave area (wave_doubles enlarged by img_rows x AS) -- and as many waves per workgroup, 4 down to 1, as max_lds
+// takes.  keep_tail: all n columns go into the image (nd = n) even where the matrix ends in the identity
+// (PYCLLP_FLAG_NO_SLACK_PATH).  Returns 1 when no variant covers (m, n) or not even one wave fits.
+int wreg_plan_create_dense_pa(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
+                              int keep_tail, hipStream_t st, WregPlan** out);
 void wreg_plan_free(WregPlan* p);
 
 // Solve B LPs (same argument meaning as pycllp_hip_sparse_solve).  LPs whose factorisation would have needed the
 // Nocedal-Wright guard are NOT solved: their indices are appended to defer[1..] (defer[0] = count, zeroed here) and
 // their status is left at -1; the caller runs them through the guarded kernel afterwards.
-// a_batch: [B, nnz] values of every LP in the CSR order of the arrays the plan was built from (PA plans only, else null).
+// a_batch: [B, nnz] values of every LP in the CSR order of the arrays the plan was built from (PA plans only, else null); on a
+// plan of wreg_plan_create_dense_pa: the dense matrices [B, m, nd], row-major.
 hipError_t wreg_launch_solve(WregPlan* p, long B, const double* a_batch, const double* b, const double* c, double* x, double* y, double* z,
                              double* pobj, double* dobj, int* status, int* iters, int* qhead, int* defer, DevOpts o,
                              int num_cu, hipStream_t st, int* grid_out);
@@ -151,6 +165,7 @@ hipError_t wreg_launch_ldl_solve(int n, long B, const double* A, const double* r
 int wreg_lds_bytes(const WregPlan* p);
 int wreg_block_threads(const WregPlan* p);   // 64 x waves per workgroup
 int wreg_variant(const WregPlan* p);         // 1 = term tables, 2 = dense image
+int wreg_image_cols(const WregPlan* p);      // the columns of a dense image (nd: n - m with an implied identity tail, else n); 0 on term tables
 void wreg_shape(const WregPlan* p, int* mb, int* nq);   // the plan's (MB, NQ); (0, 0) for a null plan
 int wreg_has_predcorr(const WregPlan* p);   // 1 when the plan's kernels have a PYCLLP_FLAG_PREDCORR variant (every plan of the wave kernel)
 #endif

@@ -41,7 +41,7 @@
 // This file is the per-wave machinery (WReg, the batched LDS reads, newton_solve), the phases the kernels share (next_item,
 // load_lp, store_lp), the launcher template and the launcher table macro.  The kernels
 // on top of it: ipm_wreg_solve.inc, ipm_wreg_hsd.inc, ipm_wreg_newton.inc, ipm_wreg_bounded.inc, compiled by the units
-// ipm_wreg_{tab,da,pa,pc,pcda,pcpa,bd}.hip (one launcher table of wreg.h each); ipm_wreg.hip is the host side.
+// ipm_wreg_{tab,da,pa,dapa,pc,pcda,pcpa,bd}.hip (one launcher table of wreg.h each); ipm_wreg.hip is the host side.
 #ifndef PYCLLP_WREG_WAVE_H
 #define PYCLLP_WREG_WAVE_H
 #include "wreg.h"
@@ -229,7 +229,8 @@ __device__ __forceinline__ void lds_terms3_uu(unsigned aa, unsigned ab, unsigned
 // ---- the per-wave machinery ------------------------------------------------------------------------------------
 template <int MB, int NQ, bool DA = false, bool PA = false>
 struct WReg {
-    static_assert(!(DA && PA), "per-problem values exist on the table variants only");
+    // DA && PA: the dense image belongs to the wave (behind its area, where the table-PA variants keep cvl_()) and holds the
+    // matrix of the LP the wave is working on (load_lp_values); no tables at all
     using G = WGeo<MB>;
     static constexpr int MP = G::MP, MR = G::MR, MPL = G::MPL, NP = 64 * NQ, STAGE_D = stage_d(NQ), TILE_OFF = tile_off(NQ);
 
@@ -260,6 +261,7 @@ struct WReg {
     __device__ __forceinline__ double* rdv_() const { return W0 + STAGE_D + MB * WL + NP + 3 * MP; }      // [MP] 1/D
     __device__ __forceinline__ double* flr_() const { return W0 + STAGE_D + MB * WL + NP + 4 * MP; }      // [MP] per-column pivot floors (HSD)
     __device__ __forceinline__ double* cvl_() const { return W0 + G::WAVE_D(NQ); }                         // PA: [nnzp] this LP's values of A, CSR order
+    __device__ __forceinline__ double* wimg_() const { return W0 + G::WAVE_D(NQ); }                        // DA && PA: [img_rows][AS] this LP's dense image
     mutable int lane, q, c16;
     int m, n, rmax;
     // x and z of the column at position lane + 64 qq where they are parked in the stage (at NP and 2 NP): across factor and
@@ -931,6 +933,17 @@ __device__ __forceinline__ void wreg_carve(WReg<MB, NQ, DA, PA>& w, double* W0, 
 template <int MB, int NQ, bool DA, bool PA>
 __device__ __forceinline__ void wreg_setup(WReg<MB, NQ, DA, PA>& w, const WregTab& T, unsigned char* lraw, int tid) {
     using G = WGeo<MB>;
+    if constexpr (DA && PA) {
+        // nothing is shared across the workgroup: every wave zeroes its own image once, pad rows and pad columns included (no
+        // LP writes them afterwards: all LPs of a batch have the same m and nd), and fills it per LP in load_lp_values
+        wreg_carve(w, (double*)(lraw + T.o_wave) + (size_t)(tid >> 6) * T.wave_doubles, tid);
+        const int cnt = T.img_rows * T.as;
+        for (int i = tid & 63; i < cnt; i += 64) w.wimg_()[i] = 0.0;
+        wave_lds_sync();
+        w.img = w.wimg_(); w.nd = T.nd; w.AS = T.as; w.imgR = T.img_rows;
+        w.m = T.m; w.n = T.n; w.rmax = 0;
+        return;
+    }
     if constexpr (PA) {
         // structure tables only; the values of a wave's LP go behind its wave area when it takes the LP
         int* s_lev = (int*)(lraw + T.o_lev);
@@ -1076,11 +1089,35 @@ __device__ __forceinline__ int newton_solve(WReg<MB, NQ, DA, PA>& w, const bool 
     return pass;
 }
 
-// PA: the values of LP `lp` (a row of a_batch [B, nnz], CSR order of the plan) into this wave's copy -- HBM -> LDS once per
+// PA: the values of LP `lp` (a row of a_batch [B, nnz], CSR order of the plan; DA && PA: its dense matrix) into this wave's copy -- HBM -> LDS once per
 // LP, 8 nnz bytes next to the 16 (m + n) + 24 of b, c, x, y; through a buffer descriptor (see row_rsrc), all loads of the
 // wave in flight before the first store
 template <int MB, int NQ, bool DA, bool PA>
 __device__ __forceinline__ void load_lp_values(WReg<MB, NQ, DA, PA>& w, const double* ag, long lp, int nnz) {
+    if constexpr (DA) {
+        // DA && PA: the LP's matrix, m x nd contiguous doubles (row-major [m, a_cols], a_cols = nd), into the wave's image at
+        // row stride AS.  Element e sits at (row, column) = (e / nd, e % nd); a lane's elements are 64 apart, so the pair is
+        // divided out once per LP (for e = lane) and then stepped by (64 / nd, 64 % nd) with one carry -- no division per
+        // element.  Eight loads per lane in flight per trip; a read past the matrix returns 0 and is not stored.
+        const int nd = w.nd, AS = w.AS, tot = w.m * nd;
+        const __amdgpu_buffer_rsrc_t ra = row_rsrc(ag + lp * tot, tot);
+        const int dq = 64 / nd, dr = 64 - dq * nd;       // (wave-uniform)
+        int row = w.lane / nd, col = w.lane - row * nd;
+        double* im = w.wimg_();
+        for (int e0 = 0; e0 < tot; e0 += 512) {
+            double v[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) v[k] = buf_ld(ra, 8u * (unsigned)(e0 + 64 * k + w.lane));
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                if (e0 + 64 * k + w.lane < tot) im[row * AS + col] = v[k];
+                col += dr; row += dq;
+                if (col >= nd) { col -= nd; row++; }
+            }
+        }
+        wave_lds_sync();
+        return;
+    }
     const __amdgpu_buffer_rsrc_t ra = row_rsrc(ag + lp * nnz, nnz);
     double* cv = w.cvl_();
     for (int e0 = 0; e0 < nnz; e0 += 512) {

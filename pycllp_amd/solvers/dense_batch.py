@@ -3,7 +3,9 @@
 ``lp.A`` is a ``SparseMatrix`` with ``data [nproblems, nnz]`` (one structure, per-problem values).  Up to m = 32 rows and
 n = 128 columns of the equality form the values are densified to ``[B, m, a_cols]`` on the host and solved on the lane-group
 kernel for per-problem A (``pycllp_hip_dense_solve_batch``, csrc/ipm_group_slot.inc, PA): ``kernel == 'group per-problem'``.
-Beyond that the LP goes to ``HipSparsePrimalNormalSolver`` unchanged: ``kernel == 'delegated'``.
+Beyond that a fully dense structure (``fully_dense``) of up to m = 128 rows and n = 256 columns goes through the same entry to the
+wavefront-per-LP kernel with a dense image per wave (csrc/ipm_wreg_dapa.hip), where its LDS plan admits the shape:
+``kernel == 'wave per-problem'``.  Every other LP goes to ``HipSparsePrimalNormalSolver`` unchanged: ``kernel == 'delegated'``.
 """
 import numpy as np
 import torch
@@ -16,6 +18,7 @@ from .hip import (RESULTS, DeviceArrays, Handle, HipSparsePrimalNormalSolver, _r
 
 GROUP_MAX_ROWS, GROUP_MAX_COLS = 32, 128      # the lane-group kernels
 SLACK_MAX_DENSE_COLS = 96                     # ... and their slack-aware shapes: at most 96 columns before the identity tail
+WAVE_MAX_ROWS, WAVE_MAX_COLS = 128, 256       # the wave kernel with an image per wave (WREG_DAPA_SHAPES of csrc/wreg.h)
 _REJECTED = _native.FLAG_HSD | _native.FLAG_PREDCORR | _native.FLAG_WARM_START | _native.FLAG_WAVE_KERNEL
 
 
@@ -30,6 +33,19 @@ def identity_tail(rows, cols, data, m, n):
     if int(nz.sum()) != m or not np.array_equal(np.sort(rows[nz]), np.arange(m)):
         return False
     return bool((rows[nz] == cols[nz] - (n - m)).all() and (data[:, nz] == 1.0).all())
+
+
+def fully_dense(rows, cols, data, m, n):
+    """True when the structure is that of a dense matrix: every position of the first nd columns is present exactly once, where
+    nd = n - m and the last m columns are the identity (``identity_tail``), or nd = n and there is no such tail."""
+    rows, cols = np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64)
+    if rows.size == 0 or rows.min() < 0 or rows.max() >= m or cols.min() < 0 or cols.max() >= n:
+        return False
+    nd = n - m if identity_tail(rows, cols, data, m, n) else n
+    head = cols < nd
+    if nd == n and rows.size != m * n or int(head.sum()) != m * nd:
+        return False
+    return np.unique(rows[head] * nd + cols[head]).size == m * nd
 
 
 def densify_batch(rows, cols, data, m, a_cols):
@@ -73,6 +89,7 @@ class HipDenseBatchPrimalNormalSolver(DeviceArrays, BaseSolver):
         self.hsd, self.autoscale, _, _, self.options = plugin_options(options, hsd, autoscale)
         self.device, self.stream = device, stream
         self._handle = self._delegate = None
+        self._wave = False
         self.kernel = None
         self.slack = False
 
@@ -85,16 +102,16 @@ class HipDenseBatchPrimalNormalSolver(DeviceArrays, BaseSolver):
         self.m, self.n = m, n
         self._handle = self._delegate = None
         self._keepalive = None
-        if m > GROUP_MAX_ROWS or n > GROUP_MAX_COLS:
-            self._delegate = HipSparsePrimalNormalSolver(device=self.device, stream=self.stream, autoscale=self.autoscale,
-                                                         hsd=self.hsd, **self.options)
-            self._delegate.init(lp, verbose=verbose)
-            return
         A = lp.A
+        group = m <= GROUP_MAX_ROWS and n <= GROUP_MAX_COLS
+        self._wave = (not group and m <= WAVE_MAX_ROWS and n <= WAVE_MAX_COLS and isinstance(A, SparseMatrix)
+                      and fully_dense(A._rows, A._cols, A.data, m, n))
+        if not group and not self._wave:
+            return self._delegate_to_sparse(lp, verbose)
         if not isinstance(A, SparseMatrix):
             raise ValueError("%s takes lp.A as a SparseMatrix with data [nproblems, nnz]" % self.name)
         no_slack = bool(int(self.options.get("flags", 0)) & _native.FLAG_NO_SLACK_PATH)
-        ident = identity_tail(A._rows, A._cols, A.data, m, n) and n - m <= SLACK_MAX_DENSE_COLS
+        ident = identity_tail(A._rows, A._cols, A.data, m, n) and (self._wave or n - m <= SLACK_MAX_DENSE_COLS)
         self.slack = ident and not no_slack
         # a handle whose matrix has the identity tail where this batch as a whole has not (problem 0 only, say) would expect
         # the short matrices: the full ones then go with FLAG_NO_SLACK_PATH
@@ -103,13 +120,29 @@ class HipDenseBatchPrimalNormalSolver(DeviceArrays, BaseSolver):
         if verbose > 0:
             print("Initializing %s (m=%d, n=%d, a_cols=%d) on %s" % (type(self).__name__, m, n, self.a_cols, self.device))
         self._handle = Handle(np.ascontiguousarray(A.todense(0), dtype=np.float64).reshape(m, n), self.device, self.stream)
+        if self._wave:
+            # the first launch, of an empty batch: the library builds its LDS plan and declines here where no variant or plan
+            # covers the shape -- the solver then delegates from now on
+            try:
+                empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)
+                self._launch(empty(0, m, self.a_cols), empty(0, m), empty(0, n), 0, {})
+            except NotImplementedError:
+                self._handle = None
+                self._delegate_to_sparse(lp, verbose)
+
+    def _delegate_to_sparse(self, lp, verbose):
+        self._wave = False
+        self._delegate = HipSparsePrimalNormalSolver(device=self.device, stream=self.stream, autoscale=self.autoscale,
+                                                     hsd=self.hsd, **self.options)
+        self._delegate.init(lp, verbose=verbose)
 
     def solve_device(self, A_dev, b_dev, c_dev, **options):
         """Device-resident entry: A [B, m, a_cols] (``self.a_cols``: n - m where the identity tail is implied, else n),
         b [B, m], c [B, n] (torch CUDA tensors or numpy) -> dict of CUDA tensors (``RESULTS``).  Asynchronous on the solver's
         stream; the kernel's verdict stands (no look at the data: ``autoscale='auto'`` and ``hsd='auto'`` count as off)."""
         if self._handle is None:
-            raise RuntimeError("solve_device() needs init() on an LP the lane-group kernel serves (m <= 32, n <= 128)")
+            raise RuntimeError("solve_device() needs init() on an LP the lane-group kernel (m <= 32, n <= 128) or the wave "
+                               "kernel for per-problem dense matrices serves")
         return self._launch(self._dev(A_dev), self._dev(b_dev), self._dev(c_dev), 0, options)
 
     def _launch(self, A, b, c, extra_flags, overrides):
@@ -125,7 +158,7 @@ class HipDenseBatchPrimalNormalSolver(DeviceArrays, BaseSolver):
         o = solve_opts(self.options, self._flags | extra_flags, **overrides)
         self._handle.solve_batch_dense(self.stream, A, b, c, out, o)
         self._keepalive = (A, b, c)
-        self.kernel = "group per-problem"
+        self.kernel = "wave per-problem" if self._wave else "group per-problem"
         return out
 
     def solve(self, lp, verbose=0):
@@ -193,6 +226,6 @@ class HipDenseBatchPrimalNormalSolver(DeviceArrays, BaseSolver):
                 run(np.array([k]))
 
     def launch_info(self):
-        """grid / block / LDS bytes, ``group_shape`` (MP, NP) and ``slack`` of the last launch (``Handle.launch_info``); the
-        delegate's where it served the solve."""
+        """grid / block / LDS bytes, ``group_shape`` (MP, NP) and ``slack`` of the last launch (``Handle.launch_info``) -- on the
+        wave kernel ``wave_shape`` (MB, NQ), ``variant`` and ``kernel`` instead; the delegate's where it served the solve."""
         return self._delegate.launch_info() if self._delegate is not None else self._handle.launch_info()
