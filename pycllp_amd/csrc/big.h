@@ -1,4 +1,4 @@
-// big.h -- internal interface between ipm_dense.hip (C ABI, handles) and ipm_big.hip (the workgroup-per-LP kernel for LPs
+// big.h -- internal interface between abi_sparse.hip (C ABI, handles; host.h) and ipm_big.hip (the workgroup-per-LP kernel for LPs
 // beyond the register-resident kernels: 128 < m <= 256 rows or 512 < n <= 1280 columns).  Not part of the public ABI.
 #ifndef PYCLLP_BIG_H
 #define PYCLLP_BIG_H

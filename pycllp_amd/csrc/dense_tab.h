@@ -1,0 +1,43 @@
+// dense_tab.h -- internal interface between abi_dense.hip (C ABI, handle, queue ring) and ipm_dense.hip, the translation unit of
+// the lane-group kernels on a shared dense A: its launcher tables, and the launch plans of every lane-group kernel (those of
+// ipm_group_pa.hip and ipm_group_pabd.hip included: the plans need the kernels' geometry).  Not part of the public ABI.
+#ifndef PYCLLP_DENSE_TAB_H
+#define PYCLLP_DENSE_TAB_H
+#include "group_pa.h"
+#include "host.h"
+
+// A plan depends on the kernel's compile-time geometry, so the rows hold it as a function
+typedef LaunchPlan (*dense_plan_fn)(const DeviceLimits&, long B, const DevOpts&);
+// One launch on its plan; sets the kernel's dynamic LDS itself.  GroupPaArgs (group_pa.h) with A = the handle's row-major copy
+// [m, n]; the queue-ring slot behind a.queue and the plan's publication are the caller's.
+typedef hipError_t (*dense_launch_fn)(const GroupPaArgs&, const LaunchPlan&, DevOpts, hipStream_t);
+struct DenseKernel { dense_plan_fn plan; dense_launch_fn launch; };
+
+struct NewtonArgs { int m, n; long B; const double *pack, *x, *z, *y, *b, *c; double mu; double* dy; int* nref; };
+typedef hipError_t (*newton_launch_fn)(const NewtonArgs&, const LaunchPlan&, DevOpts, hipStream_t);
+typedef hipError_t (*pack_launch_fn)(int m, int n, const double* A, double* pack, hipStream_t);
+
+struct Variant {
+    int mp, np, apack;
+    pack_launch_fn pack;
+    DenseKernel solve_group;  // group-per-LP kernel (default)
+    DenseKernel solve_hsd;    // group-per-LP kernel on the homogeneous self-dual embedding (PYCLLP_FLAG_HSD)
+    DenseKernel solve_pc;     // group-per-LP kernel with Mehrotra's predictor-corrector (PYCLLP_FLAG_PREDCORR)
+    dense_plan_fn newton_plan;
+    newton_launch_fn newton;
+};
+// slack-aware group kernels: (MP, NP) with NP - MP padded dense columns + the m identity columns
+struct SlackVariant { int mp, np; DenseKernel solve_group, solve_hsd, solve_pc, solve_bounded; };
+
+// one row per lane-group shape of GROUP_SHAPES (group_pa.h), in its order: the first that covers (m, n) is used, in both tables
+extern const Variant kVariants[];
+extern const int kNumVariants;
+extern const SlackVariant kSlackVariants[];
+extern const int kNumSlackVariants;
+
+// launch plans of the kernels for per-problem dense A; their launchers are kGroupPA's and kGroupPABD's (group_pa.h)
+struct PaPlan { int mp, np, sl; dense_plan_fn plan; };
+struct PaPlans { const PaPlan* v; int n; };
+extern const PaPlans kPaPlans;
+extern const PaPlans kPaBdPlans;   // ... and with upper bounds
+#endif

@@ -1,4 +1,4 @@
-// group_pa.h -- internal interface between ipm_dense.hip (C ABI, handles, launch plans) and ipm_group_pa.hip / ipm_group_pabd.hip,
+// group_pa.h -- internal interface between abi_dense.hip (C ABI, handles; the launch plans are dense_tab.h's) and ipm_group_pa.hip / ipm_group_pabd.hip,
 // the translation units of the lane-group kernels for per-problem dense A (ipm_group_slot.inc), and the home of GROUP_SHAPES,
 // the shape list of all three.  Not part of the public ABI.
 #ifndef PYCLLP_GROUP_PA_H

@@ -15,24 +15,8 @@
 // (thread = column), m-vectors in LDS.  The triangular solves run inside one wavefront (readlane broadcasts, no
 // workgroup barriers).  Semantics = oracle/ipm_dense_ref.c, including the x-space refinement (the reference's
 // sparse solve has its refinement commented out, ldl.cl:698-711).
-#define BLK_T 256
-#define BLK_MAX_M 128
-#define BLK_MAX_N 512
+// (BLK_T, BLK_MAX_M, BLK_MAX_N and BlockA, the device-side description of the shared constraint matrix: block.h)
 #define BLK_NC (BLK_MAX_N / BLK_T)
-
-struct BlockA {            // device-side description of the shared constraint matrix
-    int m, n, nnz;
-    const double* csr_val; const int* csr_ptr; const int* csr_col;   // A by rows
-    const double* csc_val; const int* csc_ptr; const int* csc_row;   // A by columns
-    int n_entries, n_terms;                                          // Gram term list
-    const int* ent_tri; const int* ent_ptr;                          // packed index of entry e, its term range
-    const double* term_w; const int* term_col;                       // weight a_ij a_kj and column j
-    int a_in_lds;                                                    // CSR/CSC copied to LDS at block start
-    // per-problem values of A (SparseMatrix.data[nproblems, nnz], pycllp/lp.py:16-54): the structure above is shared, the
-    // values of LP `lp` are a_batch[lp, :] in CSR order (kernel argument); what the kernel then needs besides them:
-    const int* csc_src;                                              // CSC position -> CSR index of the same entry
-    const int* term_ia; const int* term_ib;                          // Gram term = val[term_ia] * val[term_ib]
-};
 
 __device__ __forceinline__ int tri_idx(int i, int k) { return i * (i + 1) / 2 + k; }
 

@@ -1,7 +1,7 @@
 // ipm_group_pa.hip -- translation unit of ipm_group_pa_kernel (ipm_group_slot.inc): the lane-group kernel for batches of LPs
 // with per-problem dense A.  A unit of its own (as ipm_wreg_bd.o is for the bounded wave kernel), so that the code objects of
-// every other kernel of the library are what they were before this kernel existed.  ipm_dense.hip owns the handle, the launch
-// plan and the C ABI (pycllp_hip_dense_solve_batch) and reaches the kernels through kGroupPA (group_pa.h).
+// every other kernel of the library are what they were before this kernel existed.  abi_dense.hip owns the handle and the C ABI
+// (pycllp_hip_dense_solve_batch), ipm_dense.hip the launch plan (dense_tab.h); the kernels are reached through kGroupPA (group_pa.h).
 #include "group_pa.h"
 #include "ipm_group.inc"
 #include "ipm_group_slot.inc"

@@ -1,8 +1,8 @@
 // ipm_group_pabd.hip -- translation unit of ipm_bounded_pa_kernel (ipm_group_slot.inc): the lane-group kernel for batches of LPs
 // with upper bounds AND per-problem dense A.  A unit of its own (as ipm_group_pa.o is for the kernel without bounds), so that
-// the code objects of every other kernel of the library are what they were before this kernel existed.  ipm_dense.hip owns the
-// handle, the launch plan and the C ABI (pycllp_hip_dense_solve_batch_bounded) and reaches the kernels through kGroupPABD
-// (group_pa.h).
+// the code objects of every other kernel of the library are what they were before this kernel existed.  abi_dense.hip owns the
+// handle and the C ABI (pycllp_hip_dense_solve_batch_bounded), ipm_dense.hip the launch plan (dense_tab.h); the kernels are
+// reached through kGroupPABD (group_pa.h).
 #include "group_pa.h"
 #include "ipm_group.inc"
 #include "ipm_group_slot.inc"

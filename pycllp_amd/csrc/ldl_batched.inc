@@ -5,8 +5,7 @@
 // tests/test_ldl.py:139-193 on 32 matrices of 100 x 100).  Here one matrix is owned by one workgroup: the matrix
 // sits in LDS (row stride n+1: column reads are conflict free), thread i owns row i, the sweep is right-looking
 // and stores L in place.  Output layout as the reference: L packed lower-triangular with unit diagonal,
-// L[i(i+1)/2 + j] (ldl.cl:12-18, per matrix instead of batch-interleaved), D[n].
-#define LDL_MAX_N 128
+// L[i(i+1)/2 + j] (ldl.cl:12-18, per matrix instead of batch-interleaved), D[n].  n <= LDL_MAX_N (block.h).
 
 __device__ __forceinline__ double block_max(double v, double* red, int tid, int nwaves) {
     v = wave_max(v);

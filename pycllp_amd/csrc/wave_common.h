@@ -56,7 +56,7 @@ __device__ __forceinline__ double readlane_d(double v, int srclane) {
 // every use instead of being hoisted out of a persistent loop into long-lived VGPRs
 __device__ __forceinline__ double sopaque(double v) { asm volatile("" : "+s"(v)); return v; }
 __device__ __forceinline__ int iopaque(int v) { asm volatile("" : "+s"(v)); return v; }
-// The two scaling options as the kernels see them (DevOpts::flags; to_dev in ipm_dense.hip): PYCLLP_FLAG_AUTOSCALE -- the scaling
+// The two scaling options as the kernels see them (DevOpts::flags; to_dev in abi_sparse.hip): PYCLLP_FLAG_AUTOSCALE -- the scaling
 // code of an LP's load and store runs, as it always has -- and PYCLLP_FLAG_AUTOSCALE_PER_LP beside it -- that code takes a verdict
 // per LP.  (A caller sets one of the two; the entries refuse both and hand a caller's PER_LP on as the pair.)
 #define PYCLLP_AUTOSCALE_ANY (PYCLLP_FLAG_AUTOSCALE | PYCLLP_FLAG_AUTOSCALE_PER_LP)

@@ -1,4 +1,4 @@
-// wreg.h -- internal interface between ipm_dense.hip (C ABI, handles), ipm_wreg.hip (host side of the register-resident
+// wreg.h -- internal interface between abi_sparse.hip (C ABI, handles; host.h), ipm_wreg.hip (host side of the register-resident
 // one-LP-per-wavefront kernels of the sparse shared-A path) and the units that compile those kernels (ipm_wreg_*.hip on
 // wreg_wave.h).  Not part of the public ABI.
 #ifndef PYCLLP_WREG_H

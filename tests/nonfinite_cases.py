@@ -515,7 +515,7 @@ def sized(row, guess):
 
 
 def first_guess(row):
-    """B for four resident compute units by the launch rules (ipm_dense.hip plan_group: eight waves per workgroup, 64 / MP
+    """B for four resident compute units by the launch rules (ipm_dense.hip plan_group with host.h small_batch_wpb: eight waves per workgroup, 64 / MP
     lane groups per wave; the wave kernel: four waves per workgroup and up to two workgroups per compute unit; block and
     large-LP kernel: up to four workgroups per compute unit); ``sized`` corrects it from ``launch_info()``."""
     if row.family in ("slack", "group", "perA-dense"):

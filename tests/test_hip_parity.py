@@ -1461,3 +1461,57 @@ def test_sparse_results_do_not_depend_on_batch_size(hsd):
         torch.cuda.synchronize()
         for k in ("x", "y", "z", "pobj", "dobj", "status", "iters"):
             assert torch.equal(part[k][:nb], full[k][idx]), (nb, k)
+
+
+def test_dense_handle_beyond_the_lane_groups_is_the_sparse_handle_of_its_csr():
+    """pycllp_hip_dense_init beyond the lane-group kernels (m = 33 > 32) builds its sparse handle from the host CSR arrays of A's
+    non-zeros: pycllp_hip_dense_solve on it and pycllp_hip_sparse_solve on a handle pycllp_hip_sparse_init made from the same
+    CSR arrays run the same kernel on the same plan and return the same bits.  The LPs are feasible and bounded by construction
+    (b = A x0, c = A'y0 + z0 with x0, z0 > 0)."""
+    import ctypes
+    from pycllp_amd import _native
+    L = _native.lib()
+    m, n, B = 33, 40, 8
+    rs = np.random.RandomState(33)
+    A = np.c_[rs.rand(m, n - m) + 0.1, np.eye(m)]
+    x0, y0, z0 = rs.rand(B, n) + 0.5, rs.rand(B, m), rs.rand(B, n) + 0.5
+    b, c = x0 @ A.T, y0 @ A + z0
+    nz = A != 0.0
+    data, indices = A[nz], np.nonzero(nz)[1]                    # row-major: CSR order
+    indptr = np.r_[0, np.cumsum(nz.sum(axis=1))]
+    dev = torch.device("cuda", 0)
+    t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
+    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    Ad, bd, cd = t(A, np.float64), t(b, np.float64), t(c, np.float64)
+    vd, pd, id_ = t(data, np.float64), t(indptr, np.int32), t(indices, np.int32)
+    hd, hs = ctypes.c_void_p(), ctypes.c_void_p()
+    torch.cuda.synchronize()
+    _native.check(L.pycllp_hip_dense_init(m, n, p(Ad), None, ctypes.byref(hd)), "dense_init")
+    try:
+        _native.check(L.pycllp_hip_sparse_init(m, n, int(data.size), p(vd), p(pd), p(id_), None, ctypes.byref(hs)), "sparse_init")
+        try:
+            out, info = {}, {}
+            for name, solve, h in (("dense", L.pycllp_hip_dense_solve, hd), ("sparse", L.pycllp_hip_sparse_solve, hs)):
+                x = torch.empty((B, n), dtype=torch.float64, device=dev); z = torch.empty_like(x)
+                y = torch.empty((B, m), dtype=torch.float64, device=dev)
+                po = torch.empty(B, dtype=torch.float64, device=dev); do = torch.empty_like(po)
+                st = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty_like(st)
+                torch.cuda.synchronize()
+                _native.check(solve(h, B, p(bd), p(cd), p(x), p(y), p(z), p(po), p(do), p(st), p(it), None, None), name)
+                torch.cuda.synchronize()
+                out[name] = dict(x=x, y=y, z=z, pobj=po, dobj=do, status=st, iters=it)
+            g, bl, lds, kern = (ctypes.c_int() for _ in range(4))
+            mp, np_ = ctypes.c_int(), ctypes.c_int()
+            assert L.pycllp_hip_dense_launch_info(hd, ctypes.byref(g), ctypes.byref(bl), ctypes.byref(lds), ctypes.byref(mp), ctypes.byref(np_)) == 0
+            info["dense"] = (g.value, bl.value, lds.value, L.pycllp_hip_dense_kernel_kind(hd))
+            assert L.pycllp_hip_sparse_launch_info(hs, ctypes.byref(g), ctypes.byref(bl), ctypes.byref(lds), ctypes.byref(kern)) == 0
+            info["sparse"] = (g.value, bl.value, lds.value, kern.value)
+            print("launch_info (grid, block, lds, kernel kind):", info)
+            assert info["dense"] == info["sparse"] and info["dense"][0] > 0 and info["dense"][3] > 0
+            assert (out["dense"]["status"] == 0).all()
+            for k in ("x", "y", "z", "pobj", "dobj", "status", "iters"):
+                assert torch.equal(out["dense"][k], out["sparse"][k]), k
+        finally:
+            L.pycllp_hip_sparse_free(hs)
+    finally:
+        L.pycllp_hip_dense_free(hd)

@@ -28,7 +28,7 @@ WAVE_DA_SHAPES = [(1, 4), (2, 4), (3, 4), (4, 2), (4, 4), (5, 4), (6, 4), (7, 4)
 GROUP_SHAPES = [(16, 32), (16, 48), (16, 64), (32, 64), (32, 96), (32, 128)]
 
 # kinds per family: the launcher tables of csrc/wreg.h (kWTab, kWPA, kWPC, kWPCPA, kWBD / kWDA, kWPCDA, kWBDDA) and the
-# Variant / SlackVariant tables of csrc/ipm_dense.hip
+# Variant / SlackVariant tables of csrc/ipm_dense.hip (declared in csrc/dense_tab.h; the C ABI that uses them is csrc/abi_dense.hip)
 KINDS = {
     "tables": ("plain", "hsd", "newton", "pc", "pa", "pa-hsd", "pa-pc", "bounded"),
     "image": ("plain", "hsd", "newton", "pc", "bounded"),

@@ -689,11 +689,11 @@ def ldl_slots(entry, modified):
 def test_ldl_launch_rules_are_those_of_the_sources():
     """What ldl_slots restates: min(B, 4096) workgroups in the three launches of ldl_batched.inc's kernels, min(CUs, (B + 3) / 4)
     workgroups of four waves in ldl_solve_wreg_kernel's."""
-    dense = open(os.path.join(tkv.CSRC, "ipm_dense.hip")).read()
+    block = open(os.path.join(tkv.CSRC, "ipm_block.hip")).read()
     wreg = open(os.path.join(tkv.CSRC, "ipm_wreg.hip")).read()
-    assert dense.count("blocks = B < 4096 ? B : 4096;") == 3
+    assert block.count("blocks = B < 4096 ? B : 4096;") == 3
     for kernel in ("ldl_batched_kernel", "ldl_solve_batched_kernel", "forward_backward_ldl_kernel"):
-        assert "hipLaunchKernelGGL(%s, dim3((unsigned)blocks)" % kernel in dense, kernel
+        assert "hipLaunchKernelGGL(%s, dim3((unsigned)blocks)" % kernel in block, kernel
     launch = wreg[wreg.index("hipError_t wreg_launch_ldl_solve"):]
     assert "long grid = std::min((long)num_cu, (B + 3) / 4);" in launch[:launch.index("hipLaunchKernelGGL")]
     assert "hipLaunchKernelGGL((ldl_solve_wreg_kernel<8>), dim3((unsigned)grid), dim3(256)" in launch

@@ -315,7 +315,7 @@ def _src(name):
 
 
 def test_constants_and_shape_list_of_the_sources():
-    big, bigh, blk = _src("ipm_big.hip"), _src("big.h"), _src("ipm_block.inc")
+    big, bigh, blk = _src("ipm_big.hip"), _src("big.h"), _src("block.h")
     line = re.search(r"#define BIG_SHAPES\(X\)(.*)", big).group(1)
     assert [(int(a), int(b)) for a, b in re.findall(r"X\((\d+),\s*(\d+)\)", line)] == BIG_SHAPES
     assert int(re.search(r"constexpr int BT = (\d+);", big).group(1)) == BT

@@ -4,7 +4,7 @@
     python tools/isa_compare.py PARENT/libpycllp_hip.so BRANCH/libpycllp_hip.so OUTDIR TAG
 
 OUTDIR/isa_identity_TAG.txt: every kernel's disassembly (llvm-objdump -d --no-show-raw-insn, address comments and the padding
-mark behind a code object's last kernel removed, split at the <symbol>: lines) -- identical, changed, gone or new, and in how
+mark behind a code object's last kernel and the s_nop fill behind a kernel's last instruction removed, split at the <symbol>: lines) -- identical, changed, gone or new, and in how
 many code objects it sits.  OUTDIR/kernel_resources_parent_branch_TAG.txt: for the wave kernels the figures of
 tools/kernel_resources.py side by side and the instruction counts per opcode of f64 arithmetic, MFMA, LDS and memory
 instructions compared (a changed f64 count means an operation was contracted or split differently)."""
@@ -28,6 +28,8 @@ def load(lib):
                 if cur is None or not line.strip(): continue
                 t = re.sub(r"\s*//.*$", "", line).strip()
                 if t != "...": body[cur].append(t)   # "...": objdump's mark for the zero padding behind a code object's last kernel
+            for b in body.values():                  # ... and the s_nop fill behind a kernel's last instruction: alignment of the next
+                while b and b[-1] == "s_nop 0": b.pop()   # function or, behind a code object's last kernel, its 256-byte tail
             syms = [s for s in body if s in recs]
             for s, d in zip(syms, dem(syms)):
                 ks.setdefault(d, []).append((body[s], recs[s]))
