@@ -11,7 +11,7 @@
 //     the diagonal blocks' lower tiles on v_mfma_f64_4x4x4_4b_f64, see gram_pair()), groups taking turns;
 //     its operands now come straight from ONE row-major image of A in LDS (odd row stride: the
 //     row-per-lane reads are conflict free, the MFMA-order reads see a harmless 2-way conflict);
-//   * group reductions use DPP row operations (+ one ds_swizzle for 32-lane groups) instead of ds_bpermute;
+//   * group reductions use DPP row operations (+ one lane swap between the two rows of a 32-lane group) instead of ds_bpermute;
 //   * the LDL' column sweep hands the RAW column (pivot included) through LDS, so no cross-lane pivot broadcast
 //     sits on the critical path: every lane derives 1/D_j itself from the broadcast read;
 //   * groups are independent slots: a slot that finishes its LP stores it and immediately loads its next one, so
@@ -136,6 +136,10 @@ struct GeoG {
 };
 
 // sum / max over the MP lanes of each group; every lane of the group receives the result
+// MP = 32: the last stage is a lane swap between the group's two 16-lane rows, which moves active lanes only.  Every call site
+// is reached by whole 32-lane groups: the kernels' bodies and GWave's members run under wave-uniform conditions, and the one
+// per-group condition (finalize(), whose verdict every lane of a group derives from these very sums) keeps both rows of a group
+// together.  A reduction across groups (v_permlane32_swap) would not be allowed there.
 template <int MP>
 __device__ __forceinline__ double grp_sum(double v) {
     // v is pinned first: were its producer a product, the compiler would contract the first stage into
@@ -147,7 +151,7 @@ __device__ __forceinline__ double grp_sum(double v) {
     v += dpp_d<0x4E>(v);    // quad_perm(2,3,0,1): xor 2
     v += dpp_d<0x141>(v);   // row_half_mirror: the other quad of each 8
     v += dpp_d<0x140>(v);   // row_mirror: the other 8 of each 16
-    if (MP == 32) v += swz_xor16_d(v);
+    if (MP == 32) v = row_pair_sum(v);   // top + bottom in both rows: the bits of own + other
     return v;
 }
 template <int MP>
@@ -156,7 +160,7 @@ __device__ __forceinline__ double grp_max(double v) {
     v = fmax(v, dpp_d<0x4E>(v));
     v = fmax(v, dpp_d<0x141>(v));
     v = fmax(v, dpp_d<0x140>(v));
-    if (MP == 32) v = fmax(v, swz_xor16_d(v));
+    if (MP == 32) v = row_pair_max(v);
     return v;
 }
 // value held by lane k (0 <= k < MP, wave-uniform) of the caller's own group
@@ -225,21 +229,34 @@ struct GWave {
     // read next to its FMA and the loop runs at LDS latency.  The partial sums are pinned after every batch too: left free,
     // the scheduler may sink every FMA below the last batch's loads and keep the whole image of A live at once (the
     // predictor-corrector kernel spilled 96-433 registers that way; 6.06 -> 5.45 ms at (32, 96)).
+    // u_i comes from registers: a DPP row broadcast (lane i & 15) of the u of the group's top or bottom 16-lane row, which one lane
+    // swap hands to both rows (whole wave active at every call site).  STAGED: u through the wave's staging area instead -- a
+    // write, a wave sync and MP broadcast reads, as before the lane swaps -- for the kernel that pays for the registers with
+    // scratch (AT_STAGED in the HSD kernel).  Same FMAs in the same order either way.
+    template <bool STAGED = false>
     __device__ __forceinline__ void At_times(double u, double (&out)[NCG]) const {
         const int g = ogl();
-        stage[grp * MP + g] = u;
-        wave_lds_sync();
-        unsigned uba = lds_addr(stage + grp * MP);      // opaque: see A_times
-        asm volatile("" : "+v"(uba));
-        const __attribute__((address_space(3))) double* ub = (const __attribute__((address_space(3))) double*)(size_t)uba;
+        double ur[2] = {u, u};
+        const __attribute__((address_space(3))) double* ub = nullptr;
+        if constexpr (STAGED) {
+            stage[grp * MP + g] = u;
+            wave_lds_sync();
+            unsigned uba = lds_addr(stage + grp * MP);      // opaque: see A_times
+            asm volatile("" : "+v"(uba));
+            ub = (const __attribute__((address_space(3))) double*)(size_t)uba;
+        } else if constexpr (MP == 32) {
+            ur[0] = top_row_d(u); ur[1] = bottom_row_d(u);
+        }
         const double* ac = Aimg + g;
         constexpr int RB = PYCLLP_AT_RB, NB = MP / RB;
         double a0[RB][NCD], a1[RB][NCD], u0[RB], u1[RB];
 #define AT_LOAD(A_, U_, I0)                                                                     \
-    _Pragma("unroll") for (int ii = 0; ii < RB; ii++) {                                         \
-        U_[ii] = ub[(I0) + ii + tok];                                                           \
-        _Pragma("unroll") for (int q = 0; q < NCD; q++) A_[ii][q] = ac[((I0) + ii) * AS + MP * q + tok]; \
-    }
+    static_for<0, RB>([&](auto ic_) {                                                           \
+        constexpr int ii = decltype(ic_)::value, i_ = (I0) + ii;                                \
+        if constexpr (STAGED) U_[ii] = ub[i_ + tok];                                            \
+        else U_[ii] = row_bcast<(i_ & 15)>(ur[i_ >> 4]);                                        \
+        _Pragma("unroll") for (int q = 0; q < NCD; q++) A_[ii][q] = ac[i_ * AS + MP * q + tok]; \
+    });
 #define AT_USE(A_, U_)                                                                          \
     _Pragma("unroll") for (int ii = 0; ii < RB; ii++) {                                         \
         asm volatile("" : "+v"(U_[ii]));                                                        \
@@ -267,7 +284,7 @@ struct GWave {
         });
 #undef AT_LOAD
 #undef AT_USE
-        wave_lds_sync();
+        if constexpr (STAGED) wave_lds_sync();
     }
 
     // (A v)_gl with v given per column of the own group's LP -- row-per-lane, conflict-free thanks to the odd stride;
@@ -309,11 +326,13 @@ struct GWave {
     }
 
     // Gram product of group g's LP on the matrix cores (whole wave), fused with A*x (AX) and A*(d.t).
-    // stage holds that LP's x, d, d*t in k-layout.  M goes to group g's slab; Ax/Adt come back for rows (l & 15) + 16 J.
+    // stage holds that LP's x, d, d*t in k-layout.  M goes to group g's slab; Ax/Adt come back for row l & (MP - 1), in every lane
+    // group (ax is left alone without AX).  Reached with the whole wave active, which the lane swaps of its last lines need.
     // LATE: the store offsets are read after the k-loop instead of before it (their latency is then exposed, but they are not live
     // across the loop: the bounded kernel, which has no registers to spare there, spilt four without it).
     template <bool AX = true, bool LATE = false>
-    __device__ __forceinline__ void gram_one(int g, double (&axp)[JB], double (&adp)[JB]) const {
+    __device__ __forceinline__ void gram_one(int g, double& ax, double& ad) const {
+        double axp[JB], adp[JB];
         int lo0_ = lane;                      // opaque copy: see ogl()
         asm volatile("" : "+v"(lo0_));
         const int kg = lo0_ >> 4, cc = lo0_ & 15;
@@ -409,14 +428,15 @@ struct GWave {
 #pragma unroll
             for (int r4 = 0; r4 < 4; r4++) sg[G_::sidx(kg2 + 4 * r4, cc2)] = acc[r4];
         }
-#pragma unroll
-        for (int J = 0; J < JB; J++) {
-            if (AX) {
-                axp[J] += __shfl_xor(axp[J], 16, WAVE);
-                axp[J] += __shfl_xor(axp[J], 32, WAVE);
-            }
-            adp[J] += __shfl_xor(adp[J], 16, WAVE);
-            adp[J] += __shfl_xor(adp[J], 32, WAVE);
+        // The partial sums over k = kg mod 4 of the four 16-lane rows, summed on lane swaps (whole wave: see the head of the function).
+        // MP = 32: lane (kg, cc) holds rows cc and 16 + cc; the total of row cc comes back in the even 16-lane rows, that of row 16 + cc
+        // in the odd ones, which is the lane -> row map of a group (gl = l & 31).  MP = 16: the total of row cc in all four rows.
+        if constexpr (MP == 32) {
+            if (AX) ax = quad_sum2(axp[0], axp[1]);
+            ad = quad_sum2(adp[0], adp[1]);
+        } else {
+            if (AX) ax = quad_sum(axp[0]);
+            ad = quad_sum(adp[0]);
         }
     }
 
@@ -441,12 +461,7 @@ struct GWave {
     // L ends up in W (W[j] = L[gl][j], 0 on and above the diagonal) and is written to the slab column by column, as
     // each becomes final, in the layout the substitution reads.  Arithmetic: u_i u_k / D_j as fma(-(u_i / D_j), u_k, .).
     // top row's value of u in both DPP rows of a 32-lane group (gfx950 v_permlane16_swap: [0] = rows (0, 0, 2, 2))
-    __device__ __forceinline__ static double top_row_of(double u) {
-        const int lo = __double2loint(u), hi = __double2hiint(u);
-        auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        return __hiloint2double(b[0], a[0]);
-    }
+    __device__ __forceinline__ static double top_row_of(double u) { return top_row_d(u); }
 
     // The sweep takes "below the pivot" / "the pivot's lane" as EXEC masks (wave_common.h, round 3).  Tried and removed:
     // software-pipelining the next pivot's chain into column j's updates (6.314 against 6.26 ms per 65 536 LPs: with two waves
@@ -461,7 +476,7 @@ struct GWave {
     // so EXEC is not touched and lanes on and above a pivot still execute r -= 0 * r_j as they do there.
     //   MP = 16: step j follows column j, j = 0 .. 14.
     //   MP = 32: the top DPP row's steps follow columns 0 .. 14; its finished values then cross to the bottom row (one
-    //   ds_swizzle, issued after column 14) for the 16 accumulate steps of dot16_bcast, the subtraction and the bottom row's 15
+    //   lane swap, issued after column 14) for the 16 accumulate steps of dot16_bcast, the subtraction and the bottom row's 15
     //   steps.  These 32 dependent operations are dealt two to a column over columns 16 .. 31, one behind the pivot's broadcast
     //   and one behind its reciprocal, so that none of their latency stands in front of a pivot: the step of column c runs
     //   inside column 17 + c / 2, on the W[c] that the lane still holds, and only the last one (c = 30) follows column 31.
@@ -551,7 +566,7 @@ struct GWave {
                 for (int i = 0; i < NR; i++) fwd_step<j, (MP == 32) ? 0x5 : 0xF>(r[i], l);
                 if constexpr (MP == 32 && j == 14) {
 #pragma unroll
-                    for (int i = 0; i < NR; i++) so[i] = swz_xor16_d(r[i]);
+                    for (int i = 0; i < NR; i++) so[i] = top_row_d(r[i]);   // (whole wave, like top_row_of above)
                 }
             }
         });
@@ -604,7 +619,7 @@ struct GWave {
 
     // s <- (L D L')^-1 s for every group.  Substitution runs in 16x16 blocks so that every broadcast stays inside
     // a 16-lane DPP row (row_newbcast: 2 moves, no SGPR round trip); a 32-lane group does top block, the 16x16
-    // off-diagonal product (operand fetched across the rows by one ds_swizzle) and bottom block.
+    // off-diagonal product (operand fetched across the rows by one lane swap, top_row_d / bottom_row_d) and bottom block.
     // forward(s): s <- L^-1 s from the slab's column layout; backward(s, rdiag): s <- L^-T D^-1 s from its rows.  fwd_back is the
     // whole solve, for callers that have no sweep to carry their right-hand side (refinement, the corrector, the guarded path);
     // behind factor_dpp_fwd the caller runs back_after_sweep() on what the sweep returned: the row loads are then the first
@@ -642,7 +657,7 @@ struct GWave {
         } else {
             const bool top = gl < 16;
             if (top) subst15_up(s, lf);           // t1 = L11^-1 r1
-            const double so = swz_xor16_d(s);     // bottom rows see t1
+            const double so = top_row_d(s);       // bottom rows see t1 (outside the branches: the swap needs both rows active)
             if (!top) {
                 s -= dot16_bcast(so, lf);         // r2 -= L21 t1 (no serial dependence)
                 subst15_up(s, lf + 16);           // t2 = L22^-1 r2
@@ -660,7 +675,7 @@ struct GWave {
         } else {
             const bool top = gl < 16;
             if (!top) subst15_down(s, lb + 16);   // x2 = L22^-T s2
-            const double so = swz_xor16_d(s);     // top rows see x2
+            const double so = bottom_row_d(s);    // top rows see x2 (outside the branches: the swap needs both rows active)
             if (top) {
                 s -= dot16_bcast(so, lb + 16);    // s1 -= L21^T x2
                 subst15_down(s, lb);              // x1 = L11^-T s1
@@ -830,6 +845,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 double cm = 0.0;
 #pragma unroll
                 for (int q = 0; q < NCG; q++) cm = fmax(cm, ok[q] ? fabs(cg[lp * n + gcol(q, go)]) : 0.0);
+                // (under a per-group condition: both rows of the group are active, which is all grp_max's lane swap needs)
                 sb = grp_max<MP>(rowok ? fabs(bg[lp * m + go]) : 0.0);
                 sc = grp_max<MP>(cm);
                 const bool scaled = autoscale_lp(o.flags, sb, sc, 0.0);      // (the verdict of the load: the same maxima)
@@ -936,13 +952,10 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                     }
                 }
                 wave_lds_sync();
-                double axp[JB], adp[JB];
-                if (carried) w.template gram_one<false>(g, axp, adp); else w.template gram_one<true>(g, axp, adp);
+                double axg = 0.0, adg;
+                if (carried) w.template gram_one<false>(g, axg, adg); else w.template gram_one<true>(g, axg, adg);
                 wave_lds_sync();
-                if (grp == g) {
-                    Ax_ = (JB == 1) ? axp[0] : ((gl >> 4) ? axp[JB - 1] : axp[0]);
-                    Adt_ = (JB == 1) ? adp[0] : ((gl >> 4) ? adp[JB - 1] : adp[0]);
-                }
+                if (grp == g) { Ax_ = axg; Adt_ = adg; }
             }
             if (SL) {   // identity columns: x_slack and (d t)_slack go straight to row gl, d_slack onto the diagonal of M
                 Ax_ += ok[NCG - 1] ? x[NCG - 1] : 0.0;

@@ -23,24 +23,39 @@ struct GWaveH : GWave<MP, NP, SL> {
     using G_ = GeoG<MP, NP, SL>;
     static constexpr int G = G_::G, NCG = G_::NCG, NCD = G_::NCD, AS = G_::AS, MS = G_::MS;
 
-    // A'u1 and A'u2 in one pass over the image of A (pipelined like GWave::At_times)
+    // A'u1 and A'u2 in one pass over the image of A (pipelined like GWave::At_times; u1 and u2 from registers like there, or
+    // STAGED through the wave's staging area)
+    template <bool STAGED = false>
     __device__ __forceinline__ void At_times2(double u1, double u2, double (&o1)[NCG], double (&o2)[NCG]) const {
         const int g = this->ogl();     // opaque: see GWave::ogl()
-        this->stage[this->grp * MP + g] = u1;
-        this->stage[G * MP + this->grp * MP + g] = u2;
-        wave_lds_sync();
-        unsigned uba = lds_addr(this->stage + this->grp * MP);      // opaque: see GWave::A_times
-        asm volatile("" : "+v"(uba));
-        const __attribute__((address_space(3))) double* ub = (const __attribute__((address_space(3))) double*)(size_t)uba;
+        double ur1[2] = {u1, u1}, ur2[2] = {u2, u2};
+        const __attribute__((address_space(3))) double* ub = nullptr;
+        if constexpr (STAGED) {
+            this->stage[this->grp * MP + g] = u1;
+            this->stage[G * MP + this->grp * MP + g] = u2;
+            wave_lds_sync();
+            unsigned uba = lds_addr(this->stage + this->grp * MP);      // opaque: see GWave::A_times
+            asm volatile("" : "+v"(uba));
+            ub = (const __attribute__((address_space(3))) double*)(size_t)uba;
+        } else if constexpr (MP == 32) {   // (whole wave active)
+            ur1[0] = top_row_d(u1); ur1[1] = bottom_row_d(u1);
+            ur2[0] = top_row_d(u2); ur2[1] = bottom_row_d(u2);
+        }
         const double* ac = this->Aimg + g;
         constexpr int RB = PYCLLP_HSD_AT_RB, NB = MP / RB;
         double a0[RB][NCD], a1[RB][NCD], u0[RB][2], u1_[RB][2];
 #define AT_LOAD(A_, U_, I0)                                                                     \
-    _Pragma("unroll") for (int ii = 0; ii < RB; ii++) {                                         \
-        U_[ii][0] = ub[(I0) + ii + tok];                                                        \
-        U_[ii][1] = ub[G * MP + (I0) + ii + tok];                                               \
-        _Pragma("unroll") for (int q = 0; q < NCD; q++) A_[ii][q] = ac[((I0) + ii) * AS + MP * q + tok]; \
-    }
+    static_for<0, RB>([&](auto ic_) {                                                           \
+        constexpr int ii = decltype(ic_)::value, i_ = (I0) + ii;                                \
+        if constexpr (STAGED) {                                                                 \
+            U_[ii][0] = ub[i_ + tok];                                                           \
+            U_[ii][1] = ub[G * MP + i_ + tok];                                                  \
+        } else {                                                                                \
+            U_[ii][0] = row_bcast<(i_ & 15)>(ur1[i_ >> 4]);                                     \
+            U_[ii][1] = row_bcast<(i_ & 15)>(ur2[i_ >> 4]);                                     \
+        }                                                                                       \
+        _Pragma("unroll") for (int q = 0; q < NCD; q++) A_[ii][q] = ac[i_ * AS + MP * q + tok]; \
+    });
 #define AT_USE(A_, U_)                                                                          \
     _Pragma("unroll") for (int ii = 0; ii < RB; ii++) {                                         \
         asm volatile("" : "+v"(U_[ii][0]));                                                     \
@@ -71,7 +86,7 @@ struct GWaveH : GWave<MP, NP, SL> {
         });
 #undef AT_LOAD
 #undef AT_USE
-        wave_lds_sync();
+        if constexpr (STAGED) wave_lds_sync();
     }
 
     // (s, t) <- (L D L')^-1 (s, t): GWave::fwd_back for two right-hand sides, the two dependency chains interleaved
@@ -100,7 +115,7 @@ struct GWaveH : GWave<MP, NP, SL> {
         } else {
             const bool top = gl < 16;
             if (top) subst15_up2(s, t, lf);
-            const double so = swz_xor16_d(s), to = swz_xor16_d(t);
+            const double so = top_row_d(s), to = top_row_d(t);          // (outside the branches: both rows active)
             if (!top) {
                 s -= dot16_bcast(so, lf); t -= dot16_bcast(to, lf);
                 subst15_up2(s, t, lf + 16);
@@ -119,7 +134,7 @@ struct GWaveH : GWave<MP, NP, SL> {
         } else {
             const bool top = gl < 16;
             if (!top) subst15_down2(s, t, lb + 16);
-            const double so = swz_xor16_d(s), to = swz_xor16_d(t);
+            const double so = bottom_row_d(s), to = bottom_row_d(t);    // (outside the branches: both rows active)
             if (top) {
                 s -= dot16_bcast(so, lb + 16); t -= dot16_bcast(to, lb + 16);
                 subst15_down2(s, t, lb);
@@ -381,13 +396,10 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                     }
                 }
                 wave_lds_sync();
-                double axp[JB], adp[JB];
-                w.gram_one(g, axp, adp);
+                double axg, adg;
+                w.gram_one(g, axg, adg);
                 wave_lds_sync();
-                if (grp == g) {
-                    Adc_ = (JB == 1) ? axp[0] : ((go >> 4) ? axp[JB - 1] : axp[0]);
-                    Adr_ = (JB == 1) ? adp[0] : ((go >> 4) ? adp[JB - 1] : adp[0]);
-                }
+                if (grp == g) { Adc_ = axg; Adr_ = adg; }
             }
             if (SL) {
                 Adc_ += d[NCG - 1] * c[NCG - 1];
@@ -438,7 +450,9 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         if (fused) { pv = fr[0]; qv = fr[1]; w.backward2(pv, qv, rdiag); }
         else w.fwd_back2(pv, qv, rdiag);
         double ap[NCG], aq[NCG], dx[NCG], d[NCG], wv[NCG];
-        w.At_times2(pv, qv, ap, aq);
+        // (the (32, 128) kernel without the identity tail alone keeps u1, u2 through the staging area: 0 -> 3 spilt registers otherwise)
+        constexpr bool AT_STAGED = MP == 32 && NP == 128 && !SL;
+        w.template At_times2<AT_STAGED>(pv, qv, ap, aq);
         double dsum = 0.0, nsum = 0.0;
 #pragma unroll
         for (int q = 0; q < NCG; q++) {

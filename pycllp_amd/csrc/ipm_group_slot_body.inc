@@ -324,15 +324,12 @@
                     }
                 }
                 wave_lds_sync();
-                double axp[JB], adp[JB];
+                double axg, adg;
                 if constexpr (PA) w.Aimg = areas + g * P_::AREA;       // group g's matrix (wave-uniform)
-                w.template gram_one<true, true>(g, axp, adp);
+                w.template gram_one<true, true>(g, axg, adg);
                 if constexpr (PA) w.Aimg = own_area;
                 wave_lds_sync();
-                if (grp == g) {
-                    Ax_ = (JB == 1) ? axp[0] : ((gl >> 4) ? axp[JB - 1] : axp[0]);
-                    Adt_ = (JB == 1) ? adp[0] : ((gl >> 4) ? adp[JB - 1] : adp[0]);
-                }
+                if (grp == g) { Ax_ = axg; Adt_ = adg; }
             }
             if (SL) {   // identity columns: x_slack and (d t~)_slack go straight to row gl, d_slack onto the diagonal of M
                 Ax_ += act(NCG - 1) ? x[NCG - 1] : 0.0;

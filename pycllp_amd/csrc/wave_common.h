@@ -138,18 +138,12 @@ struct DevOpts {
 #define STAMP_FLUSH(o, wid)
 #endif
 
-// ---- DPP / swizzle helpers -------------------------------------------------------------------------------------
+// ---- DPP helpers (the exchanges across 16-lane rows are the lane swaps further down) -------------------------------------------------------------------------------------
 template <int CTRL>
 __device__ __forceinline__ double dpp_d(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
     hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double swz_xor16_d(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_ds_swizzle(lo, 0x401F);
-    hi = __builtin_amdgcn_ds_swizzle(hi, 0x401F);
     return __hiloint2double(hi, lo);
 }
 // compile-time loop (DPP controls must be immediates)
@@ -459,6 +453,49 @@ __device__ __forceinline__ double quad_sum(double v) {
     auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
     auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
     return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
+}
+// Lane swaps move ACTIVE lanes only: v_permlane16_swap needs both 16-lane rows of a 32-lane group in EXEC, v_permlane32_swap the
+// whole wave.  Every call site says which it has.  They are VALU instructions: no LDS, no lgkmcnt.
+// a and b are partial sums per 16-lane row: the sum of a over the four rows arrives in rows 0 and 2, that of b in rows 1 and 3.
+// Per lane (own + lane ^ 16) + (lane ^ 32) with operands commuted: the bits of two __shfl_xor stages.  Whole wave.
+__device__ __forceinline__ double quad_sum2(double a, double b) {
+    auto l = __builtin_amdgcn_permlane16_swap(__double2loint(a), __double2loint(b), false, false);   // [0] = rows (a0, b0, a2, b2)
+    auto h = __builtin_amdgcn_permlane16_swap(__double2hiint(a), __double2hiint(b), false, false);   // [1] = rows (a1, b1, a3, b3)
+    const double v = __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
+}
+// v of the top / of the bottom 16-lane row of the caller's 32-lane group, in both rows ([0] = rows (0, 0, 2, 2), [1] = rows
+// (1, 1, 3, 3) of a self-swap).  Both rows of the group active.
+__device__ __forceinline__ double top_row_d(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return __hiloint2double(b[0], a[0]);
+}
+__device__ __forceinline__ double bottom_row_d(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return __hiloint2double(b[1], a[1]);
+}
+// v of the top row + v of the bottom row / the larger of the two, in both rows: [0] and [1] of one self-swap, the last stage of
+// a reduction over a 32-lane group.  The swap overwrites both operands, so it costs two copies more than a ds_swizzle pair
+// (+4 vector instructions, -2 LDS instructions and their wait): what that buys is latency, 42 against 73 cycles on a dependent
+// path (tools/dev/ubench_xchg.hip, profiles/lane_swaps).  Both rows of the group active.
+__device__ __forceinline__ double row_pair_sum(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
+}
+__device__ __forceinline__ double row_pair_max(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return fmax(__hiloint2double(b[0], a[0]), __hiloint2double(b[1], a[1]));
 }
 // sum over the 16 lanes of each DPP row (identical inside the row)
 __device__ __forceinline__ double row_sum(double v) {
