@@ -186,6 +186,8 @@ struct GWave {
     // The sweep stores L column by column and carries the first solve's right-hand side (factor_dpp_fwd) where that is free:
     // the (32, 128) shapes have neither the address registers nor room for the carried values (10-19 registers spilt with them).
     static constexpr bool CARRY = COLB || MP == 16;
+    // The sweep shares the rank-1 updates of the bottom-right 16 x 16 block between both DPP rows of the group (factor_sweep).
+    static constexpr bool SPLIT = MP == 32;
     unsigned rb[ROWB ? 16 : 1];   // ... and of the sixteen 16-byte pairs of the lane's own ROW (load_own_row), swizzle included
     unsigned xb[COLB ? 16 : 1];   // MP = 32: LDS byte address of slab entry (row c, column gl), c < 16, swizzle included: entry (k, gl) of the
                           // factor's column layout is at xb[k & 15] + 256 (k & 16).  Kernel-lifetime values (16 registers, which the kernel
@@ -220,6 +222,94 @@ struct GWave {
         for (int p2 = 0; p2 < MP / 2; p2++) {
             const double2_t t = rp[p2 ^ g15];
             out[2 * p2] = t[0]; out[2 * p2 + 1] = t[1];
+        }
+    }
+
+    // The row as the SPLIT sweep wants it.  Bottom lanes (gl >= 16): load_own_row.  Top lane t: its own row, except that W[24 + s],
+    // s = 0 .. 7 -- don't-care values of the upper triangle there -- take M[R][16 + s] of row R = 16 + (t ^ 8), the half of the
+    // bottom-right block that the lane updates for the bottom lane t ^ 8.  Pair 8 + q, q < 4, of row R sits at pair
+    // (8 + q) ^ (R & 15) = q ^ t of that row: the address of the lane's own pair 12 + q plus ONE per-lane offset (the rows are
+    // R - t = 24 or 8 apart, and (12 + q) ^ t - (q ^ t) = 12 - 2 (t & 12) whatever q < 4 is), formed here and not held.
+    // backward() keeps load_own_row: the top lanes use lb[16 .. 31] there.
+    // (Why not rb[q] + 256 (R - t), which needs no swizzle term: the bottom lanes want rb[12 + q], so that form is a select between
+    // two address registers per pair; this one is an add of a value that is 0 in the bottom lanes.)
+    // The three helpers below are that offset in the two address forms, shared with merge_through_slab.  Bit arithmetic on the
+    // opaque g, not selects between constants: those are loop invariants to the compiler, which gives each a register for the
+    // whole kernel, and the headline kernel has none to spare.
+    __device__ __forceinline__ static unsigned top_lanes(int g) { return (((unsigned)g >> 4) & 1u) - 1u; }   // all ones in the top lanes, 0 in the bottom lanes
+    // ROWB: bytes from rb[12 + q] to pair 8 + q of row R: 256 (R - t) - 16 (12 - 2 (t & 12)), R - t = 24 - 2 (t & 8); 0 in the bottom lanes
+    __device__ __forceinline__ static unsigned split_off(int g) {
+        return (5952u - (((unsigned)g & 8u) << 9) + (((unsigned)g & 12u) << 5)) & top_lanes(g);
+    }
+    // pointer form: 16-byte pairs from the own row to row R, and the swizzle term of pairs 12 .. 15 ((p2 ^ 12) ^ t = q ^ t for p2 = 12 + q)
+    __device__ __forceinline__ static unsigned split_row(int g) { return ((24u - 2u * ((unsigned)g & 8u)) * (unsigned)(MS / 2)) & top_lanes(g); }
+    __device__ __forceinline__ static int split_swz(int g) { return (g & 15) ^ (int)(12u & top_lanes(g)); }
+    template <bool SP = SPLIT>
+    __device__ __forceinline__ void load_row_for_sweep(double (&out)[MP]) const {
+        if constexpr (!SP) {
+            load_own_row(out);
+        } else {
+            typedef double double2_t __attribute__((ext_vector_type(2)));
+            const int g = ogl();
+            if constexpr (ROWB) {
+                const unsigned off = split_off(g);
+#pragma unroll
+                for (int p2 = 0; p2 < MP / 2; p2++) {
+                    const double2_t t = *(const __attribute__((address_space(3))) double2_t*)(size_t)(rb[p2] + (p2 >= 12 ? off : 0u));
+                    out[2 * p2] = t[0]; out[2 * p2 + 1] = t[1];
+                }
+            } else {
+                const double2_t* rp = (const double2_t*)(slab + g * MS);
+                const int g15 = g & 15;
+                const double2_t* rs = rp + split_row(g);   // row R (top lanes)
+                const int g15s = split_swz(g);
+#pragma unroll
+                for (int p2 = 0; p2 < MP / 2; p2++) {
+                    const double2_t t = p2 >= 12 ? rs[p2 ^ g15s] : rp[p2 ^ g15];
+                    out[2 * p2] = t[0]; out[2 * p2 + 1] = t[1];
+                }
+            }
+        }
+    }
+
+    // The merge behind column 15 of the SPLIT sweep: every lane puts its W[24 .. 31] back where load_row_for_sweep took them from
+    // (the top lanes: columns 16 .. 23 of row R; the bottom lanes: columns 24 .. 31 of their own row, which nobody reads), then
+    // re-reads columns 16 .. 23 of its own row into W[16 .. 23]: four ds_write_b128 and four ds_read_b128 at addresses that
+    // exist already, no EXEC switch.  Rows 16 .. 31 of the slab are dead between the row load and the stores of columns 16 .. 31
+    // (columns 0 .. 15 of L go to rows 0 .. 15; the (32, 128) shapes store L behind the sweep).  The top lanes receive
+    // don't-care values, as before.
+    __device__ __forceinline__ void merge_through_slab(double (&W)[MP]) const {
+        typedef double double2_t __attribute__((ext_vector_type(2)));
+        const int g = ogl();
+        if constexpr (ROWB) {
+            const unsigned off = split_off(g);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                double2_t t; t[0] = W[24 + 2 * q]; t[1] = W[25 + 2 * q];
+                *(__attribute__((address_space(3))) double2_t*)(size_t)(rb[12 + q] + off) = t;
+            }
+            wave_lds_sync();
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const double2_t t = *(const __attribute__((address_space(3))) double2_t*)(size_t)rb[8 + q];
+                W[16 + 2 * q] = t[0]; W[17 + 2 * q] = t[1];
+            }
+        } else {
+            double2_t* rp = (double2_t*)(slab + g * MS);
+            const int g15 = g & 15;
+            double2_t* rs = rp + split_row(g);
+            const int g15s = split_swz(g);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                double2_t t; t[0] = W[24 + 2 * q]; t[1] = W[25 + 2 * q];
+                rs[(12 + q) ^ g15s] = t;
+            }
+            wave_lds_sync();
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const double2_t t = rp[(8 + q) ^ g15];
+                W[16 + 2 * q] = t[0]; W[17 + 2 * q] = t[1];
+            }
         }
     }
 
@@ -446,7 +536,7 @@ struct GWave {
     // exactly as the reference does -- when nothing bites the two are the same arithmetic.  RELF (HSD kernel): the pivot floor of
     // column j is fl[j] (LDS, written by the caller: pivot_floor^2 |M_jj|) instead of the scalar floor_.
     // (Rounds 1-2 also carried factor<GUARD>, the round-1 sweep that handed every raw column through LDS; nothing called it.)
-    // No LDS in the sweep.  Lane gl keeps row gl of the trailing matrix in W; by symmetry
+    // No LDS in a column's updates (the SP sweep, below, has one round trip behind column 15).  Lane gl keeps row gl of the trailing matrix in W; by symmetry
     // the entry M[j][k] that column j's update of W[k] needs is the column-j entry u = W[j] of LANE k, i.e. a broadcast
     // inside the lane's 16-lane DPP row -- which the DP ALU does inside the FMA itself (v_fmac_f64_dpp row_newbcast, see
     // wave_common.h): one instruction per trailing entry, where factor() above pays an LDS broadcast read (496 per
@@ -486,16 +576,38 @@ struct GWave {
     // operations, and the shipped code has one ds_write_b64 behind every column (llvm-objdump -d of the library's gfx950 code object).  Correctness
     // does not depend on it -- a store that sank would still precede the final sync -- only the overlap does; check the
     // disassembly after a compiler change.
-    template <bool RELF = false>
+    //
+    // SP (MP = 32): the split sweep.  The rank-1 updates of the bottom-right 16 x 16 block M22 during columns j < 16 are useful in
+    // the bottom DPP row only, and there only in the lower triangle.  With SP the top row of the group works as a rotated clone of
+    // the bottom row during these columns and carries half of M22's columns: eight block FMAs per column in place of sixteen.
+    //   Lane map (t: index inside the 16-lane row).  Bottom lane i keeps row 16 + i as before, but only its columns 24 .. 31
+    //   (W[24 + s] = M[16 + i][24 + s]) are updated during columns j < 16.  Top lane t keeps its own row's left half W[0 .. 15] as
+    //   before; its W[24 + s], s = 0 .. 7, don't-care values until now, hold M[R][16 + s] of row R = 16 + (t ^ 8)
+    //   (load_row_for_sweep).
+    //   Column j < 16.  The self-swap of u = W[j] that yields the top row's u in both rows (the pivot chain's operand) also yields
+    //   the bottom row's u in both rows (both_rows_d).  In the top rows that copy is rotated by 8 lanes (ror8_top_d): X is the
+    //   lane's own u in bottom lane i and the u of row R in top lane t.  X rD has the bits of the multiplier l that the masked
+    //   chain forms in the bottom lane of row R (same two factors; rD is one value per group).  Then, in all lanes and without
+    //   an EXEC switch, W[24 + s] -= (X of lane 8 + s of the DPP row) * (X rD): lane 8 + s of the bottom row's X is u of row
+    //   24 + s, so bottom lane i updates column 24 + s of its row; lane 8 + s of the top row's X is u of row 16 + s, so top lane t
+    //   updates column 16 + s of row R (chain_half_neg).  Every entry of M22 gets the sixteen FMAs it got, in column order, on
+    //   the same two multiplicands: the lower triangle of the block is what the plain sweep computes, bit for bit.  Nothing is
+    //   added to the pivot's dependent path: the rotation, the multiply and the eight FMAs follow the chain of W[0 .. 15].
+    //   Behind column 15 the halves meet again through rows 16 .. 31 of the slab, which are dead at that point (merge_through_slab:
+    //   4 + 4 128-bit LDS operations per lane; measured against 16 rotations and 16 v_permlane16_swap in registers, which need no
+    //   LDS but cost 0.011 ms of the 0.089 ms this split gains on 65 536 LPs of 32 x 64, profiles/sweep_split).  Columns 16 .. 31,
+    //   the carried forward substitution, the column stores of L and the guard's running maximum are those of the plain sweep.
+    // A kernel takes SP where it costs no scratch and no spilt register (its `SPLIT` constant, next to `CARRY`).
+    template <bool RELF = false, bool SP = SPLIT>
     __device__ __forceinline__ bool factor_dpp(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
                                                const double* fl = nullptr) const {
-        return factor_sweep<RELF, 0>(W, beta2, floor_, live, rdiag, fl, nullptr);
+        return factor_sweep<RELF, 0, SP>(W, beta2, floor_, live, rdiag, fl, nullptr);
     }
     // r <- L^-1 r for the NR right-hand sides r (lane = row) along with the factorisation; the caller goes on with backward()
-    template <bool RELF = false, int NR>
+    template <bool RELF = false, bool SP = SPLIT, int NR>
     __device__ __forceinline__ bool factor_dpp_fwd(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
                                                    double (&r)[NR], const double* fl = nullptr) const {
-        return factor_sweep<RELF, NR>(W, beta2, floor_, live, rdiag, fl, r);
+        return factor_sweep<RELF, NR, SP>(W, beta2, floor_, live, rdiag, fl, r);
     }
     // operation `op` (0 .. 31) of the bottom DPP row's part of the carried forward substitution, MP = 32 (see above)
     template <int OP, int NR>
@@ -511,7 +623,7 @@ struct GWave {
             for (int i = 0; i < NR; i++) fwd_step<OP - 17, 0xA>(r[i], W[OP - 1]);    // step of column OP - 1
         }
     }
-    template <bool RELF, int NR>
+    template <bool RELF, int NR, bool SP>
     __device__ __forceinline__ bool factor_sweep(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
                                                  const double* fl, double* r) const {
         rdiag = 1.0;
@@ -532,7 +644,9 @@ struct GWave {
             constexpr int j = decltype(jc)::value;
             const double u = W[j];
             double src = u;        // the u whose lane j % 16 is the pivot row as seen from this lane's DPP row
-            if constexpr (MP == 32 && j < 16) src = top_row_of(u);
+            double ub = u;         // SPLIT: the bottom row's u in both rows, the other half of the same swap
+            if constexpr (SP && j < 16) src = both_rows_d(u, ub);
+            else if constexpr (MP == 32 && j < 16) src = top_row_of(u);
             const double piv = bcast64<j % 16>(src);
             if constexpr (NR > 0 && MP == 32 && j > 16) fwd_bottom_op<2 * (j - 16) - 1, NR>(W, r, so, acc);
             const double aD = RELF ? max_abs<false>(piv, fl[j]) : max_abs<true>(piv, floor_);
@@ -552,9 +666,12 @@ struct GWave {
                 chain_step_exec<j, MB_, MB_, 1, ONE_, ONE_>(W, 0.0, rD, l, ymax, rdiag);
             } else if constexpr (j < 16) {
                 chain_step_exec<j, MB_, MB_, 0, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[0]), src, rD, l, ymax, rdiag);
-                // the bottom-right block's columns, in ALL lanes: what the top row's lanes hold in W[16..31] is never read (upper
-                // triangle; overwritten with 0 when its column comes), so the EXEC mask of rounds 2-3 only cost its switches
-                chain_all_neg(*reinterpret_cast<double (*)[16]>(&W[16]), W[j], l);
+                // the bottom-right block's columns.  SP: half of them per DPP row (see above; the top lanes' W[24 .. 31] are M22's
+                // columns 16 .. 23 of row R).  Plain: all sixteen in ALL lanes -- what the top row's lanes hold in W[16..31] is then
+                // never read (upper triangle; overwritten with 0 when its column comes), so the EXEC mask of rounds 2-3 only cost
+                // its switches
+                if constexpr (SP) chain_half_neg(*reinterpret_cast<double (*)[8]>(&W[24]), ror8_top_d(ub), rD);
+                else chain_all_neg(*reinterpret_cast<double (*)[16]>(&W[16]), W[j], l);
             } else {
                 chain_step_exec<j - 16, MB_, MB_, 1, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[16]), 0.0, rD, l, ymax, rdiag);
             }
@@ -569,6 +686,7 @@ struct GWave {
                     for (int i = 0; i < NR; i++) so[i] = top_row_d(r[i]);   // (whole wave, like top_row_of above)
                 }
             }
+            if constexpr (SP && j == 15) merge_through_slab(W);
         });
         if constexpr (NR > 0 && MP == 32) fwd_bottom_op<31, NR>(W, r, so, acc);
         const bool viol = live && (ymax > beta2);
@@ -975,6 +1093,8 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         // `fused` is a run-time flag, not `if constexpr`: whether the guarded path replaces the factor is known only when the sweep
         // returns, so both back_after_sweep() and the whole fwd_back() are inlined at the first solve of a carrying kernel
         bool fused = CARRY;      // (wave-uniform) ... unless the guarded path replaced the factor
+        // the split sweep (GWave::factor_sweep) wherever it costs no register: the same kernel as above goes from 2 to 10 spilt with it
+        constexpr bool SPLIT = GWave<MP, NP, SL>::SPLIT && !(PC && SL && MP == 32 && NP == 96);
         {
             double W[MP];
             const int gd = w.ogl();
@@ -984,14 +1104,14 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 if (!rowok) w.slab[G_::sidx(gd, gd)] = 1.0;
                 wave_lds_sync();
             }
-            w.load_own_row(W);
+            w.template load_row_for_sweep<SPLIT>(W);
             double diag = rowok ? w.slab[G_::sidx(gd, gd)] : 0.0;
             const double beta2 = grp_max<MP>(fabs(diag));
             wave_lds_sync();
             STAMP(3)
             bool redo;
-            if constexpr (CARRY) redo = w.factor_dpp_fwd(W, beta2, o.pivot_floor, live, rdiag, fs);
-            else redo = w.factor_dpp(W, beta2, o.pivot_floor, live, rdiag);
+            if constexpr (CARRY) redo = w.template factor_dpp_fwd<false, SPLIT>(W, beta2, o.pivot_floor, live, rdiag, fs);
+            else redo = w.template factor_dpp<false, SPLIT>(W, beta2, o.pivot_floor, live, rdiag);
             if (redo || (o.flags & PYCLLP_FLAG_FORCE_GUARD_PATH)) {
                 // the Nocedal-Wright guard would have bitten somewhere: re-form M and factor with the guard applied
                 double Ax2, Adt2;

@@ -415,6 +415,7 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         constexpr bool CARRY = GWave<MP, NP, SL>::CARRY;
         double fr[2] = {pv, qv};   // both right-hand sides ride through the sweep (see ipm_group_kernel)
         bool fused = CARRY;
+        constexpr bool SPLIT = GWave<MP, NP, SL>::SPLIT;   // the split sweep (GWave::factor_sweep): no HSD kernel pays registers for it
         {
             double W[MP];
             const int go = w.ogl();
@@ -422,7 +423,7 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 if (!rowok) w.slab[G_::sidx(go, go)] = 1.0;
                 wave_lds_sync();
             }
-            w.load_own_row(W);
+            w.template load_row_for_sweep<SPLIT>(W);
             double diag = rowok ? w.slab[G_::sidx(go, go)] : 0.0;
             const double beta2 = grp_max<MP>(fabs(diag));
             // pivot floor of column j: pivot_floor^2 |M_jj| -- relative to the pivot's own original diagonal entry (see the
@@ -436,8 +437,8 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             wave_lds_sync();
             // (a software-pipelined sweep paid 1.7 % here only while this kernel ran one wave per SIMD; see GWave::factor_dpp)
             bool redo;
-            if constexpr (CARRY) redo = w.template factor_dpp_fwd<true>(W, beta2, 0.0, live, rdiag, fr, fl);
-            else redo = w.template factor_dpp<true>(W, beta2, 0.0, live, rdiag, fl);
+            if constexpr (CARRY) redo = w.template factor_dpp_fwd<true, SPLIT>(W, beta2, 0.0, live, rdiag, fr, fl);
+            else redo = w.template factor_dpp<true, SPLIT>(W, beta2, 0.0, live, rdiag, fl);
             if (redo || (o.flags & PYCLLP_FLAG_FORCE_GUARD_PATH)) {
                 double t1, t2;
                 do_gram(t1, t2);

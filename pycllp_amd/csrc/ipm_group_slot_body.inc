@@ -358,6 +358,9 @@
         constexpr bool CARRY = GWave<MP, NP, SL>::CARRY;
         double fs[1] = {rhs};     // the first solve's right-hand side rides through the sweep (see ipm_group_kernel)
         bool fused = CARRY;
+        // the split sweep (GWave::factor_sweep); the bounded per-problem-A kernel at (32, 96) alone keeps the plain one: 0 -> 4 spilt
+        // VGPRs with it
+        constexpr bool SPLIT = GWave<MP, NP, SL>::SPLIT && !(BD && PA && MP == 32 && NP == 96);
         {
             double W[MP];
             const int gd = w.ogl();
@@ -365,13 +368,13 @@
                 if (!rowok) w.slab[G_::sidx(gd, gd)] = 1.0;
                 wave_lds_sync();
             }
-            w.load_own_row(W);
+            w.template load_row_for_sweep<SPLIT>(W);
             double diag = rowok ? w.slab[G_::sidx(gd, gd)] : 0.0;
             const double beta2 = grp_max<MP>(fabs(diag));
             wave_lds_sync();
             bool redo;
-            if constexpr (CARRY) redo = w.factor_dpp_fwd(W, beta2, o.pivot_floor, work, rdiag, fs);
-            else redo = w.factor_dpp(W, beta2, o.pivot_floor, work, rdiag);
+            if constexpr (CARRY) redo = w.template factor_dpp_fwd<false, SPLIT>(W, beta2, o.pivot_floor, work, rdiag, fs);
+            else redo = w.template factor_dpp<false, SPLIT>(W, beta2, o.pivot_floor, work, rdiag);
             if (redo || (o.flags & PYCLLP_FLAG_FORCE_GUARD_PATH)) {
                 double Ax2, Adt2;
                 do_gram(Ax2, Adt2);

@@ -253,6 +253,24 @@ __device__ __forceinline__ void chain_all_neg(double (&Wd)[16], double src, doub
                  : "+v"(Wd[0]), "+v"(Wd[1]), "+v"(Wd[2]), "+v"(Wd[3]), "+v"(Wd[4]), "+v"(Wd[5]), "+v"(Wd[6]), "+v"(Wd[7]), "+v"(Wd[8]), "+v"(Wd[9]), "+v"(Wd[10]), "+v"(Wd[11]), "+v"(Wd[12]), "+v"(Wd[13]), "+v"(Wd[14]), "+v"(Wd[15])
                  : "v"(src), "v"(l));
 }
+// Half of that block per DPP row (the split sweep of GWave::factor_sweep): Wd[s] -= (x of lane 8 + s) * (x rD), s = 0 .. 7, in
+// ALL lanes.  x rD has the bits of the multiplier chain_col forms from the same two factors.  The multiply and the s_nop stand
+// between a DPP move that wrote x just before the statement and the first read of x through DPP (two wait states).
+__device__ __forceinline__ void chain_half_neg(double (&Wd)[8], double x, double rD) {
+    double lx;
+    asm volatile("v_mul_f64 %8, %9, %10\n\t"
+                 "s_nop 0\n\t"
+                 "v_fmac_f64_dpp %0, %9, -%8 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_fmac_f64_dpp %1, %9, -%8 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_fmac_f64_dpp %2, %9, -%8 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_fmac_f64_dpp %3, %9, -%8 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_fmac_f64_dpp %4, %9, -%8 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_fmac_f64_dpp %5, %9, -%8 row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_fmac_f64_dpp %6, %9, -%8 row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_fmac_f64_dpp %7, %9, -%8 row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
+                 : "+v"(Wd[0]), "+v"(Wd[1]), "+v"(Wd[2]), "+v"(Wd[3]), "+v"(Wd[4]), "+v"(Wd[5]), "+v"(Wd[6]), "+v"(Wd[7]), "=&v"(lx)
+                 : "v"(x), "v"(rD));
+}
 // max(|a|, b) as ONE instruction (fmax(fabs(a), b) costs a canonicalising v_max_f64 a, a first); BS: b is wave-uniform (SGPR)
 template <bool BS>
 __device__ __forceinline__ double max_abs(double a, double b) {
@@ -480,6 +498,22 @@ __device__ __forceinline__ double bottom_row_d(double v) {
     auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
     auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
     return __hiloint2double(b[1], a[1]);
+}
+// both halves of ONE self-swap: returns top_row_d(v), `bot` receives bottom_row_d(v).  Both rows of the group active.
+__device__ __forceinline__ double both_rows_d(double v, double& bot) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    bot = __hiloint2double(b[1], a[1]);
+    return __hiloint2double(b[0], a[0]);
+}
+// v rotated by 8 lanes inside the TOP 16-lane row of every 32-lane group (lane t takes lane t ^ 8's); the bottom rows keep
+// theirs: two v_mov_b32_dpp row_ror:8 row_mask:0x5, in place
+__device__ __forceinline__ double ror8_top_d(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x128, 0x5, 0xF, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x128, 0x5, 0xF, false);
+    return __hiloint2double(hi, lo);
 }
 // v of the top row + v of the bottom row / the larger of the two, in both rows: [0] and [1] of one self-swap, the last stage of
 // a reduction over a 32-lane group.  The swap overwrites both operands, so it costs two copies more than a ds_swizzle pair
