@@ -125,6 +125,10 @@ extern "C" {
                                         identity (diagnostic: results must agree to rounding)                    */
 #define PYCLLP_FLAG_FORCE_GUARD_PATH 4 /* diagnostic: always run the guarded (cold) LDL' path of the group
                                           kernel; results must not change when the guard is inactive */
+#define PYCLLP_FLAG_GENERIC_SHAPE 512 /* diagnostic: pycllp_hip_dense_solve keeps the generic instantiation of the slack-aware
+                                         lane-group kernel where the LP fills a compiled shape exactly (m = MP, n = NP) and a
+                                         full-shape instantiation would serve it; the results are the same bits.  The other
+                                         entries have no such instantiation and ignore the flag. */
 #define PYCLLP_FLAG_BLOCK_KERNEL 64 /* sparse solver: use the workgroup-per-LP kernel (ipm_block_kernel) even where the
                                        register-resident wavefront-per-LP kernel covers the problem (diagnostic / A-B runs;
                                        results agree to rounding)                                                  */
@@ -270,6 +274,11 @@ int pycllp_hip_dense_kernel_kind(const pycllp_hip_dense *handle);
  * Newton step); (0, 0, 0) before the first launch.  A handle handed to the sparse path's kernels: *a, *b = the (MB, NQ) of
  * pycllp_hip_sparse_variant_info and *slack = -1. */
 int pycllp_hip_dense_variant_info(const pycllp_hip_dense *handle, int *a, int *b, int *slack);
+
+/* 1 when the last launch on this handle ran a full-shape instantiation of a lane-group kernel -- pycllp_hip_dense_solve on
+ * the slack-aware path, without PYCLLP_FLAG_HSD or PYCLLP_FLAG_PREDCORR, for an LP whose m and n (equality form) are exactly the
+ * (MP, NP) of a compiled shape, e.g. 32 x 64 -> (32, 96), without PYCLLP_FLAG_GENERIC_SHAPE -- else 0. */
+int pycllp_hip_dense_full_shape(const pycllp_hip_dense *handle);
 
 /* pycllp_hip_sparse_plan_info of a handle handed to the sparse path's kernels; (0, 0, -1, -1) on the lane-group kernels. */
 int pycllp_hip_dense_plan_info(const pycllp_hip_dense *handle, int *wgpc, int *bnc, int *factor_in_lds, int *a_in_lds);

@@ -16,6 +16,7 @@ FLAG_HSD = 32
 FLAG_BLOCK_KERNEL = 64
 FLAG_PREDCORR = 128
 FLAG_AUTOSCALE_PER_LP = 256
+FLAG_GENERIC_SHAPE = 512
 
 
 class Opts(ctypes.Structure):
@@ -49,6 +50,7 @@ SIGNATURES = (
     ("pycllp_hip_dense_newton", [_p, _l, _p, _p, _p, _p, _p, _d, _p, _p, _O, _p], _i),
     ("pycllp_hip_dense_launch_info", [_p] + [_ip] * 5, _i), ("pycllp_hip_dense_kernel_kind", [_p], _i),
     ("pycllp_hip_dense_variant_info", [_p] + [_ip] * 3, _i), ("pycllp_hip_dense_plan_info", [_p] + [_ip] * 4, _i),
+    ("pycllp_hip_dense_full_shape", [_p], _i),
     ("pycllp_hip_dense_free", [_p], None),
     ("pycllp_hip_ldl", [_i, _l, _p, _p, _p, _i, _d, _d, _p], _i),
     ("pycllp_hip_ldl_solve", [_i, _l, _p, _p, _p, _i, _d, _d, _p], _i),
@@ -72,6 +74,17 @@ SIGNATURES = (
     ("pycllp_hip_general_to_bounded_batch", [_i, _i, _i, _l, _p, _i] + [_p] * 4 + [_l] + [_p] * 13 + [_p], _i),
 )
 EXPORTS = tuple(name for name, _, _ in SIGNATURES)
+# Entries that a library built from an earlier commit does not have.  Only a library named by PYCLLP_HIP_LIB (a diagnostic or
+# an earlier build, for A/B runs of two builds under one Python tree) may lack them: it loads without them, `has_entry` says so,
+# and what they report is then left out, never made up.  The product's own library must have every entry (AttributeError).
+LATER_ENTRIES = ("pycllp_hip_dense_full_shape",)
+_absent = set()
+
+
+def has_entry(name):
+    """Whether the loaded library exports ``name`` (False only for a LATER_ENTRIES symbol of a PYCLLP_HIP_LIB library)."""
+    lib()
+    return name not in _absent
 
 _lib = None
 
@@ -86,6 +99,9 @@ def lib():
             "g.build()'` or `make -C pycllp_amd/csrc` (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     for name, args, res in SIGNATURES:
+        if name in LATER_ENTRIES and os.environ.get("PYCLLP_HIP_LIB") and not hasattr(L, name):
+            _absent.add(name)
+            continue
         f = getattr(L, name)
         f.argtypes, f.restype = args, res
     if L.pycllp_hip_abi_version() != 1:

@@ -3,18 +3,20 @@
 // a matrix beyond them (m > 32 or n > 128) gets a sparse handle, whose entries and bodies are abi_sparse.hip's (host.h).
 #include "dense_tab.h"
 
-static void publish(pycllp_hip_dense* h, const LaunchPlan& p) {
+static void publish(pycllp_hip_dense* h, const LaunchPlan& p, bool full = false) {
     std::lock_guard<std::mutex> g(h->info_mu);
-    h->grid = p.grid; h->block = p.block; h->lds = p.lds; h->mp = p.mp; h->np = p.np; h->sl = p.sl;
+    h->grid = p.grid; h->block = p.block; h->lds = p.lds; h->mp = p.mp; h->np = p.np; h->sl = p.sl; h->full = full ? 1 : 0;
 }
 
-// Plans k for a.B LPs, launches it on a queue-ring slot (a.queue) and publishes the plan for launch_info
-static hipError_t run_group(pycllp_hip_dense* h, const DenseKernel& k, GroupPaArgs a, const DevOpts& o, hipStream_t st) {
+// Plans k for a.B LPs, launches it on a queue-ring slot (a.queue) and publishes the plan for launch_info.  full: k.launch is a
+// full-shape instantiation
+static hipError_t run_group(pycllp_hip_dense* h, const DenseKernel& k, GroupPaArgs a, const DevOpts& o, hipStream_t st,
+                            bool full = false) {
     const LaunchPlan p = k.plan(h->lim, a.B, o);
     return h->ring.run(st, [&](int* qhead) {
         a.queue = qhead;
         const hipError_t el = k.launch(a, p, o, st);
-        publish(h, p);
+        publish(h, p, full);
         return el;
     });
 }
@@ -157,14 +159,18 @@ int pycllp_hip_dense_solve(pycllp_hip_dense* h, long B, const double* b_dev, con
         return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve: the first-generation kernel (PYCLLP_FLAG_WAVE_KERNEL) has been removed");
     const Variant& v = kVariants[h->variant];
     const bool hsd = (o.flags & PYCLLP_FLAG_HSD) != 0, pc = (o.flags & PYCLLP_FLAG_PREDCORR) != 0;
-    const DenseKernel* k = hsd ? &v.solve_hsd : (pc ? &v.solve_pc : &v.solve_group);
+    DenseKernel k = hsd ? v.solve_hsd : (pc ? v.solve_pc : v.solve_group);
+    bool full = false;
     if (h->variant_sl >= 0 && !(o.flags & PYCLLP_FLAG_NO_SLACK_PATH)) {
         const SlackVariant& s = kSlackVariants[h->variant_sl];
-        k = hsd ? &s.solve_hsd : (pc ? &s.solve_pc : &s.solve_group);
+        k = hsd ? s.solve_hsd : (pc ? s.solve_pc : s.solve_group);
+        // an LP that fills the shape exactly goes to its full-shape instantiation, on the same plan
+        const dense_launch_fn f = (hsd || pc) ? nullptr : s.full_group;
+        if (f && h->m == s.mp && h->n == s.np && !(o.flags & PYCLLP_FLAG_GENERIC_SHAPE)) { k.launch = f; full = true; }
     }
     const GroupPaArgs a = {h->m, h->n, B, h->a_rm, b_dev, c_dev, nullptr, x_dev, y_dev, z_dev, nullptr, pobj_dev, dobj_dev,
                            status_dev, iters_dev, nullptr};
-    hipError_t e = run_group(h, *k, a, o, (hipStream_t)stream);
+    hipError_t e = run_group(h, k, a, o, (hipStream_t)stream, full);
     if (e != hipSuccess) return set_err((int)e, "solve kernel launch");
     return 0;
 }
@@ -267,6 +273,12 @@ int pycllp_hip_dense_variant_info(const pycllp_hip_dense* h, int* a, int* b, int
     if (b) *b = ran ? h->np : 0;
     if (slack) *slack = ran ? h->sl : 0;
     return 0;
+}
+
+int pycllp_hip_dense_full_shape(const pycllp_hip_dense* h) {
+    if (!h || h->sp) return 0;
+    std::lock_guard<std::mutex> g(h->info_mu);
+    return h->full;
 }
 
 int pycllp_hip_dense_plan_info(const pycllp_hip_dense* h, int* wgpc, int* bnc, int* factor_in_lds, int* a_in_lds) {

@@ -27,7 +27,13 @@ struct Variant {
     newton_launch_fn newton;
 };
 // slack-aware group kernels: (MP, NP) with NP - MP padded dense columns + the m identity columns
-struct SlackVariant { int mp, np; DenseKernel solve_group, solve_hsd, solve_pc, solve_bounded; };
+// full_group: the full-shape instantiation of solve_group, launched on its plan, for a matrix with m == mp and n == np
+// exactly; null where none was compiled (ipm_dense.hip full_group_kernel)
+struct SlackVariant {
+    int mp, np;
+    DenseKernel solve_group, solve_hsd, solve_pc, solve_bounded;
+    dense_launch_fn full_group;
+};
 
 // one row per lane-group shape of GROUP_SHAPES (group_pa.h), in its order: the first that covers (m, n) is used, in both tables
 extern const Variant kVariants[];

@@ -116,10 +116,11 @@ struct pycllp_hip_dense {
     double* pack = nullptr;
     double* a_rm = nullptr;   // row-major copy of A [m,n] for the group kernel
     QueueRing ring; // device work-queue heads of the group kernel
-    mutable std::mutex info_mu;   // guards grid/block/lds/mp/np/sl (what launch_info and variant_info report: the LAST launch)
+    mutable std::mutex info_mu;   // guards grid/block/lds/mp/np/sl/full (what launch_info and variant_info report: the LAST launch)
     int variant_sl = -1; // index into kSlackVariants when the last m columns of A are the identity, else -1
     int grid = 0, block = 0, lds = 0;
     int sl = -1;         // the last launch ran a kernel of the slack-aware table (1) or of the general one (0); -1: none yet
+    int full = 0;        // ... and that kernel was a full-shape instantiation (SlackVariant::full_group)
     DeviceLimits lim;
     struct pycllp_hip_sparse* sp = nullptr;   // LPs beyond the lane-group kernels (m <= 128, n <= 512): served by the sparse path's kernels
 };

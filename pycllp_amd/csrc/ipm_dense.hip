@@ -448,15 +448,22 @@ static LaunchPlan plan_group_pa(const DeviceLimits& d, long B, const DevOpts& o)
     return LaunchPlan{resident_blocks(B, wpb, resident), wpb * WAVE, (int)P::lds_bytes(wpb), MP, NP, SL ? 1 : 0};
 }
 
-template <int MP, int NP, bool SL, bool HSD = false, bool PC = false>
+template <int MP, int NP, bool SL, bool HSD = false, bool PC = false, bool FULL = false>
 static hipError_t launch_solve_group(const GroupPaArgs& a, const LaunchPlan& p, DevOpts o, hipStream_t st) {
-    auto kernel = HSD ? hsd_group_kernel<MP, NP, SL> : ipm_group_kernel<MP, NP, SL, PC>;
+    auto kernel = HSD ? hsd_group_kernel<MP, NP, SL> : ipm_group_kernel<MP, NP, SL, PC, FULL>;
     const hipError_t e = set_dyn_lds((const void*)kernel, p.lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, st, a.m, a.n, a.B, a.A, a.b, a.c, a.x, a.y, a.z, a.pobj,
                        a.dobj, a.status, a.iters, a.queue, o);
     return hipGetLastError();
 }
+
+// The full-shape instantiation of the plain slack-aware kernel (ipm_group_kernel's FULL, for an LP with m = MP and n = NP: no
+// padded column), launched on the generic instantiation's plan (same geometry).  A shape whose full-shape kernel had scratch
+// or a spilt VGPR, or was slower than the generic one, would get a null launcher, which abi_dense.hip skips, and be named
+// here: none (tools/kernel_resources.py, profiles/full_shape).
+template <int MP, int NP>
+constexpr dense_launch_fn full_group_kernel() { return launch_solve_group<MP, NP, true, false, false, true>; }
 
 // the bounded slack-aware kernel (ipm_group_slot.inc): planned with PYCLLP_WPB_BOUNDED waves per workgroup
 template <int MP, int NP>
@@ -485,7 +492,8 @@ static hipError_t launch_newton(const NewtonArgs& a, const LaunchPlan& p, DevOpt
       GROUP_KERNEL(MP, NP, false, true, false), GROUP_KERNEL(MP, NP, false, false, true), plan_newton<MP, NP>, launch_newton<MP, NP> },
 #define SLACK_VARIANT(MP, NP) \
     { MP, NP, GROUP_KERNEL(MP, NP, true, false, false), GROUP_KERNEL(MP, NP, true, true, false), \
-      GROUP_KERNEL(MP, NP, true, false, true), { plan_group<MP, NP, true, PYCLLP_WPB_BOUNDED>, launch_solve_bounded<MP, NP> } },
+      GROUP_KERNEL(MP, NP, true, false, true), { plan_group<MP, NP, true, PYCLLP_WPB_BOUNDED>, launch_solve_bounded<MP, NP> }, \
+      full_group_kernel<MP, NP>() },
 #define PA_PLAN(MP, NP) { MP, NP, 0, plan_group_pa<MP, NP, false> }, { MP, NP, 1, plan_group_pa<MP, NP, true> },
 // ... with upper bounds: the same rule, at most PYCLLP_WPB_BOUNDED waves per workgroup
 #define PABD_PLAN(MP, NP) { MP, NP, 1, plan_group_pa<MP, NP, true, GeoPA<GeoG<MP, NP, true>>::wpb_capped(PYCLLP_WPB_BOUNDED)> },

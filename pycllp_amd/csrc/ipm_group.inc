@@ -806,7 +806,19 @@ struct GWave {
 // factorisation of an iteration a predictor solve with mu = 0, the centering parameter from how far that step gets
 // (sigma = (gamma_a / gamma)^3), then the corrector solve with the second-order term dx_a dz_a; a second forward/back
 // substitution, A'u and A v per iteration buy ~27 % fewer iterations at the reference's step fraction (0.9), ~45 % at 0.99.
-template <int MP, int NP, bool SL, bool PC = false>
+// FULL = true (slack-aware kernels only): the instantiation for LPs that fill it exactly, m = MP and n = NP (so n - m = ND dense
+// columns), which the host guarantees (abi_dense.hip launches SlackVariant::full_group for no other LP).  No column is
+// padding then: every `ok[q]` is true, the selects on them fold away (35 v_cndmask of the (32, 96) kernel's text), and
+// the identity rows of a padded M are never written.  A select on a true condition is the identity: the results are those of
+// the generic instantiation, bit for bit (tests/test_full_shape.py).  `rowok`, m and n stay run-time values although they are
+// known as well: with `rowok` true -- even at the one select on the hot path, M's diagonal before the sweep -- or with m = MP
+// as a constant (which makes `rowok` one), the (32, 96) kernel spills 2-11 VGPRs (DESIGN section 13.8); as it stands no
+// full-shape kernel has scratch or a spilt VGPR.  Where a select stood between a product and a sum it also kept the two from
+// contracting into an fma; the two places of the plain step (gam, d_slack onto M's diagonal) pin the product for FULL.  That
+// rests on what the compiler contracts (DESIGN section 13.8); tests/test_full_shape.py holds the two texts together.  Plain
+// step only: the predictor-corrector text with FULL did not give the generic bits, for a reason not found, and is not built.
+// Without FULL the text is what it was, and so is every generic kernel's machine code.
+template <int MP, int NP, bool SL, bool PC = false, bool FULL = false>
 __global__ void __launch_bounds__(PYCLLP_WPB * 64)
 ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const double* __restrict__ bg,
                  const double* __restrict__ cg, double* __restrict__ xg, double* __restrict__ yg,
@@ -814,6 +826,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                  int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue, DevOpts o) {
     using G_ = GeoG<MP, NP, SL>;
     constexpr int G = G_::G, NCG = G_::NCG, NCD = G_::NCD, ND = G_::ND, JB = G_::JB, AS = G_::AS;
+    static_assert(!FULL || (SL && !PC), "full-shape instantiations exist for the plain slack-aware kernels only");
     const int nd = SL ? n - m : n;          // dense columns of A (the last m columns are the identity when SL)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
@@ -872,7 +885,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
     bool ok[NCG];
 #pragma unroll
     for (int q = 0; q < NCG; q++) {
-        ok[q] = (q < NCD) ? (gl + MP * q < nd) : (gl < m);
+        ok[q] = FULL || ((q < NCD) ? (gl + MP * q < nd) : (gl < m));
         x[q] = 1.0; z[q] = 1.0; c[q] = 0.0; v[q] = 0.0;
     }
     // global column of register q (dense registers first, then (SL) the slack column of row gl) from an OPAQUE lane index: the
@@ -944,7 +957,16 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         for (int q = 0; q < NCG; q++) {
             const double sg = ok[q] ? c[q] - v[q] + z[q] : 0.0;
             s2 = fma(sg, sg, s2);
-            gam += ok[q] ? x[q] * z[q] : 0.0;
+            if constexpr (FULL) {
+                // without the select nothing keeps the product from contracting into the sum; the generic text adds the ROUNDED
+                // product, so this one must (the pin is no instruction, it only forbids the fma).  A branch of its own: the
+                // generic line written with a named product compiles to other machine code in every generic kernel
+                double xz = x[q] * z[q];
+                asm volatile("" : "+v"(xz));
+                gam += xz;
+            } else {
+                gam += ok[q] ? x[q] * z[q] : 0.0;
+            }
             pp += c[q] * (ok[q] ? x[q] : 0.0);
         }
         s2 = grp_sum<MP>(s2); gam = grp_sum<MP>(gam);
@@ -1078,7 +1100,13 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             if (SL) {   // identity columns: x_slack and (d t)_slack go straight to row gl, d_slack onto the diagonal of M
                 Ax_ += ok[NCG - 1] ? x[NCG - 1] : 0.0;
                 Adt_ += d[NCG - 1] * t[NCG - 1];
-                w.slab[G_::sidx(gl, gl)] += d[NCG - 1];
+                if constexpr (FULL) {   // d_slack is a bare product here: added rounded, as the generic text adds it (see gam above)
+                    double ds = d[NCG - 1];
+                    asm volatile("" : "+v"(ds));
+                    w.slab[G_::sidx(gl, gl)] += ds;
+                } else {
+                    w.slab[G_::sidx(gl, gl)] += d[NCG - 1];
+                }
                 wave_lds_sync();
             }
         };
@@ -1098,7 +1126,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         {
             double W[MP];
             const int gd = w.ogl();
-            if (m < MP) {   // padded rows of A are zero rows/columns of M: make them identity rows -- in the slab, before the rows
+            if (!FULL && m < MP) {   // padded rows of A are zero rows/columns of M: make them identity rows -- in the slab, before the rows
                             // are fetched (one masked LDS write; as 32 selects on the fetched row it was 98 vector instructions
                             // per iteration, executed whether or not m < MP: the compiler had if-converted the branch)
                 if (!rowok) w.slab[G_::sidx(gd, gd)] = 1.0;

@@ -296,7 +296,9 @@ class Handle(object):
         ``wave_shape`` (MB, NQ) on the wavefront-per-LP kernel, ``group_shape`` (MP, NP) and ``slack`` (1: the slack-aware
         kernel) on the lane-group kernels, ``big_shape`` (WGPC, BNC) and ``factor_in_lds`` (the factor blocks in LDS, else in the
         L2 workspace) on the large-LP kernel; ``a_in_lds`` (A's CSR / CSC copy in LDS, else read through L2) where the block
-        kernel served the launch."""
+        kernel served the launch.  Dense family: ``full_shape``, whether a full-shape instantiation of a lane-group kernel served
+        it (the LP fills a compiled shape exactly; ``_native.FLAG_GENERIC_SHAPE`` in ``flags`` keeps the generic one; the key
+        is absent with a PYCLLP_HIP_LIB library that predates the entry, ``_native.LATER_ENTRIES``)."""
         keys = ("grid", "block", "lds_bytes") + (("m_pad", "n_pad") if self.family == "dense" else ("kernel",))
         vals = [ctypes.c_int() for _ in keys]
         self._call("launch_info", self, *[ctypes.byref(v) for v in vals])
@@ -311,6 +313,8 @@ class Handle(object):
             d["wave_shape"] = (a, b)
         elif a > 0:
             d["group_shape"], d["slack"] = (a, b), shape[2].value
+        if self.family == "dense" and _native.has_entry("pycllp_hip_dense_full_shape"):
+            d["full_shape"] = bool(_native.lib().pycllp_hip_dense_full_shape(self))
         plan = [ctypes.c_int() for _ in range(4)]
         self._call("plan_info", self, *[ctypes.byref(v) for v in plan])
         wgpc, bnc, factor, a_lds = [v.value for v in plan]
