@@ -1,7 +1,12 @@
 // abi_sparse.hip -- the C ABI of the sparse handle (include/pycllp_hip.h: pycllp_hip_sparse_*), the three LDL' entries, the
 // entries that belong to no handle (ABI version, default options, last error) and the thread's error message.  Host code only:
 // the kernels are reached through wreg.h (the wave kernels), big.h (the large-LP kernel) and block.h (the block kernel, LDL').
+// The block kernel's plan comes from block_plan.h; pycllp_hip_debug_plan (last in this file) builds any plan without a HIP call.
 #include "host.h"
+#include "wreg_plan.h"
+#include "big_plan.h"
+#include "block_plan.h"
+#include "plan_upload.h"
 
 static thread_local char g_err[512] = "";
 
@@ -102,15 +107,6 @@ static long block_plan(int lds, long cus, long B) {
     return blocks > B ? B : blocks;
 }
 
-template <typename T>
-static T* blob_put(char* host, size_t& off, const std::vector<T>& v, char* dev_base) {
-    off = (off + 15) & ~(size_t)15;
-    if (!v.empty()) memcpy(host + off, v.data(), v.size() * sizeof(T));
-    T* p = (T*)(dev_base + off);
-    off += v.size() * sizeof(T);
-    return p;
-}
-
 int sparse_init_host(int m, int n, int nnz, const std::vector<double>& val, const std::vector<int>& ptr, const std::vector<int>& col,
                      void* stream, pycllp_hip_sparse** handle) {
     hipStream_t st = (hipStream_t)stream;
@@ -135,37 +131,6 @@ int sparse_init_host(int m, int n, int nnz, const std::vector<double>& val, cons
         *handle = hb;
         return 0;
     }
-    // CSC by counting sort (rows ascending inside a column)
-    std::vector<int> cptr(n + 1, 0), crow(nnz), csrc(nnz);
-    std::vector<double> cval(nnz);
-    for (int e = 0; e < nnz; e++) cptr[col[e] + 1]++;
-    for (int j = 0; j < n; j++) cptr[j + 1] += cptr[j];
-    {
-        std::vector<int> fill(cptr.begin(), cptr.end() - 1);
-        for (int i = 0; i < m; i++)
-            for (int e = ptr[i]; e < ptr[i + 1]; e++) { const int q = fill[col[e]]++; crow[q] = i; cval[q] = val[e]; csrc[q] = e; }
-    }
-    // Gram term list: entry (i,k), i >= k, gets a term a_ij a_kj for every column j holding both rows
-    struct Term { int key, colj; double w; int ia, ib; };
-    std::vector<Term> terms;
-    for (int j = 0; j < n; j++)
-        for (int a = cptr[j]; a < cptr[j + 1]; a++)
-            for (int b2 = cptr[j]; b2 <= a; b2++) {
-                const int i = crow[a], k = crow[b2];
-                const int hi = i > k ? i : k, lo = i > k ? k : i;
-                terms.push_back({hi * (hi + 1) / 2 + lo, j, cval[a] * cval[b2], csrc[a], csrc[b2]});
-                if (terms.size() > (size_t)8 << 20)
-                    return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_init: A is too dense for the term-list Gram assembly");
-            }
-    std::stable_sort(terms.begin(), terms.end(), [](const Term& x, const Term& y) { return x.key < y.key; });
-    std::vector<int> ent_tri, ent_ptr, term_col(terms.size()), term_ia(terms.size()), term_ib(terms.size());
-    std::vector<double> term_w(terms.size());
-    for (size_t t = 0; t < terms.size(); t++) {
-        if (t == 0 || terms[t].key != terms[t - 1].key) { ent_tri.push_back(terms[t].key); ent_ptr.push_back((int)t); }
-        term_col[t] = terms[t].colj; term_w[t] = terms[t].w; term_ia[t] = terms[t].ia; term_ib[t] = terms[t].ib;
-    }
-    ent_ptr.push_back((int)terms.size());
-
     pycllp_hip_sparse* h = new (std::nothrow) pycllp_hip_sparse();
     if (!h) return set_err(PYCLLP_E_NOMEM, "pycllp_hip_sparse_init: out of host memory");
     // on failure the partly built handle goes through pycllp_hip_sparse_free, which skips what was not made
@@ -174,43 +139,28 @@ int sparse_init_host(int m, int n, int nnz, const std::vector<double>& val, cons
     if (e != hipSuccess) { pycllp_hip_sparse_free(h); return set_err((int)e, "hipGetDeviceProperties"); }
     h->num_cu = lim.num_cu;
     const int max_lds = lim.max_lds;
-    const size_t total = 64 + sizeof(double) * (val.size() + cval.size() + term_w.size()) +
-                         sizeof(int) * (ptr.size() + col.size() + cptr.size() + crow.size() + ent_tri.size() + ent_ptr.size() +
-                                        term_col.size() + csrc.size() + term_ia.size() + term_ib.size()) + 16 * 16;
-    std::vector<char> host(total);
-    e = hipMalloc(&h->dev_blob, total);
-    if (e == hipSuccess) e = h->ring.create();
-    if (e != hipSuccess) { pycllp_hip_sparse_free(h); return set_err((int)e, "hipMalloc(sparse A)"); }
-    size_t off = 0;
-    char* db = (char*)h->dev_blob;
-    BlockA& d = h->desc;
-    d.m = m; d.n = n; d.nnz = nnz;
-    d.csr_val = blob_put(host.data(), off, val, db);   d.csr_ptr = blob_put(host.data(), off, ptr, db);
-    d.csr_col = blob_put(host.data(), off, col, db);   d.csc_val = blob_put(host.data(), off, cval, db);
-    d.csc_ptr = blob_put(host.data(), off, cptr, db);  d.csc_row = blob_put(host.data(), off, crow, db);
-    d.ent_tri = blob_put(host.data(), off, ent_tri, db); d.ent_ptr = blob_put(host.data(), off, ent_ptr, db);
-    d.term_w = blob_put(host.data(), off, term_w, db);   d.term_col = blob_put(host.data(), off, term_col, db);
-    d.csc_src = blob_put(host.data(), off, csrc, db);
-    d.term_ia = blob_put(host.data(), off, term_ia, db); d.term_ib = blob_put(host.data(), off, term_ib, db);
-    d.n_entries = (int)ent_tri.size(); d.n_terms = (int)terms.size();
-    e = hipMemcpyAsync(h->dev_blob, host.data(), off, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { pycllp_hip_sparse_free(h); return set_err((int)e, "upload sparse A"); }
-    // LDS plan: two workgroups per CU hide each other's LDS latency, so the CSR/CSC copy goes into LDS only when the
-    // workgroup still fits in half a CU (or when it cannot be paired anyway)
-    const size_t mp8 = ((size_t)m + 7) & ~(size_t)7;
-    const size_t base = sizeof(double) * ((size_t)m * (m + 1) / 2 + 1 + 2 * ((size_t)n + 1) + 7 * mp8 + 8);
-    const size_t with_a = base + sizeof(double) * 2 * (size_t)nnz + sizeof(int) * (2 * (size_t)nnz + m + n + 2) + 16;
-    const size_t half = (size_t)max_lds / 2;
-    if (with_a <= half) d.a_in_lds = 1;
-    else if (base <= half) d.a_in_lds = 0;
-    else d.a_in_lds = with_a <= (size_t)max_lds ? 1 : 0;
-    h->lds = (int)(d.a_in_lds ? with_a : base);
-    h->lds_with_a = with_a <= (size_t)max_lds ? (int)with_a : 0;
-    if ((size_t)h->lds > (size_t)max_lds) {
+    // the block kernel's plan (block_plan.h), its tables uploaded, the device pointers set
+    BlockHostPlan H;
+    const int brc = block_host_plan(m, n, nnz, val.data(), ptr.data(), col.data(), max_lds, H);
+    if (brc != BLOCK_PLAN_OK) {
         pycllp_hip_sparse_free(h);
-        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_sparse_init: problem does not fit in LDS");
+        return set_err(PYCLLP_E_UNSUPPORTED, brc == BLOCK_PLAN_TOO_DENSE ? "pycllp_hip_sparse_init: A is too dense for the term-list Gram assembly"
+                                                                         : "pycllp_hip_sparse_init: problem does not fit in LDS");
     }
+    e = h->ring.create();
+    if (e != hipSuccess) { pycllp_hip_sparse_free(h); return set_err((int)e, "hipMalloc(sparse A)"); }
+    e = plan_upload(H.blob, st, &h->dev_blob);
+    if (e != hipSuccess) { pycllp_hip_sparse_free(h); return set_err((int)e, "upload sparse A"); }
+    const char* db = (const char*)h->dev_blob;
+    BlockA& d = h->desc;
+    d = H.desc;
+    d.csr_val = (const double*)(db + H.a_csr_val); d.csr_ptr = (const int*)(db + H.a_csr_ptr); d.csr_col = (const int*)(db + H.a_csr_col);
+    d.csc_val = (const double*)(db + H.a_csc_val); d.csc_ptr = (const int*)(db + H.a_csc_ptr); d.csc_row = (const int*)(db + H.a_csc_row);
+    d.ent_tri = (const int*)(db + H.a_ent_tri); d.ent_ptr = (const int*)(db + H.a_ent_ptr);
+    d.term_w = (const double*)(db + H.a_term_w); d.term_col = (const int*)(db + H.a_term_col);
+    d.csc_src = (const int*)(db + H.a_csc_src);
+    d.term_ia = (const int*)(db + H.a_term_ia); d.term_ib = (const int*)(db + H.a_term_ib);
+    h->lds = H.lds; h->lds_with_a = H.lds_with_a;
     // the register-resident one-LP-per-wavefront kernel takes over whenever its tables fit (ipm_wreg.hip)
     {
         WregPlan* wp = nullptr;
@@ -566,3 +516,26 @@ int pycllp_hip_forward_backward_ldl(int n, long B, const double* L_dev, const do
 }
 
 }  // extern "C"
+
+// Not part of the public ABI (absent from include/pycllp_hip.h): the plan a creator would build for the matrix given as HOST CSR
+// arrays, with no HIP call and nothing uploaded.  kind: 0 the block kernel's plan; 1 .. 6 the wave kernel's creators (wreg_plan_create,
+// the same with pa, _bounded, _bounded_pa, _dense_pa without and with keep_tail); 7 the large-LP kernel's.  Returns the creator's
+// code (the block plan: BLOCK_PLAN_*) and, where it is 0, scalars[PLAN_NSCALARS] and the digest as the plan's header documents them.
+extern "C" int pycllp_hip_debug_plan(int kind, int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
+                                     long long* scalars, unsigned long long* digest) {
+    if (kind < 0 || kind > 7 || m < 0 || n < 0 || nnz < 0 || !ptr || !scalars || !digest || (nnz > 0 && (!val || !col))) return -1;
+    memset(scalars, 0, sizeof(long long) * PLAN_NSCALARS);
+    *digest = 0;
+    int rc;
+    if (kind == 0) {
+        BlockHostPlan P;
+        if ((rc = block_host_plan(m, n, nnz, val, ptr, col, max_lds, P)) == 0) *digest = block_plan_report(P, scalars);
+    } else if (kind == 7) {
+        BigHostPlan P;
+        if ((rc = big_host_plan(m, n, nnz, val, ptr, col, max_lds, P)) == 0) *digest = big_plan_report(P, scalars);
+    } else {
+        WregHostPlan P;
+        if ((rc = wreg_plan_host((WregPlanKind)(kind - 1), m, n, nnz, val, ptr, col, max_lds, &P)) == 0) *digest = wreg_plan_report(P, scalars);
+    }
+    return rc;
+}

@@ -7,6 +7,29 @@
 constexpr int BIG_MAX_M = 256;    // rows (16 x 16 blocks: MB <= 16)
 constexpr int BIG_MAX_N = 1280;   // columns of the equality form (5 per thread)
 
+// Device view of the tables of one constraint matrix (built by big_plan.h, uploaded by big_plan_create)
+struct BigTab {
+    int m, n, nnz, MB, dense, m_in_lds, lds_bytes;
+    int nd, ks, imgR, n_sl;              // dense mode: nd dense columns, ks = k-steps of 4 columns, image rows, identity columns behind them
+    const double* csr_val; const int* csr_ptr; const int* csr_col;   // A by rows
+    const double* csc_val; const int* csc_ptr; const int* csc_row;   // A by columns
+    const double* img;                   // [ks][imgR][4]
+    const double* img_rm;                // dense mode: the dense columns row-major [m][nd] (A'u: thread = column, coalesced)
+    const double* img_cm;                // ... and column-major [nd][imgR] (A v: thread = row, coalesced)
+    int n_ent;                           // term-list mode: entries (i, k), i >= k, of M with their terms a_ij a_kj, column j
+    const int* ent_dst; const int* ent_dst2; const int* ent_ptr; const double* term_w; const int* term_col;
+};
+
+__host__ __device__ inline int bidx(int K, int I) { return I * (I + 1) / 2 + K; }     // block (K, I), K <= I, of U = L'
+// offset of element [kl][il] inside a block
+__host__ __device__ inline int boff(int kl, int il) { return (kl >> 2) * 64 + (kl & 3) * 16 + il; }
+
+// doubles of LDS the kernel carves (host and device agree through this one function)
+__host__ __device__ constexpr size_t big_lds_doubles(int MB, int n, bool m_in_lds) {
+    const size_t MP = 16 * (size_t)MB, NPv = ((size_t)n + 7) & ~(size_t)7;
+    return (m_in_lds ? (size_t)MB * (MB + 1) / 2 * 256 : 0) + (size_t)MB * 256 + 2 * NPv + 9 * MP + 272 + 256 + 32;
+}
+
 struct BigPlan;   // host tables + device copies for one shared constraint matrix
 
 // Builds the plan from a host CSR copy of A (m rows, n columns, equality form).  0 and *out on success, 1 when the problem is

@@ -24,6 +24,14 @@ struct BlockA {            // device-side description of the shared constraint m
     const int* term_ia; const int* term_ib;                          // Gram term = val[term_ia] * val[term_ib]
 };
 
+// LDS bytes of a workgroup of ipm_block_kernel: an upper bound of the carve-up at the top of ipm_block.inc -- the packed
+// triangle of M, two N-vectors, seven m-vectors padded to 8 rows, the reduction scratch; with_a: also A's CSR / CSC copy
+inline size_t block_lds_bytes(int m, int n, int nnz, bool with_a) {
+    const size_t mp8 = ((size_t)m + 7) & ~(size_t)7;
+    const size_t base = sizeof(double) * ((size_t)m * (m + 1) / 2 + 1 + 2 * ((size_t)n + 1) + 7 * mp8 + 8);
+    return with_a ? base + sizeof(double) * 2 * (size_t)nnz + sizeof(int) * (2 * (size_t)nnz + m + n + 2) + 16 : base;
+}
+
 // Solve B LPs on `blocks` workgroups with `lds` bytes of LDS each (argument meaning of pycllp_hip_sparse_solve; qhead: a zeroed
 // work-queue head).  worklist: null, or the LPs to solve (worklist[0] = count) -- those a wave kernel deferred.  a_batch: null,
 // or [B, nnz] per-problem values in CSR order.  block_set_lds(lds) comes first: the kernel's dynamic LDS, set apart from the

@@ -89,10 +89,8 @@ inline hipError_t device_limits(DeviceLimits* d) {
 struct LaunchPlan { int grid, block, lds, mp, np, sl; };   // sl: a kernel of the slack-aware table
 
 // The persistent lane-group kernels run one workgroup per CU (its 8 waves already use the whole register file, so a second
-// workgroup could not become resident whatever the LDS says), on the CUs the caller did not reserve
-inline long resident_cus(const DeviceLimits& d, const DevOpts& o) {
-    return (long)d.num_cu - o.reserve_cus > 0 ? (long)d.num_cu - o.reserve_cus : 1;
-}
+// workgroup could not become resident whatever the LDS says), on the CUs the caller did not reserve (wave_common.h)
+inline long resident_cus(const DeviceLimits& d, const DevOpts& o) { return resident_cus(d.num_cu, o); }
 // A batch too small to fill every CU's eight waves (round 3): the waves per workgroup, wpb at most, of a kernel with G lane
 // groups per wave.  Two waves on one SIMD share its issue port and the lane groups of a wave share its
 // instruction stream, so: up to one wave per SIMD everywhere (4 per CU) every LP gets a wavefront of its own -- the kernel's

@@ -25,7 +25,8 @@
 // reference kernels replaced as in ipm_block.inc (pycllp/cl/primal_normal.cl:201-375, pycllp/cl/ldl.cl:314-712).
 // The Nocedal-Wright guard (ldl.cl:368) is recorded, not applied, by the blocked factorisation; when it would have bitten
 // (rare: collapsing iterates of the embedding) M is re-formed and a column-by-column cold path applies it exactly.
-#include "big.h"
+#include "big_plan.h"
+#include "plan_upload.h"
 
 namespace {
 
@@ -34,22 +35,6 @@ namespace {
 #endif
 constexpr int BT = 256;                  // threads per workgroup
 constexpr int BNC_MAX = BIG_MAX_N / BT;  // N-vector registers per thread at the largest n (the kernel is instantiated for 2, 3 and 5)
-
-struct BigTab {
-    int m, n, nnz, MB, dense, m_in_lds, lds_bytes;
-    int nd, ks, imgR, n_sl;              // dense mode: nd dense columns, ks = k-steps of 4 columns, image rows, identity columns behind them
-    const double* csr_val; const int* csr_ptr; const int* csr_col;   // A by rows
-    const double* csc_val; const int* csc_ptr; const int* csc_row;   // A by columns
-    const double* img;                   // [ks][imgR][4]
-    const double* img_rm;                // dense mode: the dense columns row-major [m][nd] (A'u: thread = column, coalesced)
-    const double* img_cm;                // ... and column-major [nd][imgR] (A v: thread = row, coalesced)
-    int n_ent;                           // term-list mode: entries (i, k), i >= k, of M with their terms a_ij a_kj, column j
-    const int* ent_dst; const int* ent_dst2; const int* ent_ptr; const double* term_w; const int* term_col;
-};
-
-__host__ __device__ inline int bidx(int K, int I) { return I * (I + 1) / 2 + K; }     // block (K, I), K <= I, of U = L'
-// offset of element [kl][il] inside a block
-__host__ __device__ inline int boff(int kl, int il) { return (kl >> 2) * 64 + (kl & 3) * 16 + il; }
 
 __device__ __forceinline__ double bsum(double v, double* red, int tid) {
     v = wave_sum(v);
@@ -64,12 +49,6 @@ __device__ __forceinline__ double bmax(double v, double* red, int tid) {
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-
-// doubles of LDS the kernel carves (host and device agree through this one function)
-__host__ __device__ constexpr size_t big_lds_doubles(int MB, int n, bool m_in_lds) {
-    const size_t MP = 16 * (size_t)MB, NPv = ((size_t)n + 7) & ~(size_t)7;
-    return (m_in_lds ? (size_t)MB * (MB + 1) / 2 * 256 : 0) + (size_t)MB * 256 + 2 * NPv + 9 * MP + 272 + 256 + 32;
 }
 
 // WGPC: workgroups per CU the instance is compiled for (2: 256 registers per lane; 3: 168, more spills, more overlap).
@@ -765,14 +744,6 @@ ipm_big_kernel(BigTab T, long B, const double* __restrict__ bg, const double* __
     if (o.prof && tid == 0) { STAMP_FLUSH_BLOCK(o, blockIdx.x) }
 }
 
-template <typename T>
-size_t put(std::vector<char>& host, const std::vector<T>& v) {
-    size_t off = (host.size() + 15) & ~(size_t)15;
-    host.resize(off + std::max<size_t>(v.size(), 1) * sizeof(T));
-    if (!v.empty()) memcpy(host.data() + off, v.data(), v.size() * sizeof(T));
-    return off;
-}
-
 }  // namespace
 
 struct BigPlan {
@@ -782,105 +753,23 @@ struct BigPlan {
     std::atomic<int> launched{0};        // WGPC << 8 | BNC of the instantiation the last launch ran (0: none yet)
 };
 
+// the host plan (big_plan.h), its tables uploaded, the device pointers set (an empty table's points behind the one before)
 int big_plan_create(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds, hipStream_t st,
                     BigPlan** out) {
-    if (m > BIG_MAX_M || n > BIG_MAX_N || m < 1 || n < 1) return 1;
-    const int MB = (m + 15) / 16, MP = 16 * MB;
+    BigHostPlan H;
+    const int rc = big_host_plan(m, n, nnz, val, ptr, col, max_lds, H);
+    if (rc != 0) return rc;
     BigPlan* P = new BigPlan();
+    const hipError_t e = plan_upload(H.blob, st, &P->dev_blob);
+    if (e != hipSuccess) { delete P; return 1000 + (int)e; }
+    P->tab = H.tab; P->ws_doubles_per_block = H.ws_doubles_per_block;
     BigTab& T = P->tab;
-    memset(&T, 0, sizeof(T));
-    T.m = m; T.n = n; T.nnz = nnz; T.MB = MB;
-    // ---- CSC by counting sort (rows ascending inside a column) ----
-    std::vector<int> cptr(n + 1, 0), crow(nnz);
-    std::vector<double> cval(nnz);
-    for (int e = 0; e < nnz; e++) cptr[col[e] + 1]++;
-    for (int j = 0; j < n; j++) cptr[j + 1] += cptr[j];
-    {
-        std::vector<int> fill(cptr.begin(), cptr.end() - 1);
-        for (int i = 0; i < m; i++)
-            for (int e = ptr[i]; e < ptr[i + 1]; e++) { const int p = fill[col[e]]++; crow[p] = i; cval[p] = val[e]; }
-    }
-    // ---- identity tail (equality form of a StandardLP)? ----
-    bool sl = n > m;
-    {
-        std::vector<int> tail_cnt(sl ? m : 0, 0);
-        for (int i = 0; i < m && sl; i++)
-            for (int e = ptr[i]; e < ptr[i + 1]; e++)
-                if (col[e] >= n - m) { if (col[e] != n - m + i || val[e] != 1.0) sl = false; else tail_cnt[i]++; }
-        for (int i = 0; i < m && sl; i++) if (tail_cnt[i] != 1) sl = false;
-    }
-    const int nd = sl ? n - m : n;
-    // ---- Gram by term list or on the matrix cores?  terms = sum over columns of len (len + 1) / 2 products per Newton step,
-    //      against MP^2 / 2 * nd for the dense product at the 8x higher rate of the matrix pipe over a gather-bound loop ----
-    double n_terms = 0.0;
-    for (int j = 0; j < n; j++) { const double l = cptr[j + 1] - cptr[j]; n_terms += l * (l + 1) / 2; }
-    T.dense = n_terms > 0.125 * (double)MP * MP * nd ? 1 : 0;
-    std::vector<double> img, img_rm, img_cm;
-    std::vector<int> ent_dst, ent_dst2, ent_ptr, term_col;
-    std::vector<double> term_w;
-    if (T.dense) {
-        T.nd = nd; T.n_sl = n - nd; T.ks = (nd + 3) / 4; T.imgR = MP;
-        img.assign((size_t)T.ks * MP * 4, 0.0);
-        img_rm.assign((size_t)m * nd, 0.0);
-        img_cm.assign((size_t)nd * MP, 0.0);
-        for (int i = 0; i < m; i++)
-            for (int e = ptr[i]; e < ptr[i + 1]; e++)
-                if (col[e] < nd) {
-                    img[((size_t)(col[e] >> 2) * MP + i) * 4 + (col[e] & 3)] = val[e];
-                    img_rm[(size_t)i * nd + col[e]] = val[e];
-                    img_cm[(size_t)col[e] * MP + i] = val[e];
-                }
-    } else {
-        struct Term { int key, colj; double w; };
-        std::vector<Term> terms;
-        for (int j = 0; j < n; j++)
-            for (int a = cptr[j]; a < cptr[j + 1]; a++)
-                for (int b2 = cptr[j]; b2 <= a; b2++) {
-                    const int i = crow[a], k = crow[b2];     // rows ascend inside a column: i >= k
-                    terms.push_back({i * m + k, j, cval[a] * cval[b2]});
-                    if (terms.size() > ((size_t)1 << 24)) { delete P; return 1; }
-                }
-        std::stable_sort(terms.begin(), terms.end(), [](const Term& x, const Term& y) { return x.key < y.key; });
-        term_col.resize(terms.size()); term_w.resize(terms.size());
-        for (size_t t = 0; t < terms.size(); t++) {
-            if (t == 0 || terms[t].key != terms[t - 1].key) {
-                const int i = terms[t].key / m, k = terms[t].key % m;
-                const int K = k >> 4, I = i >> 4, kl = k & 15, il = i & 15;
-                ent_dst.push_back(bidx(K, I) * 256 + boff(kl, il));
-                ent_dst2.push_back((K == I && kl != il) ? bidx(K, K) * 256 + boff(il, kl) : -1);
-                ent_ptr.push_back((int)t);
-            }
-            term_col[t] = terms[t].colj; term_w[t] = terms[t].w;
-        }
-        ent_ptr.push_back((int)terms.size());
-        T.n_ent = (int)ent_dst.size();
-    }
-    // ---- LDS plan: the blocks in LDS only when two workgroups still fit a CU with them -- measured (round 3,
-    //      profiles/r03/large_lp_kernel.txt): a second resident workgroup is worth more than LDS-resident blocks (m = 144 with
-    //      the blocks in LDS and one workgroup per CU: 22 k LPs/s; with the blocks in the L2 workspace and two: 35 k, three: 44 k) ----
-    T.m_in_lds = big_lds_doubles(MB, n, true) * sizeof(double) * 2 <= (size_t)max_lds ? 1 : 0;
-    const size_t lds = big_lds_doubles(MB, n, T.m_in_lds != 0) * sizeof(double);
-    if (lds > (size_t)max_lds) { delete P; return 1; }
-    T.lds_bytes = (int)lds;
-    P->ws_doubles_per_block = T.m_in_lds ? 0 : (size_t)MB * (MB + 1) / 2 * 256;
-    // ---- device copies ----
-    std::vector<char> host;
-    std::vector<double> csr_val(val, val + nnz);
-    std::vector<int> csr_ptr(ptr, ptr + m + 1), csr_col(col, col + nnz);
-    const size_t a1 = put(host, csr_val), a2 = put(host, csr_ptr), a3 = put(host, csr_col), a4 = put(host, cval),
-                 a5 = put(host, cptr), a6 = put(host, crow), a7 = put(host, img), a8 = put(host, ent_dst),
-                 a9 = put(host, ent_dst2), a10 = put(host, ent_ptr), a11 = put(host, term_w), a12 = put(host, term_col),
-                 a13 = put(host, img_rm), a14 = put(host, img_cm);
-    hipError_t e = hipMalloc(&P->dev_blob, host.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(P->dev_blob, host.data(), host.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { if (P->dev_blob) (void)hipFree(P->dev_blob); delete P; return 1000 + (int)e; }
-    char* db = (char*)P->dev_blob;
-    T.csr_val = (const double*)(db + a1); T.csr_ptr = (const int*)(db + a2); T.csr_col = (const int*)(db + a3);
-    T.csc_val = (const double*)(db + a4); T.csc_ptr = (const int*)(db + a5); T.csc_row = (const int*)(db + a6);
-    T.img = (const double*)(db + a7); T.img_rm = (const double*)(db + a13); T.img_cm = (const double*)(db + a14);
-    T.ent_dst = (const int*)(db + a8); T.ent_dst2 = (const int*)(db + a9); T.ent_ptr = (const int*)(db + a10);
-    T.term_w = (const double*)(db + a11); T.term_col = (const int*)(db + a12);
+    const char* db = (const char*)P->dev_blob;
+    T.csr_val = (const double*)(db + H.a_csr_val); T.csr_ptr = (const int*)(db + H.a_csr_ptr); T.csr_col = (const int*)(db + H.a_csr_col);
+    T.csc_val = (const double*)(db + H.a_csc_val); T.csc_ptr = (const int*)(db + H.a_csc_ptr); T.csc_row = (const int*)(db + H.a_csc_row);
+    T.img = (const double*)(db + H.a_img); T.img_rm = (const double*)(db + H.a_img_rm); T.img_cm = (const double*)(db + H.a_img_cm);
+    T.ent_dst = (const int*)(db + H.a_ent_dst); T.ent_dst2 = (const int*)(db + H.a_ent_dst2); T.ent_ptr = (const int*)(db + H.a_ent_ptr);
+    T.term_w = (const double*)(db + H.a_term_w); T.term_col = (const int*)(db + H.a_term_col);
     *out = P;
     return 0;
 }
@@ -930,7 +819,7 @@ void big_shape(const BigPlan* p, int* wgpc, int* bnc, int* m_in_lds) {
 static hipError_t big_launch(BigPlan* p, long B, const double* b, const double* c, double* x, double* y, double* z, double* pobj,
                              double* dobj, int* status, int* iters, int* qhead, double mu, double* nwt_dy, int* nwt_nref,
                              DevOpts o, int num_cu, hipStream_t st, int* grid_out) {
-    long cus = (long)num_cu - o.reserve_cus > 0 ? (long)num_cu - o.reserve_cus : 1;
+    long cus = resident_cus(num_cu, o);
     const BigVariant* v = big_select(p->tab.n, p->tab.lds_bytes);
     if (!v) return hipErrorInvalidConfiguration;
     const big_kernel_fn kern = v->kern;

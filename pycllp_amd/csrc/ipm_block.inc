@@ -52,7 +52,7 @@ ipm_block_kernel(BlockA A, long B, const double* __restrict__ bg, const double* 
     const int m = A.m, n = A.n;
     const int ntri = m * (m + 1) / 2;
     const int mp = (m + 7) & ~7;           // m-vectors are padded to whole 8-row tiles (and stay 16-byte aligned)
-    // ---- LDS carve-up ----
+    // ---- LDS carve-up (the host sizes it by block_lds_bytes, block.h: an upper bound of what follows) ----
     double* M = lds;                       // packed lower triangle, then L (unit diagonal implicit) in place
     double* vx = M + ((ntri + 1) & ~1);    // [n] staging of an N-vector (x, d*t, dx) for the CSR products
     double* vd = vx + ((n + 1) & ~1);      // [n] d = x/z for the Gram assembly

@@ -111,6 +111,8 @@ struct DevOpts {
     int reserve_cus;           // host side only: CUs left idle by the launch plan
     unsigned long long* prof;  // diagnostic build only (-DPYCLLP_PROFILE): per-wave phase cycle sums
 };
+// the CUs left to a solve: those the caller did not reserve, one at least
+inline long resident_cus(int num_cu, const DevOpts& o) { return (long)num_cu - o.reserve_cus > 0 ? (long)num_cu - o.reserve_cus : 1; }
 
 // In-kernel phase stamps (diagnostic build only; the shipped library has no stamp executing).
 #ifdef PYCLLP_PROFILE

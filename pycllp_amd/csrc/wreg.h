@@ -9,7 +9,7 @@
 constexpr int MAX_NQ = 8;
 constexpr int META_COFF = MAX_NQ, META_SEG = 2 * MAX_NQ, META_N = META_SEG + 16;
 
-// Geometry of a wave's LDS area: the kernels (wreg_wave.h) and the plan builders of the host (ipm_wreg.hip) compute the same.
+// Geometry of a wave's LDS area: the kernels (wreg_wave.h) and the plan builders of the host (wreg_plan.h) call the same functions.
 // stage proper: N-vector staging; during factor/solve t, x and z parked at 0, NP, 2 NP and the stride-17 tile of the current
 // diagonal block behind them
 constexpr int TILE_D = 272;
@@ -18,6 +18,13 @@ __host__ __device__ constexpr int stage_d(int NQ) { return tile_off(NQ) + TILE_D
 constexpr int HB = 8;            // 16 x 16 blocks per Gram staging chunk: the stage and, behind it, the still unused W area (16 KB)
 constexpr int WL = 144;          // doubles per diagonal-block slot: first the ORIGINAL diagonal block of M (lower triangle with
                                  // diagonal, row i at i(i+1)/2: 136), from stage K on W_K (strictly lower triangle, row i at i(i-1)/2)
+// per-wave LDS doubles of an (MB, NQ) kernel: the stage, an N-vector, five m-vectors, the diagonal-block slots (a plan adds
+// what its kind keeps behind them: t and s of the bounded kernel, an LP's own values or image)
+__host__ __device__ constexpr int wave_doubles(int MB, int NQ) { return stage_d(NQ) + 64 * NQ + 5 * 16 * MB + MB * WL; }
+// the diagonal blocks' entries ride with the last Gram staging chunk when its blocks end in front of the W area (where they go)
+__host__ __device__ constexpr bool merge_diag(int MB, int NQ) {
+    return MB * (MB - 1) / 2 > 0 && (MB * (MB - 1) / 2 - HB * ((MB * (MB - 1) / 2 + HB - 1) / HB - 1)) * 256 <= stage_d(NQ);
+}
 template <int MB>
 struct WGeo {
     static constexpr int MP = 16 * MB;
@@ -28,9 +35,8 @@ struct WGeo {
     __host__ __device__ static constexpr int bix(int K, int I) { return K * MB - K * (K + 1) / 2 + (I - K - 1); }
     // Gram staging chunks: the off-diagonal blocks in bix order, HB at a time; chunk NCHUNK = the diagonal blocks
     static constexpr int NCHUNK = (NBLK + HB - 1) / HB;
-    // the diagonal blocks' entries ride with the last chunk when its blocks end in front of the W area (where they go)
-    __host__ __device__ static constexpr bool MERGE_DIAG(int NQ) { return NBLK > 0 && (NBLK - HB * (NCHUNK - 1)) * 256 <= stage_d(NQ); }
-    static constexpr int WAVE_D(int NQ) { return stage_d(NQ) + 64 * NQ + 5 * MP + MB * WL; }   // per-wave LDS doubles
+    __host__ __device__ static constexpr bool MERGE_DIAG(int NQ) { return merge_diag(MB, NQ); }
+    static constexpr int WAVE_D(int NQ) { return wave_doubles(MB, NQ); }
 };
 // byte offset of a padded position of the N-vectors inside an LP's row: past the row, where a buffer load reads 0 and a
 // store is dropped (row_rsrc, wreg_wave.h)

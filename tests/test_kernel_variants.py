@@ -132,7 +132,7 @@ def wave_doubles(mb, nq, bounded):
 
 
 def image_waves(m, N, tail, shape, bounded):
-    """Waves per workgroup of the dense-image plan (wreg_plan_create_dense), 0 when the image does not fit."""
+    """Waves per workgroup of the dense-image plan (wreg_plan.h wreg_image_plan), 0 when the image does not fit."""
     nd = N - m if tail else N
     img = 8 * ((m + 7) // 8 * 8) * (((max(nd, 1) + 15) // 16) * 16 + 1)
     return max([w for w in (1, 2, 3, 4) if img + 16 + 8 * w * wave_doubles(*shape, bounded) <= MAX_LDS], default=0)

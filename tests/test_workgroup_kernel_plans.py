@@ -49,13 +49,13 @@ BLOCK_KINDS = {"lds-paired": ("plain", "hsd", "newton", "pa", "pa-hsd"), "l2": (
 
 # ---- restatements of the plan rules ---------------------------------------------------------------------------------------
 def big_lds_doubles(MB, n, m_in_lds):
-    """ipm_big.hip big_lds_doubles: the factor blocks (when in LDS), W_K, two N-vectors, nine m-vectors, tile, wsA, red."""
+    """big.h big_lds_doubles: the factor blocks (when in LDS), W_K, two N-vectors, nine m-vectors, tile, wsA, red."""
     MP, NPv = 16 * MB, (n + 7) & ~7
     return (MB * (MB + 1) // 2 * 256 if m_in_lds else 0) + MB * 256 + 2 * NPv + 9 * MP + 272 + 256 + 32
 
 
 def big_plan(MB, N):
-    """(cell, lds_bytes, workgroups per CU the LDS allows) of big_plan_create / big_select: the factor in LDS only when two
+    """(cell, lds_bytes, workgroups per CU the LDS allows) of big_host_plan (big_plan.h) / big_select: the factor in LDS only when two
     workgroups still fit a CU with it; three workgroups per CU where the LDS allows, else two, else one; the first BNC with
     N <= 256 BNC."""
     in_lds = 2 * 8 * big_lds_doubles(MB, N, True) <= MAX_LDS
@@ -315,7 +315,7 @@ def _src(name):
 
 
 def test_constants_and_shape_list_of_the_sources():
-    big, bigh, blk = _src("ipm_big.hip"), _src("big.h"), _src("block.h")
+    big, bigh, blk, plan = _src("ipm_big.hip"), _src("big.h"), _src("block.h"), _src("big_plan.h")
     line = re.search(r"#define BIG_SHAPES\(X\)(.*)", big).group(1)
     assert [(int(a), int(b)) for a, b in re.findall(r"X\((\d+),\s*(\d+)\)", line)] == BIG_SHAPES
     assert int(re.search(r"constexpr int BT = (\d+);", big).group(1)) == BT
@@ -326,8 +326,11 @@ def test_constants_and_shape_list_of_the_sources():
     assert max(BNCS) * BT == BIG_MAX_N and BLK_MAX_N == 2 * BLK_T
     # the selection: the first shape with WGPC = the workgroups per CU the LDS allows and n <= BNC * BT; the term cap
     assert re.search(r"v\.wgpc == per_cu && n <= v\.bnc \* BT", big)
-    assert re.search(r"terms\.size\(\) > \(\(size_t\)1 << 24\)", big) and BIG_MAX_TERMS == 1 << 24
-    assert re.search(r"T\.dense = n_terms > 0\.125 \* \(double\)MP \* MP \* nd", big)
+    # (the plan's rules: big_plan.h; gram_terms of plan_host.h refuses once more than the cap were visited)
+    assert re.search(r"const size_t max_terms = \(size_t\)1 << 24;", plan) and BIG_MAX_TERMS == 1 << 24
+    assert re.search(r"if \(!gram_terms<true>\(n, csc, max_terms,[^\n]*\n\s*return 1;", plan)
+    assert re.search(r"if \(\+\+count > cap\) return false;", _src("plan_host.h"))
+    assert re.search(r"T\.dense = n_terms > 0\.125 \* \(double\)MP \* MP \* nd", plan)
     assert {(w, k) for w in (2, 3) for k in BNCS} == set(BIG_SHAPES)
 
 
