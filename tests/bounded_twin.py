@@ -8,20 +8,28 @@ import numpy as np
 GROWTH_FLOOR = 1e3
 
 
-def ldl_guarded(M, floor, beta2):
-    """Modified LDL' of every matrix of M [B, m, m]: D_j = max(|M_jj|, floor, theta_j^2 / beta2) (ldl.cl:368)."""
+def ldl_guarded(M, floor, beta2, stats=None):
+    """Modified LDL' of every matrix of M [B, m, m]: D_j = max(|M_jj|, floor, theta_j^2 / beta2) (ldl.cl:368).  ``stats``: a
+    dict that receives, per matrix, ``floored`` (the pivots with |M_jj| < floor) and ``guard_ratio`` (the largest
+    theta_j^2 / (beta2 max(|M_jj|, floor)): above 1 the guard's term is the pivot)."""
     W = M.copy()
     B, m, _ = W.shape
     L = np.broadcast_to(np.eye(m), W.shape).copy()
     D = np.zeros((B, m))
+    floored, ratio = np.zeros(B, dtype=np.int64), np.zeros(B)
     for j in range(m):
         col = W[:, j + 1:, j]
         theta = np.abs(col).max(axis=1) if j + 1 < m else np.zeros(B)
         Dj = np.maximum(np.maximum(np.abs(W[:, j, j]), floor), theta * theta / beta2)
+        if stats is not None:
+            floored += np.abs(W[:, j, j]) < floor
+            ratio = np.fmax(ratio, theta * theta / (beta2 * np.maximum(np.abs(W[:, j, j]), floor)))
         lj = col / Dj[:, None]
         W[:, j + 1:, j + 1:] -= lj[:, :, None] * col[:, None, :]
         L[:, j + 1:, j] = lj
         D[:, j] = Dj
+    if stats is not None:
+        stats["floored"], stats["guard_ratio"] = floored, ratio
     return L, D
 
 
@@ -32,7 +40,9 @@ def ldl_solve(L, D, r):
 
 def solve(A, b, c, u, eps=1e-10, delta=0.02, r=0.9, pivot_floor=1e-6, refine_tol=1e-11, max_iter=200, max_refine=5,
           autoscale=False):
-    """dict(x, y, z, s, pobj, dobj, status, iters) for the B LPs (A [m, N] shared; b [B, m]; c, u [B, N])."""
+    """dict(x, y, z, s, pobj, dobj, status, iters, nrefs, floored, guard_ratio) for the B LPs (A [m, N] shared; b [B, m];
+    c, u [B, N]).  ``nrefs``: refinement passes spent, ``floored``: pivots that met the floor, both summed over the
+    iterations an LP was live in; ``guard_ratio``: the largest theta^2 / (beta^2 max(|M_jj|, floor)) of its factorisations."""
     A = np.asarray(A, dtype=np.float64)
     b, c, u = (np.array(v, dtype=np.float64) for v in (b, c, u))
     B, N = c.shape
@@ -59,6 +69,7 @@ def solve(A, b, c, u, eps=1e-10, delta=0.02, r=0.9, pivot_floor=1e-6, refine_tol
     out["y"] = np.zeros((B, m)); out["pobj"] = np.zeros(B); out["dobj"] = np.zeros(B)
     normr0 = np.full(B, 1e300); norms0 = np.full(B, 1e300)
     live = np.ones(B, dtype=bool)
+    nrefs = np.zeros(B, dtype=np.int32); floored = np.zeros(B, dtype=np.int32); guard_ratio = np.zeros(B)
 
     def store(sel, it):
         v = y @ A
@@ -99,7 +110,10 @@ def solve(A, b, c, u, eps=1e-10, delta=0.02, r=0.9, pivot_floor=1e-6, refine_tol
             tt = np.where(act, tt, 0.0)
             M = np.einsum("ik,bk,jk->bij", A, d, A)
             beta2 = np.abs(np.diagonal(M, axis1=1, axis2=2)).max(axis=1)
-            L, D = ldl_guarded(M, pivot_floor, beta2)
+            stats = {}
+            L, D = ldl_guarded(M, pivot_floor, beta2, stats)
+            floored += np.where(live, stats["floored"], 0).astype(np.int32)
+            guard_ratio = np.where(live, np.fmax(guard_ratio, stats["guard_ratio"]), guard_ratio)
             dy = ldl_solve(L, D, (d * tt) @ A.T - rho)
             dx = (tt - dy @ A) * d
             for _ in range(max_refine):
@@ -107,6 +121,7 @@ def solve(A, b, c, u, eps=1e-10, delta=0.02, r=0.9, pivot_floor=1e-6, refine_tol
                 need = np.abs(e).max(axis=1) > etol
                 if not need.any():
                     break
+                nrefs += live & need
                 eta = ldl_solve(L, D, np.where(need[:, None], e, 0.0))
                 dx = dx + d * (eta @ A)
                 dy = dy - eta
@@ -130,4 +145,5 @@ def solve(A, b, c, u, eps=1e-10, delta=0.02, r=0.9, pivot_floor=1e-6, refine_tol
         normr0 = np.where(live, normr, normr0); norms0 = np.where(live, norms, norms0)
     store(live, max_iter)
     out["status"], out["iters"] = status, iters
+    out["nrefs"], out["floored"], out["guard_ratio"] = nrefs, floored, guard_ratio
     return out

@@ -29,13 +29,14 @@ def first_covering(mk, n):
 
 
 @functools.lru_cache(maxsize=None)
-def make(mk, n, B=B_EVERY, seed=None):
-    """The batch of a test (shared, read-only): mk kept rows, n columns, every LP with its own matrix."""
+def make(mk, n, B=B_EVERY, seed=None, with_x0=False):
+    """The batch of a test (shared, read-only): mk kept rows, n columns, every LP with its own matrix.  ``with_x0``: (the
+    batch, the interior point its row bounds are built around)."""
     seed = 300 + sum(first_covering(mk, n)) if seed is None else seed
-    glp = make_general(mk, n, B, seed, per_problem_A=True, fixed=1, mixed_u=True, kinds=kinds(mk))
-    for a in (glp.a, glp.b, glp.c, glp.l, glp.u, glp.A.data):
+    glp, x0 = make_general(mk, n, B, seed, per_problem_A=True, fixed=1, mixed_u=True, kinds=kinds(mk), with_x0=True)
+    for a in (glp.a, glp.b, glp.c, glp.l, glp.u, glp.A.data, x0):
         a.setflags(write=False)
-    return glp
+    return (glp, x0) if with_x0 else glp
 
 
 def scaled_rows(glp, factor):
@@ -113,9 +114,9 @@ B_TRAJ = 12
 TRAJ_QUANTITIES = ("x", "y", "z", "s", "pobj", "dobj")
 
 
-def trajectory_lp(point):
+def trajectory_lp(point, with_x0=False):
     mk, n = TRAJECTORY_POINTS[point]
-    return make(mk, n, B_TRAJ, 7000 + mk)
+    return make(mk, n, B_TRAJ, 7000 + mk, with_x0)
 
 
 def _run_reference(blp, k, perm=None):

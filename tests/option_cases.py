@@ -227,9 +227,10 @@ def report(lines):
             f.write("\n".join(lines) + "\n")
 
 
-def assert_on_row(row, got):
-    """Every LP of the batch, every quantity of the case and every k of the row against the reference at the row's options."""
-    case, ks = row.case, row_ks(row)
+def assert_on_row(row, got, ks=None):
+    """Every LP of the batch, every quantity of the case and every k of the row (``ks``: default ``row_ks``) against the
+    reference at the row's options."""
+    case, ks = row.case, row_ks(row) if ks is None else ks
     ref, tol = tj.reference(case.id, row.opts, ks), tj.tolerance(case.id, row.opts, ks)
     n = ref[ks[0]]["status"].size
     dev = {k: {q: tj.deviation(got[k][q], ref[k][q]) for q in tj.quantities(case)} for k in ks}

@@ -51,17 +51,22 @@ def per_problem(base, seed, kinds, fixed):
 
 
 @functools.lru_cache(maxsize=None)
-def make(point, B=B_EVERY, seed=None):
-    """The batch of a test (shared, read-only): ``gbc.kinds`` rows (none dropped), two fixed columns, u with +inf, finite and 0."""
+def make(point, B=B_EVERY, seed=None, with_x0=False):
+    """The batch of a test (shared, read-only): ``gbc.kinds`` rows (none dropped), two fixed columns, u with +inf, finite and 0.
+    ``with_x0`` (a dense point): (the batch, the interior point its row bounds are built around)."""
     mk, n, density, _, _ = POINTS[point]
     seed = 500 + mk if seed is None else seed
+    x0 = None
     if density is None:
-        glp = make_general(mk, n, B, seed, per_problem_A=True, fixed=2, mixed_u=True, kinds=gbc.kinds(mk))
+        glp, x0 = make_general(mk, n, B, seed, per_problem_A=True, fixed=2, mixed_u=True, kinds=gbc.kinds(mk), with_x0=True)
     else:
         base = make_sparse_general(mk, n, B, seed, density, fixed=2, mixed_u=True, kinds=gbc.kinds(mk))
         glp = per_problem(base, seed + 1, gbc.kinds(mk), 2)
     for v in (glp.a, glp.b, glp.c, glp.l, glp.u, glp.A.data):
         v.setflags(write=False)
+    if with_x0:
+        assert x0 is not None, point
+        return glp, x0
     return glp
 
 
@@ -96,8 +101,8 @@ B_TRAJ = 12
 TRAJ_QUANTITIES = gbc.TRAJ_QUANTITIES
 
 
-def trajectory_lp(point):
-    return make(point, B_TRAJ, 7100 + POINTS[point][0])
+def trajectory_lp(point, with_x0=False):
+    return make(point, B_TRAJ, 7100 + POINTS[point][0], with_x0)
 
 
 @functools.lru_cache(maxsize=None)

@@ -14,9 +14,10 @@ import bounded_twin
 SHAPES = [(16, 32), (16, 48), (16, 64), (32, 64), (32, 96), (32, 128)]   # the slack-aware kernels (MP, NP)
 
 
-def make_general(m, n, B, seed, per_problem_A=False, mixed_u=False, kinds=None, fixed=0):
+def make_general(m, n, B, seed, per_problem_A=False, mixed_u=False, kinds=None, fixed=0, with_x0=False):
     """A feasible, bounded GeneralLP batch: rows by kind -- 'eq' (a == b), 'rng' (a < b), 'le' (b only), 'ge' (a only), 'free'
-    (dropped) -- around a point x0 inside [l, u]; row 0 is a '<=' row with positive coefficients, which bounds x >= l."""
+    (dropped) -- around a point x0 inside [l, u]; row 0 is a '<=' row with positive coefficients, which bounds x >= l.
+    ``with_x0``: return (the batch, x0)."""
     rng = np.random.default_rng(seed)
     P = B if per_problem_A else 1
     A = rng.uniform(-1, 1, (P, m, n))
@@ -48,7 +49,8 @@ def make_general(m, n, B, seed, per_problem_A=False, mixed_u=False, kinds=None, 
         Asp._shape = (m, n)
     else:
         Asp = SparseMatrix(matrix=A[0])
-    return GeneralLP(Asp, b, c, a=a, l=l, u=u, f=rng.uniform(-1, 1, B))
+    glp = GeneralLP(Asp, b, c, a=a, l=l, u=u, f=rng.uniform(-1, 1, B))
+    return (glp, x0) if with_x0 else glp
 
 
 def highs_general(glp, k):

@@ -19,9 +19,10 @@ def mixed_kinds(m):
     return ["le"] + [KINDS[i % len(KINDS)] for i in range(m - 1)]
 
 
-def make_sparse_general(m, n, B, seed, density, fixed=0, mixed_u=False, kinds=None):
+def make_sparse_general(m, n, B, seed, density, fixed=0, mixed_u=False, kinds=None, with_x0=False):
     """``make_general``'s batch with a SPARSE shared A: about ``density`` of the entries of rows 1.. are non-zero, every
-    column has one at least, row 0 is dense and positive.  ``kinds``: the row kinds (default ``mixed_kinds(m)``)."""
+    column has one at least, row 0 is dense and positive.  ``kinds``: the row kinds (default ``mixed_kinds(m)``);
+    ``with_x0``: return (the batch, the interior point the row bounds are built around)."""
     kinds = mixed_kinds(m) if kinds is None else kinds
     rng = np.random.default_rng(seed)
     mask = rng.uniform(size=(m, n)) < density
@@ -44,7 +45,8 @@ def make_sparse_general(m, n, B, seed, density, fixed=0, mixed_u=False, kinds=No
             b[:, i] = Ax[:, i] + rng.uniform(0.1, 1, B)
         elif k == "ge":
             a[:, i] = Ax[:, i] - rng.uniform(0.1, 1, B)
-    return GeneralLP(SparseMatrix(matrix=A), b, g.c, a=a, l=g.l, u=g.u, f=g.f)
+    glp = GeneralLP(SparseMatrix(matrix=A), b, g.c, a=a, l=g.l, u=g.u, f=g.f)
+    return (glp, x0) if with_x0 else glp
 
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------

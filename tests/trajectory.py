@@ -21,7 +21,7 @@ import bounded_twin
 import test_kernel_variants as tkv
 import test_workgroup_kernel_plans as twp
 from pycllp_amd import problems
-from pycllp_amd.lp import EqualityLP, SparseMatrix, StandardLP
+from pycllp_amd.lp import EqualityLP, GeneralLP, SparseMatrix, StandardLP
 from test_general_solver import make_general
 from test_sparse_general_solver import make_sparse_general
 
@@ -76,6 +76,54 @@ def degenerate(lp):
     return EqualityLP(SparseMatrix(matrix=A), b, c, 0.0)
 
 
+def bounded_general(key):
+    """(the GeneralLP batch of a bounded input key, the point x0 strictly inside [l, u] its row bounds are built around)."""
+    what = key[0]
+    if what in MORE_BOUNDED:                                 # per-problem matrices (tests/bounded_cases.py): not banded
+        return MORE_BOUNDED[what](key)
+    if what == "bounded-dense":
+        _, mk, n, nb, seed = key
+        glp, x0 = make_general(mk, n, nb, seed=seed, mixed_u=True, fixed=2, with_x0=True)
+    elif what == "bounded-sparse":
+        _, mk, n, nb, density, seed = key
+        kinds = tkv.bounded_kinds(mk)
+        glp, x0 = make_sparse_general(len(kinds), n, nb, seed, density=density, fixed=2, mixed_u=True, kinds=kinds, with_x0=True)
+    elif what == "bounded-image":
+        _, mk, n, nb, seed = key
+        kinds = tkv.bounded_kinds(mk)
+        glp, x0 = make_general(len(kinds), n, nb, seed, kinds=kinds, fixed=2, mixed_u=True, with_x0=True)
+    else:
+        raise KeyError(key)
+    return tkv.banded(glp), x0
+
+
+def degenerate_bounded(glp, x0, seed=36):
+    """The GeneralLP batch ``glp`` (one matrix, or one per LP) with its last kept row replaced by row 3 + 1e-6 noise (a sparse A:
+    noise = the row it replaces, as in ``degenerate``; a matrix per LP: its own noise) and both rows made equality rows through
+    x0, the interior point the batch is built around: a = b = A x0 there.  Bounds, fixed columns and costs stay.  The slacks of
+    the two rows are fixed, so M = A^ D A^' is singular to 1e-12 as in ``degenerate``, and b^ stays in the range of A^.
+    Refinement stagnates on such a matrix (an LP spends all its passes or none), at a residual of 1e-9 .. 1e-7 (1 + |b|) that
+    the noise decides; ``seed`` is one under which every input of tests/bounded_cases.py has, at every k, an LP below
+    1e-8 (1 + |b|), so that refine_tol = 1e-8 is a row of its own (test_bounded_options.py asserts it)."""
+    P = glp.A.nproblems
+    A = np.stack([np.asarray(glp.A.todense(i) if P > 1 else glp.A.todense(), dtype=np.float64) for i in range(P)])
+    kept = np.flatnonzero(np.isfinite(glp.a).any(axis=0) | np.isfinite(glp.b).any(axis=0))
+    last = int(kept[-1])
+    assert 3 in kept and last > 3
+    rs = np.random.RandomState(seed)
+    A[:, last] = A[:, 3] + 1e-6 * (rs.randn(P, A.shape[2]) if (A != 0).mean() > 0.5 else A[:, last])
+    a, b = glp.a.copy(), glp.b.copy()
+    for i in (3, last):
+        a[:, i] = b[:, i] = (A[:, i] * x0).sum(axis=1)
+    if P > 1:
+        m, n = A.shape[1:]
+        Asp = SparseMatrix(np.repeat(np.arange(m), n), np.tile(np.arange(n), m), A.reshape(P, -1))
+        Asp._shape = (m, n)
+    else:
+        Asp = SparseMatrix(matrix=A[0])
+    return GeneralLP(Asp, b, glp.c.copy(), a=a, l=glp.l.copy(), u=glp.u.copy(), f=np.array(glp.f))
+
+
 def image_bounded_rows(n, shape):
     """The most kept rows (<= 16 MB) of a dense bounded form with n columns whose image fits beside one wave area of the
     bounded kernel while its term tables do not: the bounded case of a dense-image point 'at its own kept-row count'."""
@@ -116,17 +164,10 @@ def inputs(key):
         case = key[1]
         lp = twp.make_case(case)
         return _frozen(head(lp, min(B_BIG if case[0] == "big" else B, lp.nproblems)))
-    if what == "bounded-dense":
-        _, mk, n, nb, seed = key
-        return tkv.banded(make_general(mk, n, nb, seed=seed, mixed_u=True, fixed=2))
-    if what == "bounded-sparse":
-        _, mk, n, nb, density, seed = key
-        kinds = tkv.bounded_kinds(mk)
-        return tkv.banded(make_sparse_general(len(kinds), n, nb, seed, density=density, fixed=2, mixed_u=True, kinds=kinds))
-    if what == "bounded-image":
-        _, mk, n, nb, seed = key
-        kinds = tkv.bounded_kinds(mk)
-        return tkv.banded(make_general(len(kinds), n, nb, seed, kinds=kinds, fixed=2, mixed_u=True))
+    if what in ("bounded-dense", "bounded-sparse", "bounded-image"):
+        return bounded_general(key)[0]
+    if what == "degenerate-bounded":
+        return degenerate_bounded(*bounded_general(key[1]))
     if what == "degenerate":
         return _frozen(degenerate(inputs(key[1])))
     if what in MORE_INPUTS:                                  # input keys of tests/option_cases.py
@@ -138,6 +179,7 @@ def inputs(key):
 
 
 MORE_INPUTS = {}
+MORE_BOUNDED = {}                                            # input keys that ``bounded_general`` takes from elsewhere
 Problem = collections.namedtuple("Problem", "A b c u f bmap shared tail")
 
 
@@ -148,8 +190,10 @@ def problem(key, bounded):
     lp = inputs(key)
     if bounded:
         blp, bmap = lp.to_bounded_equality_form()
-        A = np.asarray(blp.A.todense(), dtype=np.float64)
-        return Problem((A,), blp.b, blp.c, blp.u, np.broadcast_to(blp.f, (blp.nproblems,)), bmap, True, True)
+        shared = blp.A.nproblems == 1
+        As = (np.asarray(blp.A.todense(), dtype=np.float64),) if shared else \
+            tuple(np.asarray(blp.A.todense(i), dtype=np.float64) for i in range(blp.nproblems))
+        return Problem(As, blp.b, blp.c, blp.u, np.broadcast_to(blp.f, (blp.nproblems,)), bmap, shared, True)
     shared = lp.A.nproblems == 1
     As = tuple(np.asarray(lp.A.todense(i), dtype=np.float64) for i in range(lp.nproblems)) if not shared else \
         (np.asarray(lp.A.todense(), dtype=np.float64),)
@@ -198,7 +242,8 @@ def probe_entry(P):
 
 # ---- the reference --------------------------------------------------------------------------------------------------------
 def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, start=None, **opts):
-    """The reference's results after k iterations: dict(x, y, z[, s], pobj, dobj, status, iters, nrefs, aty).  ``perm``: seed of
+    """The reference's results after k iterations: dict(x, y, z[, s], pobj, dobj, status, iters, nrefs, aty; a bounded case: also
+    the twin's floored and guard_ratio, aty over the GeneralLP's own columns, a matrix per LP where the case has one).  ``perm``: seed of
     a row-and-column permutation under which the LPs are solved (results mapped back); ``r_scale``: factor on the step
     fraction r; ``a_scale``: factor on ``probe_entry`` of A; ``opts``: further fields of the oracle's options (``r``: the step
     fraction ``r_scale`` multiplies, default 0.9); ``start``: (x0, y0, z0) a warm case starts from in place
@@ -228,8 +273,12 @@ def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, start=None, **op
     As = [np.ascontiguousarray(A[rows][:, cols]) for A in As]
     b, c = P.b[:, rows], P.c[:, cols]
     if bounded:
-        r = bounded_twin.solve(As[0], b, c, P.u[:, cols], max_iter=k, r=r_frac, **opts)
-        r["nrefs"] = np.zeros(nb, dtype=np.int32)
+        u = P.u[:, cols]
+        if P.shared:
+            r = bounded_twin.solve(As[0], b, c, u, max_iter=k, r=r_frac, **opts)
+        else:
+            each = [bounded_twin.solve(As[i], b[i:i + 1], c[i:i + 1], u[i:i + 1], max_iter=k, r=r_frac, **opts) for i in range(nb)]
+            r = {q: np.concatenate([e[q] for e in each]) for q in each[0]}
     else:
         flags = ORACLE_FLAGS[case.kind] | (AUTOSCALE if "autoscale" in modes(case) else 0)
         x0, y0, z0 = (start_point(case, P) if start is None else start) if "warm" in modes(case) else (None,) * 3
@@ -253,6 +302,9 @@ def run_reference(case, k, perm=None, r_scale=1.0, a_scale=1.0, start=None, **op
     if case.family in STORES_ITS_OWN_OBJECTIVES:
         out["pobj"], out["dobj"] = (P.c * out["x"]).sum(axis=1), (P.b * out["y"]).sum(axis=1)
     if bounded:
+        # A^'y^ over the GeneralLP's own columns: over a slack column it is y^ itself, which a degenerate case does not determine
+        out["aty"] = out["aty"][:, :P.bmap.l.shape[1]]
+        out["floored"], out["guard_ratio"] = r["floored"], r["guard_ratio"]
         out["x"], out["y"], out["z"], out["s"] = P.bmap.general(out["x"], out["y"], out["z"], out["s"])
     return out
 
@@ -263,7 +315,8 @@ def a_transpose_y(P, y):
 
 def quantities(case):
     if case.mode == "degenerate":
-        return ("x", "z", "aty")       # y along the near-dependent direction is not determined (spread ~ 1e-7)
+        # y along the near-dependent direction is not determined (spread ~ 1e-7)
+        return ("x", "z", "s", "aty") if case.kind == "bounded" else ("x", "z", "aty")
     return QUANTITIES + (("s",) if case.kind == "bounded" else ())
 
 
@@ -321,10 +374,20 @@ def tolerance(cid, opts=(), ks=None):
 
 
 # ---- the GPU --------------------------------------------------------------------------------------------------------------
+# family of a bounded case -> (the plugin that solves it, the ``kernel`` it must report); 'perA-*': a matrix per LP
+BOUNDED_PLUGINS = {"slack": ("hip_general_primal_normal", "bounded group"),
+                   "tables": ("hip_sparse_general_primal_normal", "bounded wave"),
+                   "image": ("hip_sparse_general_primal_normal", "bounded wave"),
+                   "perA-group": ("hip_general_batch_primal_normal", "bounded group per-problem"),
+                   "perA-wave": ("hip_sparse_general_batch_primal_normal", "bounded wave per-problem")}
+
+
 def assert_served(case, info, lp, solver):
     if case.kind == "bounded":
-        assert solver.kernel == ("bounded group" if case.family == "slack" else "bounded wave"), solver.kernel
-    if case.where is None:                                   # the block kernel by flag, whatever its plan
+        assert solver.kernel == BOUNDED_PLUGINS[case.family][1], solver.kernel
+    if case.family.startswith("perA-"):                      # the compiled shape: lane groups (MP, NP), wave kernel (MB, NQ)
+        assert info.get("group_shape" if case.family == "perA-group" else "wave_shape") == case.where, info
+    elif case.where is None:                                # the block kernel by flag, whatever its plan
         assert info.get("kernel") == "block" and "wave_shape" not in info, info
     elif case.family in ("block", "big"):
         twp.assert_served_by(info, case.where, lp, grid=lp.nproblems)
@@ -349,15 +412,18 @@ def kernel_results(case, ks=None, seen=None, **opts):
     out = {}
     if case.kind == "bounded":
         P = problem(case.key, True)
-        name = "hip_general_primal_normal" if case.family == "slack" else "hip_sparse_general_primal_normal"
+        name = BOUNDED_PLUGINS[case.family][0]
+        n = P.bmap.l.shape[1]
         for k in ks:
-            s = solver_registry[name](device="cuda:0", hsd=False, autoscale=False, max_iter=k, **opts)
+            s = solver_registry[name](device="cuda:0", hsd=False, autoscale=False, max_iter=k,
+                                      **dict({"flags": case.flags} if case.flags else {}, **opts))
             lp.init(s)
             lp.solve(s)
             assert_served(case, s.launch_info(), lp, s)
             if seen is not None:
                 seen.append(s.launch_info())
             out[k] = dict(x=s.x, y=s.y, z=s.z, s=s.s, pobj=s.primal_obj, dobj=s.dual_obj, status=s.status, iters=s.iters)
+            out[k]["aty"] = a_transpose_y(P, P.bmap.sign * np.asarray(s.y)[:, P.bmap.rows])[:, :n]
         return out
     P = problem(case.key, False)
     dense = case.family in ("slack", "group") or (case.family == "big" and case.where[2] == "mfma")
