@@ -129,6 +129,14 @@ extern "C" {
                                          lane-group kernel where the LP fills a compiled shape exactly (m = MP, n = NP) and a
                                          full-shape instantiation would serve it; the results are the same bits.  The other
                                          entries have no such instantiation and ignore the flag. */
+#define PYCLLP_FLAG_EXACT_NORMS 1024 /* diagnostic: the lane-group kernels of pycllp_hip_dense_solve (plain and predictor-corrector
+                                        step) take their stop and growth tests on the square roots of the two residual norms in
+                                        every pass, as they do of themselves only where the tests on the squared norms are not
+                                        decided (csrc/ipm_group.inc, stop_verdict); status, iteration counts and vectors are the
+                                        same bits.  The kernels that keep their square roots (PYCLLP_FLAG_HSD, upper bounds,
+                                        per-problem matrices, the sparse path) ignore it; pycllp_hip_sparse_solve_bounded and
+                                        pycllp_hip_sparse_solve_batch_bounded, which refuse PYCLLP_FLAG_FORCE_GUARD_PATH, refuse it
+                                        likewise (PYCLLP_E_BADARG). */
 #define PYCLLP_FLAG_BLOCK_KERNEL 64 /* sparse solver: use the workgroup-per-LP kernel (ipm_block_kernel) even where the
                                        register-resident wavefront-per-LP kernel covers the problem (diagnostic / A-B runs;
                                        results agree to rounding)                                                  */

@@ -17,6 +17,7 @@ FLAG_BLOCK_KERNEL = 64
 FLAG_PREDCORR = 128
 FLAG_AUTOSCALE_PER_LP = 256
 FLAG_GENERIC_SHAPE = 512
+FLAG_EXACT_NORMS = 1024
 
 
 class Opts(ctypes.Structure):

@@ -174,7 +174,8 @@ inline int check_restricted(const char* entry, const void* h, long B, bool alway
 // what the entries with upper bounds reject: on the lane-group kernels, and on the wave kernel
 static constexpr int kBoundedRejected = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL |
                                         PYCLLP_FLAG_NO_SLACK_PATH;
-static constexpr int kWaveBoundedRejected = kBoundedRejected | PYCLLP_FLAG_BLOCK_KERNEL | PYCLLP_FLAG_FORCE_GUARD_PATH;
+static constexpr int kWaveBoundedRejected = kBoundedRejected | PYCLLP_FLAG_BLOCK_KERNEL | PYCLLP_FLAG_FORCE_GUARD_PATH |
+                                            PYCLLP_FLAG_EXACT_NORMS;   // (the diagnostic flags; the entries' sentence names the first)
 
 // ---- bodies of abi_sparse.hip that entries of the dense handle run ----
 // The sparse handle of a matrix given as host CSR arrays (validated by the caller): what pycllp_hip_sparse_init builds behind

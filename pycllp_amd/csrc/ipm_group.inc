@@ -163,6 +163,55 @@ __device__ __forceinline__ double grp_max(double v) {
     if (MP == 32) v = row_pair_max(v);
     return v;
 }
+// ---- stop and growth tests of ipm_group_kernel on the SQUARES of the two residual norms ----
+// The norms |rho| and |sigma| are only ever compared: with the tolerances, with ten times their value one iteration earlier, with
+// the growth floor, and for finiteness.  Two correctly rounded square roots per iteration bought nothing else.  The kernel
+// carries r2 = |rho|^2 and s2 = |sigma|^2 and keeps the previous pass's as squares (r2_0, s2_0; +inf before the first pass, where
+// the norms had 1e300: a finite norm is below 2^512, so "greater than ten times it" is false under either).
+//
+// ALL CLEAR, the verdict of all but a pass or two of an LP: no test holds, decided on the squares with a factor of two to spare
+// where an ulp decides on the square roots.  With h = fl(s / 2) (exact, or the nearest subnormal) and P = fl(T |T|):
+//   (a)  h > P    =>  "sqrt(s) <= T" fails                (s >= 2 h - 2^-1074 > T^2: sqrt(s) > T, and rounding is monotone)
+//   (b)  h < s0   =>  "sqrt(s) > 10 sqrt(s0)" fails       (s0 > 0 and s <= 3 s0: sqrt(s) < 1.74 sqrt(s0))
+//   (c)  h < P    =>  "sqrt(s) > FLOOR T" fails           (T > 0 and s < 4 T^2: sqrt(s) < 2 T)
+// and the pass is clear if gam is finite, (a) holds for r2 or for s2 or gam fails its own test, and (b) or (c) holds for each of
+// r2 and s2.  All three compares are strict, which is what makes them safe where a product underflows: a P below 2^-1022 is
+// within 2^-1075 of T^2, and h and P are then multiples of 2^-1074 that differ.  An overflowed P, a NaN or an infinite square
+// fail the compares they stand in ((c) holds against P = +inf, rightly: T > 2^511).  T |T| has the sign of a negative T (a
+// negative eps), for which nothing is <= T and everything above FLOOR T.  tests/test_norm_squares.py restates the three in numpy
+// against the square roots.  Two multiplies and three compares per norm, no constant but 1/2.
+// THE EXACT PATH, every other pass of an LP -- as a rule the one it ends with -- and every pass under PYCLLP_FLAG_EXACT_NORMS: the
+// text these kernels had, the square roots of r2, s2, r2_0, s2_0 (the last two are the very norms the previous pass tested) and
+// the comparisons on them.  A cold branch of the wave.  (A middle tier that decided each comparison on the squares behind a
+// band of 2^-40 was built as well: its mask arithmetic cost the (32, 96) predictor-corrector kernels spilt VGPRs and every
+// kernel about twenty SGPRs spilt to lanes, for one pass per LP; profiles/swap_copies_norm_squares.)
+// Returns the status the pass ends with, or -1: none of the tests holds.  No cross-lane operation: callable under any mask;
+// only `active` lanes send the wave down the exact path.
+__device__ __forceinline__ int stop_verdict_exact(double r2, double s2, double gam, double po, double tol_r, double tol_s,
+                                                  double r2_0, double s2_0, double eps) {
+    const double normr = sqrt(r2), norms = sqrt(s2), normr0 = sqrt(r2_0), norms0 = sqrt(s2_0);
+    if (!(isfinite(normr) && isfinite(norms) && isfinite(gam))) return PYCLLP_STATUS_NUMERICAL;
+    if (normr <= tol_r && norms <= tol_s && gam <= eps * (1.0 + fabs(po))) return PYCLLP_STATUS_OPTIMAL;
+    if (normr > 10.0 * normr0 && normr > PYCLLP_GROWTH_FLOOR * tol_r) return PYCLLP_STATUS_PRIMAL_INFEASIBLE;
+    if (norms > 10.0 * norms0 && norms > PYCLLP_GROWTH_FLOOR * tol_s) return PYCLLP_STATUS_DUAL_INFEASIBLE;
+    return -1;
+}
+__device__ __forceinline__ int stop_verdict(double r2, double s2, double gam, double po, double tol_r, double tol_s,
+                                            double r2_0, double s2_0, double eps, bool active, bool exact_always) {
+    const double Pr = tol_r * fabs(tol_r), Ps = tol_s * fabs(tol_s);
+    const double r_h = 0.5 * r2, s_h = 0.5 * s2;
+    const bool gam_ok = gam <= eps * (1.0 + fabs(po));
+    // (& and |: the compares in a row and mask arithmetic, where && and || become a branch each)
+    const bool clear = (bool)isfinite(gam) & ((r_h > Pr) | (s_h > Ps) | !gam_ok) & ((r_h < r2_0) | (r_h < Pr)) & ((s_h < s2_0) | (s_h < Ps));
+    const bool exact = active & (exact_always | !clear);
+    int v = -1;
+    if (__any(exact)) {
+        const int ve = stop_verdict_exact(r2, s2, gam, po, tol_r, tol_s, r2_0, s2_0, eps);
+        if (exact) v = ve;
+    }
+    return v;
+}
+
 // value held by lane k (0 <= k < MP, wave-uniform) of the caller's own group
 template <int MP>
 __device__ __forceinline__ double grp_bcast(double v, int k, int grp) {
@@ -335,7 +384,7 @@ struct GWave {
             asm volatile("" : "+v"(uba));
             ub = (const __attribute__((address_space(3))) double*)(size_t)uba;
         } else if constexpr (MP == 32) {
-            ur[0] = top_row_d(u); ur[1] = bottom_row_d(u);
+            ur[0] = both_rows_d(u, ur[1]);     // one swap (two calls would be two: the pinned copies are not shared)
         }
         const double* ac = Aimg + g;
         constexpr int RB = PYCLLP_AT_RB, NB = MP / RB;
@@ -525,8 +574,8 @@ struct GWave {
             if (AX) ax = quad_sum2(axp[0], axp[1]);
             ad = quad_sum2(adp[0], adp[1]);
         } else {
-            if (AX) ax = quad_sum(axp[0]);
-            ad = quad_sum(adp[0]);
+            if (AX) ax = quad_sum<true>(axp[0]);
+            ad = quad_sum<true>(adp[0]);
         }
     }
 
@@ -893,7 +942,9 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
     // (hoisted out of the persistent loop they cost ~30 registers and, at 256, scratch)
     auto gcol = [&](int q, int g_) { return (q < NCD) ? g_ + MP * q : nd + g_; };
     double b = 0.0, y = 0.0;
-    double tol_r = 0.0, tol_s = 0.0, etol = 0.0, normr0 = 1e300, norms0 = 1e300;
+    double tol_r = 0.0, tol_s = 0.0, etol = 0.0;
+    double r2_0 = __builtin_inf(), s2_0 = __builtin_inf();   // the squared norms of the previous pass (stop_verdict)
+    const bool exact_norms = (o.flags & PYCLLP_FLAG_EXACT_NORMS) != 0;
     double rho_pred = 0.0;     // b - A x of the CURRENT point, predicted exactly from the previous step:
     bool have_pred = false;    // rho+ = (1-theta) rho + theta (rho - A dx); lets the stop test run BEFORE the Newton work
     int it = 0;
@@ -941,7 +992,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 tol_r = o.eps * (1.0 + sqrt(nb2));
                 tol_s = o.eps * (1.0 + sqrt(nc2));
                 etol = o.refine_tol * (1.0 + sqrt(nb2));
-                normr0 = 1e300; norms0 = 1e300; it = 0; have_pred = false;
+                r2_0 = __builtin_inf(); s2_0 = __builtin_inf(); it = 0; have_pred = false;
                 if (warm) {
 #pragma unroll
                     for (int q = 0; q < NCG; q++) v[q] = vw[q];
@@ -971,12 +1022,11 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         }
         s2 = grp_sum<MP>(s2); gam = grp_sum<MP>(gam);
         const double po = grp_sum<MP>(pp);
-        const double du = grp_sum<MP>(b * y);
-        const double norms = sqrt(s2);
         double mu = PC ? 0.0 : o.delta * gam / (double)(n + m);     // PC: 0 for the predictor, set from its outcome below
 
-        // store a finished LP and hand the slot its next one from the device-wide queue
-        auto finalize = [&](int stat_) {
+        // store a finished LP and hand the slot its next one from the device-wide queue.  du = b'y of the point whose objectives
+        // are returned: summed by the caller, where an LP ends, and not in every pass (it is read nowhere else)
+        auto finalize = [&](int stat_, double du) {
             double sb = 1.0, sc = 1.0;
             const int go = w.ogl();
             int gro = grp;
@@ -1026,34 +1076,26 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         // So the prediction only NOMINATES a slot for finishing; the verdict is taken on rho = b - A x recomputed from x
         // (what the oracle tests every iteration, ipm_dense_ref.c ipm_one_path) -- one A*x for the wave, on the passes where
         // some slot is about to finish, i.e. about once per LP.
-        double normr_pred = sqrt(grp_sum<MP>(rho_pred * rho_pred));
+        double r2_pred = grp_sum<MP>(rho_pred * rho_pred);
         {
-            bool cand = false;
-            if (have_pred && live) {
-                cand = !(isfinite(normr_pred) && isfinite(norms) && isfinite(gam))
-                       || (normr_pred <= tol_r && norms <= tol_s && gam <= o.eps * (1.0 + fabs(po)))
-                       || (normr_pred > 10.0 * normr0 && normr_pred > PYCLLP_GROWTH_FLOOR * tol_r)
-                       || (norms > 10.0 * norms0 && norms > PYCLLP_GROWTH_FLOOR * tol_s);
-            }
+            // (a candidate is a slot for which one of the tests holds: the verdict's status is taken again below, on the true rho)
+            const bool tested = have_pred && live;
+            const bool cand = tested & (stop_verdict(r2_pred, s2, gam, po, tol_r, tol_s, r2_0, s2_0, o.eps, tested, exact_norms) >= 0);
             if (__any(cand)) {
                 double xs[NCG];
 #pragma unroll
                 for (int q = 0; q < NCG; q++) xs[q] = ok[q] ? x[q] : 0.0;
                 const double rho_true = b - w.A_times(xs);
-                const double normr_true = sqrt(grp_sum<MP>(rho_true * rho_true));
+                const double r2_true = grp_sum<MP>(rho_true * rho_true);
+                const int verdict_e = stop_verdict(r2_true, s2, gam, po, tol_r, tol_s, r2_0, s2_0, o.eps, cand, exact_norms);
                 int stat_e = PYCLLP_STATUS_ITERATION_LIMIT;
                 bool fin_e = false;
                 if (cand) {
-                    rho_pred = rho_true; normr_pred = normr_true;     // re-seed the recurrence with the true residual
-                    fin_e = true;
-                    if (!(isfinite(normr_true) && isfinite(norms) && isfinite(gam))) stat_e = PYCLLP_STATUS_NUMERICAL;
-                    else if (normr_true <= tol_r && norms <= tol_s && gam <= o.eps * (1.0 + fabs(po))) stat_e = PYCLLP_STATUS_OPTIMAL;
-                    else if (normr_true > 10.0 * normr0 && normr_true > PYCLLP_GROWTH_FLOOR * tol_r) stat_e = PYCLLP_STATUS_PRIMAL_INFEASIBLE;
-                    else if (norms > 10.0 * norms0 && norms > PYCLLP_GROWTH_FLOOR * tol_s) stat_e = PYCLLP_STATUS_DUAL_INFEASIBLE;
-                    else fin_e = false;
+                    rho_pred = rho_true; r2_pred = r2_true;     // re-seed the recurrence with the true residual
+                    if (verdict_e >= 0) { stat_e = verdict_e; fin_e = true; }
                 }
                 if (__any(fin_e)) {
-                    if (fin_e) finalize(stat_e);
+                    if (fin_e) finalize(stat_e, grp_sum<MP>(b * y));    // (per group, as grp_max inside finalize)
                     continue;   // the freed slot loads its next LP first, so the Newton pass below is never wasted
                 }
             }
@@ -1217,24 +1259,27 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             nref += need ? 1 : 0;
         }
         // ---- stop tests after the Newton work: only for a slot's first pass (no predicted rho yet), plus the NaN guard ----
-        const double normr = have_pred ? normr_pred : sqrt(grp_sum<MP>(rho * rho));
+        double r2 = r2_pred;
         const unsigned long long nf = __ballot(!isfinite(dy));
         const bool dy_bad = ((nf >> (grp * MP)) & gmask) != 0ull;
         int stat = PYCLLP_STATUS_ITERATION_LIMIT;
         bool fin = true;
-        if (have_pred) {
+        if (__all(have_pred || !live)) {    // (wave-uniform: no slot of the wave is on its first pass -- all but one pass in ~12)
             if (dy_bad) stat = PYCLLP_STATUS_NUMERICAL; else fin = false;
         } else {
-            if (!(isfinite(normr) && isfinite(norms) && isfinite(gam))) stat = PYCLLP_STATUS_NUMERICAL;
-            else if (normr <= tol_r && norms <= tol_s && gam <= o.eps * (1.0 + fabs(po))) stat = PYCLLP_STATUS_OPTIMAL;
-            else if (normr > 10.0 * normr0 && normr > PYCLLP_GROWTH_FLOOR * tol_r) stat = PYCLLP_STATUS_PRIMAL_INFEASIBLE;
-            else if (norms > 10.0 * norms0 && norms > PYCLLP_GROWTH_FLOOR * tol_s) stat = PYCLLP_STATUS_DUAL_INFEASIBLE;
+            const double r2_first = grp_sum<MP>(rho * rho);      // (whole groups, under a wave-uniform condition)
+            if (!have_pred) r2 = r2_first;
+            const int verdict = stop_verdict(r2, s2, gam, po, tol_r, tol_s, r2_0, s2_0, o.eps, live && !have_pred, exact_norms);
+            if (!have_pred && verdict >= 0) stat = verdict;
             else if (dy_bad) stat = PYCLLP_STATUS_NUMERICAL;
             else fin = false;
         }
 
+        double du_start = 0.0;       // b'y of the point this pass started from, for the LP that its step takes to the iteration limit
+        bool at_limit = false;
         if (!fin) {
             // ---- step (primal_normal.cl:122-156) ----
+            if (it + 1 >= o.max_iter) { du_start = grp_sum<MP>(b * y); at_limit = true; }     // (per group; before y moves)
             double dz[NCG];
             double th = 0.0;
 #pragma unroll
@@ -1252,14 +1297,14 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 z[q] = fma(theta, dz[q], z[q]);
                 v[q] = fma(theta, wv[q], v[q]);
             }
-            normr0 = normr; norms0 = norms;
+            r2_0 = r2; s2_0 = s2;
             rho_pred = fma(theta, e - rho, rho);   // b - A(x + theta dx) = (1-theta) rho + theta (rho - A dx)
             have_pred = true;
             it++;
             if (it >= o.max_iter) fin = true;   // status stays ITERATION_LIMIT
         }
         STAMP(8)
-        if (fin && live) finalize(stat);
+        if (fin && live) finalize(stat, at_limit ? du_start : grp_sum<MP>(b * y));
     }
     STAMP_FLUSH(o, blockIdx.x * wpb + wave)
 }

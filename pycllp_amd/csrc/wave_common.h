@@ -463,51 +463,77 @@ __device__ __forceinline__ void dot_step(double& a, double src, double l) {
 }
 
 // ---- cross-lane helpers ----------------------------------------------------------------------------------------
-// v[l] + v[l ^ 16], then + the other 32 lanes: the sum over the four 16-lane rows, identical in all of them
-__device__ __forceinline__ double quad_sum(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    v = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    lo = __double2loint(v); hi = __double2hiint(v);
-    auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
-}
 // Lane swaps move ACTIVE lanes only: v_permlane16_swap needs both 16-lane rows of a 32-lane group in EXEC, v_permlane32_swap the
 // whole wave.  Every call site says which it has.  They are VALU instructions: no LDS, no lgkmcnt.
+// A swap overwrites BOTH operands, so a double swapped with itself needs two copies of itself first.  Handed over as halves
+// (__double2loint / __double2hiint of one value, each swapped with itself) the compiler copies every half: four v_mov_b32 per
+// swap where the value stays live.  self_swap16 / self_swap32 make the two copies as doubles -- the pin keeps them 64-bit
+// values in registers of their own, one v_mov_b64 each (none where the value dies) -- and swap the halves of those.
+//   r0 / r1 <- [0] / [1] of the self-swap: v of rows (0, 0, 2, 2) / (1, 1, 3, 3) for the 16-lane swap, of lanes (0-31, 0-31) /
+//   (32-63, 32-63) for the 32-lane swap
+__device__ __forceinline__ void self_swap16(double v, double& r0, double& r1) {
+    double a = v, b = v;
+    asm("" : "+v"(a), "+v"(b));
+    auto l = __builtin_amdgcn_permlane16_swap(__double2loint(a), __double2loint(b), false, false);
+    auto h = __builtin_amdgcn_permlane16_swap(__double2hiint(a), __double2hiint(b), false, false);
+    r0 = __hiloint2double(h[0], l[0]);
+    r1 = __hiloint2double(h[1], l[1]);
+}
+__device__ __forceinline__ void self_swap32(double v, double& r0, double& r1) {
+    double a = v, b = v;
+    asm("" : "+v"(a), "+v"(b));
+    auto l = __builtin_amdgcn_permlane32_swap(__double2loint(a), __double2loint(b), false, false);
+    auto h = __builtin_amdgcn_permlane32_swap(__double2hiint(a), __double2hiint(b), false, false);
+    r0 = __hiloint2double(h[0], l[0]);
+    r1 = __hiloint2double(h[1], l[1]);
+}
+// v[l] + v[l ^ 16], then + the other 32 lanes: the sum over the four 16-lane rows, identical in all of them.  COPY64: through
+// self_swap16 / self_swap32, as the lane-group kernels call it; the wave and large-LP kernels (wreg_wave.h, ipm_big.hip), one
+// wavefront per SIMD and bound by latency, keep the halves and with them their machine code.  Same bits either way.
+template <bool COPY64 = false>
+__device__ __forceinline__ double quad_sum(double v) {
+    if constexpr (COPY64) {
+        double r0, r1;
+        self_swap16(v, r0, r1);
+        self_swap32(r0 + r1, r0, r1);
+        return r0 + r1;
+    } else {
+        int lo = __double2loint(v), hi = __double2hiint(v);
+        auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        v = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
+        lo = __double2loint(v); hi = __double2hiint(v);
+        auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
+    }
+}
 // a and b are partial sums per 16-lane row: the sum of a over the four rows arrives in rows 0 and 2, that of b in rows 1 and 3.
 // Per lane (own + lane ^ 16) + (lane ^ 32) with operands commuted: the bits of two __shfl_xor stages.  Whole wave.
 __device__ __forceinline__ double quad_sum2(double a, double b) {
     auto l = __builtin_amdgcn_permlane16_swap(__double2loint(a), __double2loint(b), false, false);   // [0] = rows (a0, b0, a2, b2)
     auto h = __builtin_amdgcn_permlane16_swap(__double2hiint(a), __double2hiint(b), false, false);   // [1] = rows (a1, b1, a3, b3)
-    const double v = __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
+    double r0, r1;
+    self_swap32(__hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]), r0, r1);
+    return r0 + r1;
 }
-// v of the top / of the bottom 16-lane row of the caller's 32-lane group, in both rows ([0] = rows (0, 0, 2, 2), [1] = rows
-// (1, 1, 3, 3) of a self-swap).  Both rows of the group active.
+// v of the top / of the bottom 16-lane row of the caller's 32-lane group, in both rows.  Both rows of the group active.
+// (A caller that needs both takes them from ONE swap: both_rows_d.)
 __device__ __forceinline__ double top_row_d(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return __hiloint2double(b[0], a[0]);
+    double r0, r1;
+    self_swap16(v, r0, r1);
+    return r0;
 }
 __device__ __forceinline__ double bottom_row_d(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return __hiloint2double(b[1], a[1]);
+    double r0, r1;
+    self_swap16(v, r0, r1);
+    return r1;
 }
 // both halves of ONE self-swap: returns top_row_d(v), `bot` receives bottom_row_d(v).  Both rows of the group active.
 __device__ __forceinline__ double both_rows_d(double v, double& bot) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    bot = __hiloint2double(b[1], a[1]);
-    return __hiloint2double(b[0], a[0]);
+    double top;
+    self_swap16(v, top, bot);
+    return top;
 }
 // v rotated by 8 lanes inside the TOP 16-lane row of every 32-lane group (lane t takes lane t ^ 8's); the bottom rows keep
 // theirs: two v_mov_b32_dpp row_ror:8 row_mask:0x5, in place
@@ -522,16 +548,14 @@ __device__ __forceinline__ double ror8_top_d(double v) {
 // (+4 vector instructions, -2 LDS instructions and their wait): what that buys is latency, 42 against 73 cycles on a dependent
 // path (tools/dev/ubench_xchg.hip, profiles/lane_swaps).  Both rows of the group active.
 __device__ __forceinline__ double row_pair_sum(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
+    double r0, r1;
+    self_swap16(v, r0, r1);
+    return r0 + r1;
 }
 __device__ __forceinline__ double row_pair_max(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return fmax(__hiloint2double(b[0], a[0]), __hiloint2double(b[1], a[1]));
+    double r0, r1;
+    self_swap16(v, r0, r1);
+    return fmax(r0, r1);
 }
 // sum over the 16 lanes of each DPP row (identical inside the row)
 __device__ __forceinline__ double row_sum(double v) {
