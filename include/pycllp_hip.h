@@ -137,6 +137,12 @@ extern "C" {
                                         per-problem matrices, the sparse path) ignore it; pycllp_hip_sparse_solve_bounded and
                                         pycllp_hip_sparse_solve_batch_bounded, which refuse PYCLLP_FLAG_FORCE_GUARD_PATH, refuse it
                                         likewise (PYCLLP_E_BADARG). */
+#define PYCLLP_FLAG_PER_LP_FIRST_GRAM 2048 /* diagnostic: the lane-group kernels of pycllp_hip_dense_solve (plain and
+                                              predictor-corrector step) form the Gram matrix and A x of every LP's first iteration
+                                              on the matrix cores, as they do of themselves under PYCLLP_FLAG_WARM_START, instead of
+                                              taking them from the image that pycllp_hip_dense_init made of A (every LP starts at
+                                              x = z = 1; csrc/ipm_group.inc, GWave::gram_first; the 32-row shapes -- the others
+                                              form the product anyway); status, iteration counts and vectors are the same bits.  Ignored and refused where PYCLLP_FLAG_EXACT_NORMS is. */
 #define PYCLLP_FLAG_BLOCK_KERNEL 64 /* sparse solver: use the workgroup-per-LP kernel (ipm_block_kernel) even where the
                                        register-resident wavefront-per-LP kernel covers the problem (diagnostic / A-B runs;
                                        results agree to rounding)                                                  */

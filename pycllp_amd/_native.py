@@ -18,6 +18,7 @@ FLAG_PREDCORR = 128
 FLAG_AUTOSCALE_PER_LP = 256
 FLAG_GENERIC_SHAPE = 512
 FLAG_EXACT_NORMS = 1024
+FLAG_PER_LP_FIRST_GRAM = 2048
 
 
 class Opts(ctypes.Structure):

@@ -125,6 +125,23 @@ int pycllp_hip_dense_init(int m, int n, const double* A_dev, void* stream, pycll
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { pycllp_hip_dense_free(h); return set_err((int)e, "pack_A_kernel"); }
+    // the images of an LP's first Gram pass: the general variant's and, for [A_dense | I], the slack-aware variant's
+    const FirstGram& fg = kVariants[vi].first;
+    const int sl_len = h->variant_sl >= 0 ? kSlackVariants[h->variant_sl].first.len : 0;
+    if (fg.len + sl_len > 0) {
+        e = hipMalloc((void**)&h->first, sizeof(double) * (size_t)(fg.len + sl_len));
+        if (e != hipSuccess) { pycllp_hip_dense_free(h); return set_err((int)e, "hipMalloc(first Gram image)"); }
+        if (fg.len > 0) {
+            h->first_gen = h->first;
+            e = fg.launch(m, n, h->a_rm, h->first_gen, st);
+        }
+        if (e == hipSuccess && sl_len > 0) {
+            h->first_sl = h->first + fg.len;
+            e = kSlackVariants[h->variant_sl].first.launch(m, n, h->a_rm, h->first_sl, st);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { pycllp_hip_dense_free(h); return set_err((int)e, "first_gram_kernel"); }
+    }
     *handle = h;
     return 0;
 }
@@ -161,15 +178,19 @@ int pycllp_hip_dense_solve(pycllp_hip_dense* h, long B, const double* b_dev, con
     const bool hsd = (o.flags & PYCLLP_FLAG_HSD) != 0, pc = (o.flags & PYCLLP_FLAG_PREDCORR) != 0;
     DenseKernel k = hsd ? v.solve_hsd : (pc ? v.solve_pc : v.solve_group);
     bool full = false;
+    const double* first = h->first_gen;
     if (h->variant_sl >= 0 && !(o.flags & PYCLLP_FLAG_NO_SLACK_PATH)) {
+        first = h->first_sl;
         const SlackVariant& s = kSlackVariants[h->variant_sl];
         k = hsd ? s.solve_hsd : (pc ? s.solve_pc : s.solve_group);
         // an LP that fills the shape exactly goes to its full-shape instantiation, on the same plan
         const dense_launch_fn f = (hsd || pc) ? nullptr : s.full_group;
         if (f && h->m == s.mp && h->n == s.np && !(o.flags & PYCLLP_FLAG_GENERIC_SHAPE)) { k.launch = f; full = true; }
     }
+    // a warm start does not begin at x = z = 1, and the diagnostic flag asks for the product itself (the HSD kernel has no such path)
+    if (o.flags & (PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_PER_LP_FIRST_GRAM)) first = nullptr;
     const GroupPaArgs a = {h->m, h->n, B, h->a_rm, b_dev, c_dev, nullptr, x_dev, y_dev, z_dev, nullptr, pobj_dev, dobj_dev,
-                           status_dev, iters_dev, nullptr};
+                           status_dev, iters_dev, nullptr, first};
     hipError_t e = run_group(h, k, a, o, (hipStream_t)stream, full);
     if (e != hipSuccess) return set_err((int)e, "solve kernel launch");
     return 0;
@@ -303,6 +324,7 @@ void pycllp_hip_dense_free(pycllp_hip_dense* h) {
     if (h->sp) pycllp_hip_sparse_free(h->sp);
     if (h->pack) (void)hipFree(h->pack);
     if (h->a_rm) (void)hipFree(h->a_rm);
+    if (h->first) (void)hipFree(h->first);
     h->ring.destroy();
     delete h;
 }

@@ -17,6 +17,11 @@ struct NewtonArgs { int m, n; long B; const double *pack, *x, *z, *y, *b, *c; do
 typedef hipError_t (*newton_launch_fn)(const NewtonArgs&, const LaunchPlan&, DevOpts, hipStream_t);
 typedef hipError_t (*pack_launch_fn)(int m, int n, const double* A, double* pack, hipStream_t);
 
+// The image of an LP's first Gram pass (first_gram_kernel, ipm_dense.hip): its length in doubles and the launch that fills it
+// from the handle's row-major A [m, n]; read by the plain and predictor-corrector kernels of the same table row
+typedef hipError_t (*first_launch_fn)(int m, int n, const double* A, double* img, hipStream_t);
+struct FirstGram { int len; first_launch_fn launch; };   // len 0, launch null: the shape's kernels read no image
+
 struct Variant {
     int mp, np, apack;
     pack_launch_fn pack;
@@ -25,6 +30,7 @@ struct Variant {
     DenseKernel solve_pc;     // group-per-LP kernel with Mehrotra's predictor-corrector (PYCLLP_FLAG_PREDCORR)
     dense_plan_fn newton_plan;
     newton_launch_fn newton;
+    FirstGram first;
 };
 // slack-aware group kernels: (MP, NP) with NP - MP padded dense columns + the m identity columns
 // full_group: the full-shape instantiation of solve_group, launched on its plan, for a matrix with m == mp and n == np
@@ -33,6 +39,7 @@ struct SlackVariant {
     int mp, np;
     DenseKernel solve_group, solve_hsd, solve_pc, solve_bounded;
     dense_launch_fn full_group;
+    FirstGram first;          // (the full-shape instantiation reads it too: its Gram bits are the generic ones)
 };
 
 // one row per lane-group shape of GROUP_SHAPES (group_pa.h), in its order: the first that covers (m, n) is used, in both tables

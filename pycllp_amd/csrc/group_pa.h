@@ -36,12 +36,13 @@ struct GeoPA {
 // One launch of ipm_group_pa_kernel<MP, NP, SL> (ipm_group_pa.hip) or, with upper bounds, of ipm_bounded_pa_kernel<MP, NP>
 // (ipm_group_pabd.hip): A [B, m, a_cols] row-major, a_cols = n - m (SL) or n; u [B, n] and s: null without bounds; the outputs
 // of pycllp_hip_dense_solve / pycllp_hip_dense_solve_bounded; queue: a zeroed work-queue head.  Sets the kernel's dynamic LDS
-// itself.
+// itself.  `first` is dense_tab.h's (ipm_group_kernel on a shared A alone reads it).
 struct GroupPaArgs {
     int m, n; long B;
     const double *A, *b, *c, *u;
     double *x, *y, *z, *s, *pobj, *dobj;
     int *status, *iters, *queue;
+    const double* first = nullptr;   // shared A, plain and predictor-corrector kernels: the handle's first-pass image, or null
 };
 typedef hipError_t (*gpa_launch_fn)(const GroupPaArgs&, int grid, int block, int lds, DevOpts, hipStream_t);
 struct GroupPaVariant { int mp, np, sl; gpa_launch_fn launch; };

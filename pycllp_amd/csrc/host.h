@@ -113,6 +113,8 @@ struct pycllp_hip_dense {
     int m = 0, n = 0, mp = 0, np = 0, variant = -1;
     double* pack = nullptr;
     double* a_rm = nullptr;   // row-major copy of A [m,n] for the group kernel
+    double* first = nullptr;  // images of an LP's first Gram pass (dense_tab.h FirstGram), one allocation: the general variant's
+    double* first_gen = nullptr, *first_sl = nullptr;   // (first_gen) and the slack-aware variant's (first_sl); null: none
     QueueRing ring; // device work-queue heads of the group kernel
     mutable std::mutex info_mu;   // guards grid/block/lds/mp/np/sl/full (what launch_info and variant_info report: the LAST launch)
     int variant_sl = -1; // index into kSlackVariants when the last m columns of A are the identity, else -1
@@ -175,7 +177,7 @@ inline int check_restricted(const char* entry, const void* h, long B, bool alway
 static constexpr int kBoundedRejected = PYCLLP_FLAG_HSD | PYCLLP_FLAG_PREDCORR | PYCLLP_FLAG_WARM_START | PYCLLP_FLAG_WAVE_KERNEL |
                                         PYCLLP_FLAG_NO_SLACK_PATH;
 static constexpr int kWaveBoundedRejected = kBoundedRejected | PYCLLP_FLAG_BLOCK_KERNEL | PYCLLP_FLAG_FORCE_GUARD_PATH |
-                                            PYCLLP_FLAG_EXACT_NORMS;   // (the diagnostic flags; the entries' sentence names the first)
+                                            PYCLLP_FLAG_EXACT_NORMS | PYCLLP_FLAG_PER_LP_FIRST_GRAM;   // (the diagnostic flags; the entries' sentence names the first)
 
 // ---- bodies of abi_sparse.hip that entries of the dense handle run ----
 // The sparse handle of a matrix given as host CSR arrays (validated by the caller): what pycllp_hip_sparse_init builds behind

@@ -395,6 +395,57 @@ newton_kernel(int m, int n, long B, const double* __restrict__ pack, const doubl
 }
 
 #include "ipm_group.inc"
+
+// ------------------------------------------------------------------------------------------------
+// setup kernel of a handle: the Gram matrix and A x of an LP's first iteration (x = z = 1), which depend on A, m and n alone.
+// One workgroup of one wave runs gram_one<true> -- the very device function ipm_group_kernel would run on that pass -- on a
+// zeroed slab with x and d staged as that kernel stages them, and writes the image GWave::gram_first reads: the slab, then A x by
+// row.  (The slack columns' diagonal term is not in it: the solve kernel adds d_slack behind either route, as it did.)
+// ------------------------------------------------------------------------------------------------
+template <int MP, int NP, bool SL>
+__global__ void __launch_bounds__(64)
+first_gram_kernel(int m, int n, const double* __restrict__ Ag, double* __restrict__ img) {
+    using G_ = GeoG<MP, NP, SL>;
+    using W_ = GWave<MP, NP, SL>;
+    constexpr int NCD = G_::NCD, ND = G_::ND, AS = G_::AS;
+    const int nd = SL ? n - m : n;
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = threadIdx.x, gl = lane & (MP - 1), grp = lane / MP;
+    for (int i = lane; i < G_::AIMG; i += WAVE) {
+        const int r = i / AS, cidx = i % AS;
+        lds[i] = (r < m && cidx < nd) ? Ag[(size_t)r * n + cidx] : 0.0;
+    }
+    G_::fill_gram_table(lds, lane, WAVE);
+    W_ w;
+    w.lane = lane; w.gl = gl; w.grp = grp; w.m = m; w.n = n;
+    w.Aimg = lds;
+    w.slab0 = lds + G_::SHARED;
+    w.slab = w.slab0 + grp * G_::SLAB;
+    w.stage = w.slab0 + G_::G * G_::SLAB;
+    for (int i = lane; i < G_::G * G_::SLAB; i += WAVE) w.slab0[i] = 0.0;
+    // x = 1 and d = x * fast_rcp(z) of the start, formed as the solve kernel forms them (from values the compiler cannot fold)
+    double one = 1.0;
+    asm volatile("" : "+v"(one));
+    const double d1 = one * fast_rcp(one);
+    if (grp == 0) {
+#pragma unroll
+        for (int q = 0; q < NCD; q++) {
+            const bool okq = gl + MP * q < nd;
+            const int p = G_::kpos(gl + MP * q);
+            w.stage[p] = okq ? one : 0.0;
+            w.stage[ND + p] = okq ? d1 : 0.0;
+            w.stage[2 * ND + p] = 0.0;
+        }
+    }
+    __syncthreads();
+    double ax = 0.0, ad;
+    w.template gram_one<true>(0, ax, ad);
+    wave_lds_sync();
+    for (int i = lane; i < G_::SLAB; i += WAVE) img[i] = w.slab0[i];
+    if (W_::FIRST_SLAB > G_::SLAB && lane == 0) img[G_::SLAB] = 0.0;
+    if (lane < MP) img[W_::FIRST_SLAB + lane] = ax;
+}
+
 #include "ipm_group_hsd.inc"
 #include "ipm_group_slot.inc"
 #include "group_pa.h"
@@ -450,13 +501,40 @@ static LaunchPlan plan_group_pa(const DeviceLimits& d, long B, const DevOpts& o)
 
 template <int MP, int NP, bool SL, bool HSD = false, bool PC = false, bool FULL = false>
 static hipError_t launch_solve_group(const GroupPaArgs& a, const LaunchPlan& p, DevOpts o, hipStream_t st) {
-    auto kernel = HSD ? hsd_group_kernel<MP, NP, SL> : ipm_group_kernel<MP, NP, SL, PC, FULL>;
-    const hipError_t e = set_dyn_lds((const void*)kernel, p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, st, a.m, a.n, a.B, a.A, a.b, a.c, a.x, a.y, a.z, a.pobj,
-                       a.dobj, a.status, a.iters, a.queue, o);
+    if constexpr (HSD) {
+        auto kernel = hsd_group_kernel<MP, NP, SL>;
+        const hipError_t e = set_dyn_lds((const void*)kernel, p.lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, st, a.m, a.n, a.B, a.A, a.b, a.c, a.x, a.y, a.z, a.pobj,
+                           a.dobj, a.status, a.iters, a.queue, o);
+    } else {
+        auto kernel = ipm_group_kernel<MP, NP, SL, PC, FULL>;
+        const hipError_t e = set_dyn_lds((const void*)kernel, p.lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, st, a.m, a.n, a.B, a.A, a.b, a.c, a.x, a.y, a.z, a.pobj,
+                           a.dobj, a.status, a.iters, a.queue, o, a.first);
+    }
     return hipGetLastError();
 }
+
+// first_gram_kernel on GeoG<MP, NP, SL>: the image (first_len doubles) of a handle's A for ipm_group_kernel<MP, NP, SL, ...>
+template <int MP, int NP, bool SL>
+static hipError_t launch_first_gram(int m, int n, const double* A, double* img, hipStream_t st) {
+    using G = GeoG<MP, NP, SL>;
+    auto kernel = first_gram_kernel<MP, NP, SL>;
+    const int lds = (int)(sizeof(double) * (size_t)(G::SHARED + G::WSZ));
+    const hipError_t e = set_dyn_lds((const void*)kernel, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(WAVE), lds, st, m, n, A, img);
+    return hipGetLastError();
+}
+// ... or { 0, null } for a shape whose kernels do not read one (GWave::FIRST_IMAGE)
+template <int MP, int NP, bool SL>
+constexpr FirstGram first_gram_of() {
+    if constexpr (GWave<MP, NP, SL>::FIRST_IMAGE) return FirstGram{GWave<MP, NP, SL>::FIRST_LEN, launch_first_gram<MP, NP, SL>};
+    else return FirstGram{0, nullptr};
+}
+#define FIRST_GRAM(MP, NP, SL) first_gram_of<MP, NP, SL>()
 
 // The full-shape instantiation of the plain slack-aware kernel (ipm_group_kernel's FULL, for an LP with m = MP and n = NP: no
 // padded column), launched on the generic instantiation's plan (same geometry).  A shape whose full-shape kernel had scratch
@@ -489,11 +567,12 @@ static hipError_t launch_newton(const NewtonArgs& a, const LaunchPlan& p, DevOpt
     { plan_group<MP, NP, SL, (HSD) ? hsd_wpb<MP>() : PYCLLP_WPB>, launch_solve_group<MP, NP, SL, HSD, PC> }
 #define VARIANT(MP, NP) \
     { MP, NP, Geo<MP, NP>::APACK, launch_pack<MP, NP>, GROUP_KERNEL(MP, NP, false, false, false), \
-      GROUP_KERNEL(MP, NP, false, true, false), GROUP_KERNEL(MP, NP, false, false, true), plan_newton<MP, NP>, launch_newton<MP, NP> },
+      GROUP_KERNEL(MP, NP, false, true, false), GROUP_KERNEL(MP, NP, false, false, true), plan_newton<MP, NP>, launch_newton<MP, NP>, \
+      FIRST_GRAM(MP, NP, false) },
 #define SLACK_VARIANT(MP, NP) \
     { MP, NP, GROUP_KERNEL(MP, NP, true, false, false), GROUP_KERNEL(MP, NP, true, true, false), \
       GROUP_KERNEL(MP, NP, true, false, true), { plan_group<MP, NP, true, PYCLLP_WPB_BOUNDED>, launch_solve_bounded<MP, NP> }, \
-      full_group_kernel<MP, NP>() },
+      full_group_kernel<MP, NP>(), FIRST_GRAM(MP, NP, true) },
 #define PA_PLAN(MP, NP) { MP, NP, 0, plan_group_pa<MP, NP, false> }, { MP, NP, 1, plan_group_pa<MP, NP, true> },
 // ... with upper bounds: the same rule, at most PYCLLP_WPB_BOUNDED waves per workgroup
 #define PABD_PLAN(MP, NP) { MP, NP, 1, plan_group_pa<MP, NP, true, GeoPA<GeoG<MP, NP, true>>::wpb_capped(PYCLLP_WPB_BOUNDED)> },

@@ -11,6 +11,8 @@
 //     the diagonal blocks' lower tiles on v_mfma_f64_4x4x4_4b_f64, see gram_pair()), groups taking turns;
 //     its operands now come straight from ONE row-major image of A in LDS (odd row stride: the
 //     row-per-lane reads are conflict free, the MFMA-order reads see a harmless 2-way conflict);
+//   * an LP's FIRST Gram product is not formed at all without warm start: x = z = 1 there, so it is A A' whatever b and c are,
+//     and the wave copies it (and A 1) from an image the handle made once (first_gram_kernel; GWave::gram_first; MP = 32);
 //   * group reductions use DPP row operations (+ one lane swap between the two rows of a 32-lane group) instead of ds_bpermute;
 //   * the LDL' column sweep hands the RAW column (pivot included) through LDS, so no cross-lane pivot broadcast
 //     sits on the critical path: every lane derives 1/D_j itself from the broadcast read;
@@ -579,6 +581,53 @@ struct GWave {
         }
     }
 
+    // The Gram pass of an LP's FIRST iteration without warm start, from the handle's image (first_gram_kernel, ipm_dense.hip).
+    // Every LP starts at x = z = 1, so d is 1 in the real columns and 0 in padding whatever b and c are: the matrix gram_one<true>
+    // leaves in the slab and the A x it returns depend on A, m and n alone.  `img` holds them as first_gram_kernel got them from
+    // gram_one<true> itself: FIRST_SLAB doubles, the slab as that call left a zeroed one, then A x of row i at FIRST_SLAB + i.
+    // The whole wave copies the slab image into group g's slab, 16 bytes per lane and load, every load issued before the k-loop,
+    // which hides them (up to 32 registers across the loop, where gram_one holds more).  ad, the A (d t) sums -- they depend on
+    // c --, come from gram_one's k-loop without its multiplies, selects and MFMAs: the same fma chain over s on the same operands
+    // and the same sums across the 16-lane rows, so the same bits.  stage holds d t of the LP in k-layout (x and d are not read).
+    // Whole wave active, as gram_one.  (The slack columns' d on M's diagonal is the caller's, behind either route.)
+    // The 32-row shapes only.  At MP = 16 the pass has 8 to 16 MFMAs to save per LP and the copy costs as much: measured on
+    // 16 x 32, 65 536 LPs 1.337 -> 1.330 / 1.340 ms (inside the scatter), and 4 096 LPs -- every LP in a slot of its own, one wave
+    // per SIMD, nothing to hide a load behind -- 0.169 -> 0.171 ms, 0.172 with one load for the four groups (profiles/first_gram).
+    static constexpr bool FIRST_IMAGE = MP == 32;
+    static constexpr int FIRST_SLAB = (G_::SLAB + 1) & ~1;     // (16-byte pairs)
+    static constexpr int FIRST_LEN = FIRST_SLAB + MP;          // doubles of an image
+    __device__ __forceinline__ void gram_first(int g, const double* __restrict__ img, double& ax, double& ad) const {
+        typedef double double2_t __attribute__((ext_vector_type(2)));
+        constexpr int PAIRS = G_::SLAB / 2, NLD = (PAIRS + 63) / 64;
+        static_assert(G_::SLAB % 2 == 0, "the slab is copied in 16-byte pairs");
+        int lo_ = lane;                       // opaque copy: see ogl()
+        asm volatile("" : "+v"(lo_));
+        const double2_t* src = (const double2_t*)img + lo_;
+        double2_t* dst = (double2_t*)(slab0 + g * G_::SLAB) + lo_;
+        double2_t cp[NLD];
+#pragma unroll
+        for (int i = 0; i < NLD; i++)
+            if (PAIRS % 64 == 0 || 64 * i + lo_ < PAIRS) cp[i] = src[64 * i];
+        ax = img[FIRST_SLAB + (lo_ & (MP - 1))];
+        const int kg = lo_ >> 4, cc = lo_ & 15;
+        const double* pt = stage + 2 * ND + kg * KS;
+        const double* arow = Aimg + cc * AS + kg;
+        double adp[JB];
+#pragma unroll
+        for (int J = 0; J < JB; J++) adp[J] = 0.0;
+#pragma unroll
+        for (int s = 0; s < KS; s++) {
+            const double tk = pt[s];
+#pragma unroll
+            for (int J = 0; J < JB; J++) adp[J] = fma(arow[16 * J * AS + 4 * s], tk, adp[J]);
+        }
+#pragma unroll
+        for (int i = 0; i < NLD; i++)
+            if (PAIRS % 64 == 0 || 64 * i + lo_ < PAIRS) dst[64 * i] = cp[i];
+        if constexpr (MP == 32) ad = quad_sum2(adp[0], adp[1]);
+        else ad = quad_sum<true>(adp[0]);
+    }
+
     // Modified LDL' of every group's matrix at once, WITHOUT the Nocedal-Wright guard D_j = max(|D_j|, (theta_j/beta)^2, floor)
     // on the hot path: the sweep records whether it WOULD have bitten (some u_i^2 > beta^2 max(|D_j|, floor)) and returns that
     // verdict for the whole wave; if so (rare) the caller re-forms M and runs factor_guarded_inplace, which applies the guard
@@ -872,10 +921,16 @@ __global__ void __launch_bounds__(PYCLLP_WPB * 64)
 ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const double* __restrict__ bg,
                  const double* __restrict__ cg, double* __restrict__ xg, double* __restrict__ yg,
                  double* __restrict__ zg, double* __restrict__ pobj, double* __restrict__ dobj,
-                 int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue, DevOpts o) {
+                 int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue, DevOpts o,
+                 const double* __restrict__ first) {
     using G_ = GeoG<MP, NP, SL>;
     constexpr int G = G_::G, NCG = G_::NCG, NCD = G_::NCD, ND = G_::ND, JB = G_::JB, AS = G_::AS;
     static_assert(!FULL || (SL && !PC), "full-shape instantiations exist for the plain slack-aware kernels only");
+    // `first` (the handle's image of an LP's first Gram pass, or null: GWave::gram_first) is read by the 32-row instantiations
+    // (GWave::FIRST_IMAGE) but the two predictor-corrector kernels that fill the register file: with the path the slack-aware
+    // (32, 96) one and the general (32, 128) one spill 2 VGPRs each (the copy after the k-loop, rolled, or half of it: 11 to
+    // 49), so they keep the product
+    constexpr bool FIRST_IMAGE = GWave<MP, NP, SL>::FIRST_IMAGE && !(PC && ((SL && NP == 96) || (!SL && NP == 128)));
     const int nd = SL ? n - m : n;          // dense columns of A (the last m columns are the identity when SL)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
@@ -1124,18 +1179,23 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 // (a slot that carries rho -- every pass but an LP's first -- needs no A x from the Gram pass: -32 FMAs,
                 // -16 LDS reads, -4 shuffles per LP-iteration, round 3)
                 const bool carried = __shfl((int)have_pred, g * MP, WAVE) != 0;
+                // an LP's first pass (have_pred is cleared where a slot loads an LP and nowhere else) starts from x = z = 1: its
+                // M and A x are the handle's (GWave::gram_first); `first` is null under warm start
+                const bool from_image = FIRST_IMAGE && first != nullptr && !carried;
                 if (grp == g) {
 #pragma unroll
                     for (int q = 0; q < NCD; q++) {
                         const int p = G_::kpos(gl + MP * q);
-                        if (!carried) w.stage[p] = ok[q] ? x[q] : 0.0;
-                        w.stage[ND + p] = d[q];
+                        if (!carried && !from_image) w.stage[p] = ok[q] ? x[q] : 0.0;
+                        if (!from_image) w.stage[ND + p] = d[q];
                         w.stage[2 * ND + p] = d[q] * t[q];
                     }
                 }
                 wave_lds_sync();
                 double axg = 0.0, adg;
-                if (carried) w.template gram_one<false>(g, axg, adg); else w.template gram_one<true>(g, axg, adg);
+                if (carried) w.template gram_one<false>(g, axg, adg);
+                else if (from_image) w.gram_first(g, first, axg, adg);
+                else w.template gram_one<true>(g, axg, adg);
                 wave_lds_sync();
                 if (grp == g) { Ax_ = axg; Adt_ = adg; }
             }

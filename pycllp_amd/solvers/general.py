@@ -371,7 +371,8 @@ class HipSparseGeneralPrimalNormalSolver(HipGeneralPrimalNormalSolver):
     ``hsd='auto'`` the LPs that do not end optimal -- NUMERICAL included -- are solved again through the expansion where it
     fits the library (``pycllp_hip_dense_max_rows()`` / ``_max_cols()``); elsewhere the wave kernel's status stands."""
     name = 'hip_sparse_general_primal_normal'
-    _rejected = _REJECTED | _native.FLAG_BLOCK_KERNEL | _native.FLAG_FORCE_GUARD_PATH | _native.FLAG_EXACT_NORMS
+    _rejected = _REJECTED | _native.FLAG_BLOCK_KERNEL | _native.FLAG_FORCE_GUARD_PATH | _native.FLAG_EXACT_NORMS | \
+        _native.FLAG_PER_LP_FIRST_GRAM
     _rejected_names = "HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and FORCE_GUARD_PATH"
     _native_kernel = "bounded wave"
 
