@@ -253,9 +253,16 @@ int pycllp_hip_dense_solve_batch(pycllp_hip_dense *handle, long B, const double 
  *   u_dev [B,n], s_dev [B,n], dobj_dev [B] = b'y + u's and the objectives at the iteration limit: as
  *                         pycllp_hip_dense_solve_bounded; the other arguments as pycllp_hip_dense_solve
  * Options: PYCLLP_FLAG_AUTOSCALE (u scales with b) and PYCLLP_FLAG_FORCE_GUARD_PATH apply.
+ * Beyond the lane-group kernels (m > 32 or n > 128) a handle with m <= 128 and n <= 256 whose tail is the identity is served by
+ * the bounded wavefront-per-LP kernel with a dense image per wave (ipm_wreg_bddapa.hip: the image of the wave's LP, then its t
+ * and s, behind every wave area; fewer waves per workgroup the larger the image -- DESIGN.md section 25), on a plan built by
+ * the first call: same arguments; an LP whose factorisation the guard would have changed ends PYCLLP_STATUS_NUMERICAL, and
+ * PYCLLP_FLAG_FORCE_GUARD_PATH has no effect there.
  * Returns PYCLLP_E_BADARG for a NULL u_dev, any of the flags HSD, PREDCORR, WARM_START, WAVE_KERNEL, NO_SLACK_PATH or an a_cols
- * other than n - m, and PYCLLP_E_UNSUPPORTED when the handle has no slack-aware lane-group kernel; all before any HIP call.
- * Uses the handle's launch-queue ring; pycllp_hip_dense_launch_info / _variant_info report the launch (slack = 1).
+ * other than n - m, and PYCLLP_E_UNSUPPORTED when the handle has no slack-aware lane-group kernel (m <= 32 with 96 < n - m and
+ * n <= 128 included) or, beyond them, no shape or LDS plan of the wave kernel (m > 128, n > 256); all before any HIP call.
+ * Uses the handle's launch-queue ring; pycllp_hip_dense_launch_info / _variant_info report the launch (slack = 1; on the wave
+ * kernel: pycllp_hip_dense_kernel_kind 2, (MB, NQ), block = 64 x waves, the plan's LDS bytes).
  * Asynchronous on `stream`. */
 int pycllp_hip_dense_solve_batch_bounded(pycllp_hip_dense *handle, long B, const double *A_dev, long a_cols,
                                          const double *b_dev, const double *c_dev, const double *u_dev,

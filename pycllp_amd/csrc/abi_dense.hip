@@ -238,7 +238,10 @@ int pycllp_hip_dense_solve_batch_bounded(pycllp_hip_dense* h, long B, const doub
                                     "HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH are not available with upper bounds "
                                     "on per-problem matrices", A_dev && b_dev && c_dev && x_dev && status_dev);
     if (rc != 0) return rc;
-    if (h->sp || h->variant_sl < 0)
+    if (h->sp)      // beyond the lane-group kernels: the bounded wave kernel with an image per wave, where a variant and an LDS plan cover the LP
+        return dense_solve_batch_bounded_wave(h->sp, B, A_dev, a_cols, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev,
+                                              dobj_dev, status_dev, iters_dev, opts, stream);
+    if (h->variant_sl < 0)
         return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_batch_bounded: A is not [A_dense | I] with m <= 32 and at most "
                                              "96 dense columns (48 when m <= 16 on the 16-row kernels)");
     return dense_solve_batch_impl("pycllp_hip_dense_solve_batch_bounded", h, B, true, A_dev, a_cols, b_dev, c_dev, u_dev, x_dev,

@@ -203,6 +203,38 @@ int dense_solve_batch_wave(pycllp_hip_sparse* h, long B, const double* A_dev, lo
                                 [&](const int* worklist) { return block_launch_deferred_to_numerical(worklist, status_dev, st); });
 }
 
+// (host.h) The bounded wave kernel on per-problem dense matrices (ipm_wreg_bddapa.hip), on a plan of its own built on first use:
+// the image per wave with the identity tail implied, t and s behind it.  A handle of the large-LP kernel and an LP no variant or
+// LDS plan covers are declined.  An LP whose factorisation the guard would have changed ends PYCLLP_STATUS_NUMERICAL in the kernel.
+int dense_solve_batch_bounded_wave(pycllp_hip_sparse* h, long B, const double* A_dev, long a_cols, const double* b_dev,
+                                   const double* c_dev, const double* u_dev, double* x_dev, double* y_dev, double* z_dev,
+                                   double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
+                                   const pycllp_hip_opts* opts, void* stream) {
+    static const char* const kStops = "pycllp_hip_dense_solve_batch_bounded: upper bounds on per-problem dense matrices beyond the "
+                                      "lane-group kernels stop at m = 128, n = 256 with [A_dense | I]";
+    if (h->big) return set_err(PYCLLP_E_UNSUPPORTED, kStops);
+    hipStream_t st = (hipStream_t)stream;
+    LazyPlan* lp = &h->lazy[LAZY_BDDAPA];
+    const int rc = lazy_plan(h, lp, "wreg_plan_create_bounded_dense_pa", [&](WregPlan** wp) {
+        return wreg_plan_create_bounded_dense_pa(h->desc.m, h->desc.n, h->desc.nnz, h->host_val.data(), h->host_ptr.data(),
+                                                 h->host_col.data(), h->max_lds, st, wp);
+    });
+    if (rc != 0) return rc;
+    if (!lp->plan) return set_err(PYCLLP_E_UNSUPPORTED, kStops);
+    const int nd = wreg_image_cols(lp->plan);
+    if (a_cols != (long)nd) return pycllp_a_cols_error("pycllp_hip_dense_solve_batch_bounded", a_cols, nd, nd != h->desc.n);
+    if (B == 0) return 0;
+    DevOpts o = to_dev(opts);
+    int grid = 0;
+    const hipError_t e = h->ring.run(st, [&](int* qw) {
+        return wreg_launch_solve_bounded(lp->plan, B, A_dev, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
+                                         status_dev, iters_dev, qw, o, h->num_cu, st, &grid);
+    });
+    record_launch(h, lp->plan, grid);
+    if (e != hipSuccess) return set_err((int)e, "ipm_wreg_bounded_dapa_kernel launch");
+    return 0;
+}
+
 // which kernels of the sparse path implement the predictor-corrector step
 static bool sparse_predcorr_available(const pycllp_hip_sparse* h, bool per_problem_a, int flags) {
     if (h->big) return true;
@@ -519,11 +551,12 @@ int pycllp_hip_forward_backward_ldl(int n, long B, const double* L_dev, const do
 
 // Not part of the public ABI (absent from include/pycllp_hip.h): the plan a creator would build for the matrix given as HOST CSR
 // arrays, with no HIP call and nothing uploaded.  kind: 0 the block kernel's plan; 1 .. 6 the wave kernel's creators (wreg_plan_create,
-// the same with pa, _bounded, _bounded_pa, _dense_pa without and with keep_tail); 7 the large-LP kernel's.  Returns the creator's
+// the same with pa, _bounded, _bounded_pa, _dense_pa without and with keep_tail); 7 the large-LP kernel's; 8 the wave kernel's
+// _bounded_dense_pa (the later creator takes the next free number: 0 .. 7 keep their meaning).  Returns the creator's
 // code (the block plan: BLOCK_PLAN_*) and, where it is 0, scalars[PLAN_NSCALARS] and the digest as the plan's header documents them.
 extern "C" int pycllp_hip_debug_plan(int kind, int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
                                      long long* scalars, unsigned long long* digest) {
-    if (kind < 0 || kind > 7 || m < 0 || n < 0 || nnz < 0 || !ptr || !scalars || !digest || (nnz > 0 && (!val || !col))) return -1;
+    if (kind < 0 || kind > 8 || m < 0 || n < 0 || nnz < 0 || !ptr || !scalars || !digest || (nnz > 0 && (!val || !col))) return -1;
     memset(scalars, 0, sizeof(long long) * PLAN_NSCALARS);
     *digest = 0;
     int rc;
@@ -535,7 +568,8 @@ extern "C" int pycllp_hip_debug_plan(int kind, int m, int n, int nnz, const doub
         if ((rc = big_host_plan(m, n, nnz, val, ptr, col, max_lds, P)) == 0) *digest = big_plan_report(P, scalars);
     } else {
         WregHostPlan P;
-        if ((rc = wreg_plan_host((WregPlanKind)(kind - 1), m, n, nnz, val, ptr, col, max_lds, &P)) == 0) *digest = wreg_plan_report(P, scalars);
+        const WregPlanKind wk = kind == 8 ? WPLAN_BOUNDED_DENSE_PA : (WregPlanKind)(kind - 1);
+        if ((rc = wreg_plan_host(wk, m, n, nnz, val, ptr, col, max_lds, &P)) == 0) *digest = wreg_plan_report(P, scalars);
     }
     return rc;
 }

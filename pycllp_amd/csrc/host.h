@@ -129,8 +129,9 @@ struct pycllp_hip_dense {
 struct LazyPlan { WregPlan* plan = nullptr; bool tried = false; };
 // ... each by the first call of: _sparse_solve_batch (structure tables only), _sparse_solve_bounded (t and s behind every wave
 // area), _sparse_solve_batch_bounded (both), _dense_solve_batch beyond the lane-group kernels (per-problem DENSE matrices, an
-// image per wave: with the identity tail implied, and with every column in the image under PYCLLP_FLAG_NO_SLACK_PATH)
-enum { LAZY_PA, LAZY_BD, LAZY_BDPA, LAZY_DAPA, LAZY_DAPA_KEEP,
+// image per wave: with the identity tail implied, and with every column in the image under PYCLLP_FLAG_NO_SLACK_PATH),
+// _dense_solve_batch_bounded beyond the lane-group kernels (that image with t and s behind it)
+enum { LAZY_PA, LAZY_BD, LAZY_BDPA, LAZY_DAPA, LAZY_DAPA_KEEP, LAZY_BDDAPA,
        LAZY_N };
 
 // ---- sparse shared-A path (one LP per workgroup) ---------------------------------------------------------------
@@ -189,4 +190,9 @@ int sparse_init_host(int m, int n, int nnz, const std::vector<double>& val, cons
 int dense_solve_batch_wave(pycllp_hip_sparse* h, long B, const double* A_dev, long a_cols, const double* b_dev, const double* c_dev,
                            double* x_dev, double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev, int* status_dev,
                            int* iters_dev, const pycllp_hip_opts* opts, void* stream);
+// ... and of pycllp_hip_dense_solve_batch_bounded for such a handle.
+int dense_solve_batch_bounded_wave(pycllp_hip_sparse* h, long B, const double* A_dev, long a_cols, const double* b_dev,
+                                   const double* c_dev, const double* u_dev, double* x_dev, double* y_dev, double* z_dev,
+                                   double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
+                                   const pycllp_hip_opts* opts, void* stream);
 #endif

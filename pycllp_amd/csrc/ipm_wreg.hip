@@ -1,6 +1,6 @@
 // ipm_wreg.hip -- host side of the register-resident one-LP-per-wavefront kernels (wreg_wave.h): the plan of one constraint
 // matrix (term tables or dense image, LDS layout: built by wreg_plan.h, uploaded here), the choice of a launcher from the tables of the kernel units
-// (ipm_wreg_{tab,da,pa,dapa,pc,pcda,pcpa,bd,bdpa}.hip), grid sizing and the wreg_launch_* entry points of wreg.h.  The only kernels
+// (ipm_wreg_{tab,da,pa,dapa,pc,pcda,pcpa,bd,bdpa,bddapa}.hip), grid sizing and the wreg_launch_* entry points of wreg.h.  The only kernels
 // compiled here are the two that have no table: the stand-alone LDL' solve and the selftest of the cross-lane primitives.
 #include "wreg_wave.h"
 #include "wreg_plan.h"
@@ -94,7 +94,7 @@ struct WregPlan {
 // the launcher table of a plan's kind; pc: its predictor-corrector kernels (plans of the bounded kernel have none)
 static const WVariants& table_of(bool da, bool pa, bool bd, bool pc = false) {
     static const WVariants none = { nullptr, 0 };
-    if (da && pa) return (bd || pc) ? none : kWDAPA;      // per-problem dense matrices: the plain kernel only
+    if (da && pa) return pc ? none : (bd ? kWBDDAPA : kWDAPA);      // per-problem dense matrices: the plain and the bounded kernel
     if (bd) return pa ? kWBDPA : (da ? kWBDDA : kWBD);
     if (pc) return pa ? kWPCPA : (da ? kWPCDA : kWPC);
     return pa ? kWPA : (da ? kWDA : kWTab);
@@ -161,6 +161,11 @@ int wreg_plan_create_bounded_pa(int m, int n, int nnz, const double* val, const 
     return wreg_plan_upload(WPLAN_BOUNDED_PA, m, n, nnz, val, ptr, col, max_lds, st, out);
 }
 
+
+int wreg_plan_create_bounded_dense_pa(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
+                                      hipStream_t st, WregPlan** out) {
+    return wreg_plan_upload(WPLAN_BOUNDED_DENSE_PA, m, n, nnz, val, ptr, col, max_lds, st, out);
+}
 
 void wreg_plan_free(WregPlan* p) {
     if (!p) return;

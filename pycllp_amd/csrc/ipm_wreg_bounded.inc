@@ -19,8 +19,9 @@
 //   * a verdict reached inside an iteration (NUMERICAL, ITERATION_LIMIT) is stored at the top of the next pass, where the
 //     point's A'y is at hand for the duals of the fixed columns; the point itself is the one the verdict was reached on.
 // No warm start, no predictor-corrector, no HSD.
-// The text serves two units: ipm_wreg_bd.hip (ipm_wreg_bounded_kernel, a shared A) and ipm_wreg_bdpa.hip
-// (ipm_wreg_bounded_pa_kernel, per-problem values of A on structure tables; DESIGN.md section 18).
+// The text serves three units: ipm_wreg_bd.hip (ipm_wreg_bounded_kernel, a shared A), ipm_wreg_bdpa.hip
+// (ipm_wreg_bounded_pa_kernel, per-problem values of A on structure tables; DESIGN.md section 18) and ipm_wreg_bddapa.hip
+// (ipm_wreg_bounded_dapa_kernel, per-problem dense matrices, an image per wave; DESIGN.md section 25).
 
 namespace {
 
@@ -29,7 +30,26 @@ namespace {
 // CSR order.  The wave's copy of its LP's values sits where t and s sit otherwise (cvl_() = W0 + WAVE_D), so t and s go BEHIND
 // it, at the wave-uniform run-time offset WAVE_D + nnzp (nnzp is even: 16-byte alignment stays).  A preprocessor switch, not a
 // template argument: the kernel's signature differs, and the shared-A kernels stay instruction for instruction what they were.
-#ifdef PYCLLP_WREG_BOUNDED_PA
+// PYCLLP_WREG_BOUNDED_DAPA (defined by ipm_wreg_bddapa.hip): per-problem DENSE matrices, WReg<MB, NQ, true, true>; the kernel is
+// then ipm_wreg_bounded_dapa_kernel<MB, NQ> and takes ag [B, m, nd] row-major (nd = n - m: the bounded form ends in the
+// identity, which the image leaves out).  The wave's image starts where t and s sit otherwise (wimg_() = W0 + WAVE_D), so t
+// and s go BEHIND it, at the wave-uniform run-time offset WAVE_D + img_rows x AS (img_rows is a multiple of 8: the offset stays
+// even, 16-byte aligned).  A wave's area: [wave area | image img_rows x AS | t NP | s NP].  The image's pad rows and columns are
+// zeroed once per wave by wreg_setup; this text writes behind the wave area only at TS and above, never into the image.
+#if defined(PYCLLP_WREG_BOUNDED_DAPA)
+template <int MB, int NQ>
+__global__ void __launch_bounds__(256, 1)
+ipm_wreg_bounded_dapa_kernel(WregTab T, long B, const double* __restrict__ ag, const double* __restrict__ bg,
+                             const double* __restrict__ cg, const double* __restrict__ ug, double* __restrict__ xg,
+                             double* __restrict__ yg, double* __restrict__ zg, double* __restrict__ sg, double* __restrict__ pobj,
+                             double* __restrict__ dobj, int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue,
+                             DevOpts o) {
+    using G = WGeo<MB>;
+    constexpr int MR = G::MR, MP = G::MP, NP = 64 * NQ;
+    const int TS = G::WAVE_D(NQ) + T.img_rows * T.as;                         // t at W0[TS, TS + NP), s behind it
+    extern __shared__ __attribute__((aligned(16))) unsigned char lraw[];
+    WReg<MB, NQ, true, true> w;
+#elif defined(PYCLLP_WREG_BOUNDED_PA)
 template <int MB, int NQ>
 __global__ void __launch_bounds__(256, 1)
 ipm_wreg_bounded_pa_kernel(WregTab T, long B, const double* __restrict__ ag, const double* __restrict__ bg,
@@ -66,7 +86,7 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
     long lp = next_item(queue, lane);
     STAMP_DECL
     while (lp < B) {
-#ifdef PYCLLP_WREG_BOUNDED_PA
+#if defined(PYCLLP_WREG_BOUNDED_PA) || defined(PYCLLP_WREG_BOUNDED_DAPA)
         load_lp_values(w, ag, lp, T.nnz);      // before anything reads A
 #endif
         // padded positions read u = 0 (buffer offset past the row): they take no part, like a fixed column

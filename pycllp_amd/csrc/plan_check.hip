@@ -80,7 +80,7 @@ void every_kind(const Csr& A, const char* name) {
     const int max_lds = 160 * 1024;
     char what[128];
     long long s[PLAN_NSCALARS];
-    for (int kind = WPLAN_SHARED; kind <= WPLAN_DENSE_PA_KEEP; kind++) {
+    for (int kind = WPLAN_SHARED; kind <= WPLAN_BOUNDED_DENSE_PA; kind++) {
         WregHostPlan P;
         snprintf(what, sizeof(what), "%s wave kind %d", name, kind);
         if (wreg_host_plan((WregPlanKind)kind, wreg_listed_shapes, A.m, A.n, (int)A.val.size(), A.val.data(), A.ptr.data(), A.col.data(),

@@ -5,7 +5,7 @@
 #define PYCLLP_WREG_H
 #include "wave_common.h"
 
-// ---- shared between the host unit (ipm_wreg.hip) and the nine units the wave kernels are compiled in (ipm_wreg_*.hip) ----
+// ---- shared between the host unit (ipm_wreg.hip) and the ten units the wave kernels are compiled in (ipm_wreg_*.hip) ----
 constexpr int MAX_NQ = 8;
 constexpr int META_COFF = MAX_NQ, META_SEG = 2 * MAX_NQ, META_N = META_SEG + 16;
 
@@ -98,6 +98,8 @@ typedef hipError_t (*wbpsolve_fn)(const WregTab&, long, const double*, const dou
 // ... and the dense-image shapes of the kernel on per-problem dense matrices (kWDAPA): the list above without (8, 6), whose
 // instantiation does not stay free of scratch (28 bytes, like the shared-A kernel of that shape) -- DESIGN.md sections 10, 24
 #define WREG_DAPA_SHAPES(X) X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4)
+// ... and those of the bounded kernel on per-problem dense matrices (kWBDDAPA): a list of its own, under the same rule -- DESIGN.md section 25
+#define WREG_BDDAPA_SHAPES(X) X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4)
 
 // The launchers of one (MB, NQ) of one kernel kind; a launcher the kind does not have is null.
 struct WVariant { int mb, nq; wsolve_fn solve, solve_hsd; wnewton_fn newton; wbsolve_fn solve_bounded; wbpsolve_fn solve_bounded_pa; };
@@ -114,6 +116,7 @@ extern const WVariants kWPCPA;     // ipm_wreg_pcpa.hip: ... of kWPA's kind
 extern const WVariants kWBD;       // ipm_wreg_bd.hip:   upper bounds, term tables
 extern const WVariants kWBDDA;     // ipm_wreg_bd.hip:   upper bounds, dense image
 extern const WVariants kWBDPA;     // ipm_wreg_bdpa.hip: upper bounds, per-problem A on structure tables
+extern const WVariants kWBDDAPA;   // ipm_wreg_bddapa.hip: upper bounds, per-problem dense A, a dense image per wave
 
 struct WregPlan;   // host tables + device copies for one shared constraint matrix
 
@@ -140,6 +143,11 @@ int wreg_plan_create_bounded_pa(int m, int n, int nnz, const double* val, const 
 // (PYCLLP_FLAG_NO_SLACK_PATH).  Returns 1 when no variant covers (m, n) or not even one wave fits.
 int wreg_plan_create_dense_pa(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
                               int keep_tail, hipStream_t st, WregPlan** out);
+// The plan of the bounded kernel on per-problem DENSE matrices (kWBDDAPA): wreg_plan_create_dense_pa's without keep_tail (the
+// bounded form always ends in the identity) and with 2 NP more doubles per wave, t and s, BEHIND the wave's image.  Returns 1
+// when no variant covers (m, n) or not even one wave fits.
+int wreg_plan_create_bounded_dense_pa(int m, int n, int nnz, const double* val, const int* ptr, const int* col, int max_lds,
+                                      hipStream_t st, WregPlan** out);
 void wreg_plan_free(WregPlan* p);
 
 // Solve B LPs (same argument meaning as pycllp_hip_sparse_solve).  LPs whose factorisation would have needed the
@@ -153,7 +161,8 @@ hipError_t wreg_launch_solve(WregPlan* p, long B, const double* a_batch, const d
 
 // Solve B LPs with upper bounds on a plan of wreg_plan_create_bounded (argument meaning of pycllp_hip_sparse_solve_bounded).
 // An LP whose factorisation would have needed the Nocedal-Wright guard ends PYCLLP_STATUS_NUMERICAL.
-// a_batch: [B, nnz] values of every LP in the plan's CSR order, on a plan of wreg_plan_create_bounded_pa only (else null).
+// a_batch: [B, nnz] values of every LP in the plan's CSR order, on a plan of wreg_plan_create_bounded_pa; the dense matrices
+// [B, m, nd], row-major, on a plan of wreg_plan_create_bounded_dense_pa; else null.
 hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* a_batch, const double* b, const double* c, const double* u, double* x, double* y,
                                      double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead,
                                      DevOpts o, int num_cu, hipStream_t st, int* grid_out);

@@ -12,9 +12,12 @@ struct WShape { int mb, nq; };
 static const std::vector<WShape> kWTabShapes = { WREG_TAB_SHAPES(WSHAPE_ENTRY) };
 static const std::vector<WShape> kWDaShapes = { WREG_DA_SHAPES(WSHAPE_ENTRY) };
 static const std::vector<WShape> kWDapaShapes = { WREG_DAPA_SHAPES(WSHAPE_ENTRY) };
+static const std::vector<WShape> kWBddapaShapes = { WREG_BDDAPA_SHAPES(WSHAPE_ENTRY) };
 #undef WSHAPE_ENTRY
 // the shape list of a plan's kind as wreg.h has it (the library asks its launcher tables instead: ipm_wreg.hip)
-inline const std::vector<WShape>& wreg_listed_shapes(bool da, bool pa, bool) { return da ? (pa ? kWDapaShapes : kWDaShapes) : kWTabShapes; }
+inline const std::vector<WShape>& wreg_listed_shapes(bool da, bool pa, bool bd) {
+    return da ? (pa ? (bd ? kWBddapaShapes : kWDapaShapes) : kWDaShapes) : kWTabShapes;
+}
 
 // the first shape of a list (ordered by cost) that covers (m, n), or null
 inline const WShape* first_covering(const std::vector<WShape>& s, int m, int n) {
@@ -35,7 +38,8 @@ struct WregHostPlan {
 };
 
 // the kinds of plan: one per creator of wreg.h
-enum WregPlanKind { WPLAN_SHARED, WPLAN_PA, WPLAN_BOUNDED, WPLAN_BOUNDED_PA, WPLAN_DENSE_PA, WPLAN_DENSE_PA_KEEP };
+enum WregPlanKind { WPLAN_SHARED, WPLAN_PA, WPLAN_BOUNDED, WPLAN_BOUNDED_PA, WPLAN_DENSE_PA, WPLAN_DENSE_PA_KEEP,
+                    WPLAN_BOUNDED_DENSE_PA };
 
 namespace wreg_plan_detail {
 
@@ -88,19 +92,20 @@ inline int wreg_image_plan(const std::vector<WShape>& shapes, int m, int n, int 
 }
 
 // The plan of the kernel on per-problem dense matrices: the geometry of the image plan, an image behind every wave area and
-// nothing in front of the waves, no table.  keep_tail: an identity tail stays in the image.
+// nothing in front of the waves, no table.  keep_tail: an identity tail stays in the image.  bd: the plan of the bounded kernel
+// (t and s behind every wave's image: [wave area | image | t NP | s NP]).
 inline int wreg_image_pa_plan(const std::vector<WShape>& shapes, int m, int n, int nnz, const double* val, const int* ptr,
-                              const int* col, int max_lds, bool keep_tail, WregHostPlan& P) {
+                              const int* col, int max_lds, bool keep_tail, WregHostPlan& P, bool bd = false) {
     using namespace wreg_plan_detail;
     if (!image_geometry(shapes, m, n, nnz, val, ptr, col, keep_tail, P)) return 1;
     WregTab& T = P.tab;
     T.pa = 1;
-    T.wave_doubles = wave_doubles(P.mb, P.nq) + T.img_rows * T.as;
+    T.wave_doubles = wave_doubles(P.mb, P.nq) + T.img_rows * T.as + (bd ? 2 * 64 * P.nq : 0);
     T.wpb = most_waves(0, T.wave_doubles, max_lds);
     if (!T.wpb) return 1;
     T.o_img = 0; T.o_wave = 0;
     T.lds_bytes = (int)(sizeof(double) * (size_t)T.wpb * T.wave_doubles);
-    P.pa = true;
+    P.pa = true; P.bd = bd;
     return 0;
 }
 
@@ -276,6 +281,8 @@ inline int wreg_host_plan(WregPlanKind kind, ShapesOf&& shapes_of, int m, int n,
     const bool bd = kind == WPLAN_BOUNDED || kind == WPLAN_BOUNDED_PA;
     if (kind == WPLAN_DENSE_PA || kind == WPLAN_DENSE_PA_KEEP)
         return wreg_image_pa_plan(shapes_of(true, true, false), m, n, nnz, val, ptr, col, max_lds, kind == WPLAN_DENSE_PA_KEEP, P);
+    if (kind == WPLAN_BOUNDED_DENSE_PA)
+        return wreg_image_pa_plan(shapes_of(true, true, true), m, n, nnz, val, ptr, col, max_lds, false, P, true);
     const bool pa = kind == WPLAN_PA || kind == WPLAN_BOUNDED_PA;
     const int rc = wreg_tables_plan(shapes_of(false, pa, bd), m, n, nnz, val, ptr, col, max_lds, pa, bd, P);
     if (rc != 1 || pa) return rc;

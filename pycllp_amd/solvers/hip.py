@@ -284,8 +284,17 @@ class Handle(object):
 
     def solve_batch_bounded(self, stream, A, b, c, u, out, o):
         """B LPs with their own dense matrices A [B, m, n - m] (dense family, a handle whose tail is the identity) and the upper
-        bounds u [B, n] into ``out`` (x, y, z, s, pobj, dobj, status, iters)."""
+        bounds u [B, n] into ``out`` (x, y, z, s, pobj, dobj, status, iters): on the lane-group kernel, or beyond it (m <= 128,
+        n <= 256) on the bounded wave kernel with an image per wave."""
         self._solve_batch("solve_batch_bounded", stream, A, (b, c, u), [out[k] for k in BOUNDED_RESULTS], o)
+
+    def plan_batch_bounded(self, stream, a_cols):
+        """An empty batch (B = 0) through ``solve_batch_bounded``'s entry with matrices of ``a_cols`` columns: nothing is
+        launched, but a handle beyond the lane-group kernels builds the bounded wave kernel's plan now, and
+        ``NotImplementedError`` says at once that no shape or LDS plan of it covers the LP."""
+        t = torch.zeros(1, dtype=torch.float64, device=self.device)      # (the entry wants u non-NULL whatever B is; nothing is read)
+        o = _native.default_opts()
+        self._call("solve_batch_bounded", self, 0, t, ctypes.c_long(int(a_cols)), *([t] * 11), ctypes.byref(o), self._stream(stream))
 
     def newton(self, stream, x, z, y, b, c, mu, dy, nrefine, o):
         self._call("newton", self, int(x.shape[0]), x, z, y, b, c, float(mu), dy, nrefine, ctypes.byref(o), self._stream(stream))
