@@ -215,6 +215,27 @@ int pycllp_hip_dense_solve_bounded(pycllp_hip_dense *handle, long B, const doubl
                                    double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
                                    const pycllp_hip_opts *opts, void *stream);
 
+/* The same LPs -- maximise c'x s.t. A x = b, 0 <= x <= u on a handle whose A is [A_dense | I_m] -- on the HOMOGENEOUS SELF-DUAL
+ * EMBEDDING with bounds (csrc/ipm_group_bdhsd.inc): an infeasible or unbounded LP ends with a certificate
+ * instead of the 10x-growth heuristic of pycllp_hip_dense_solve_bounded.  Arguments as pycllp_hip_dense_solve_bounded; outputs:
+ *   status 0 (and 5)  x, y, z, s, pobj, dobj are divided by the final tau: the solution of the LP (at the iteration limit the
+ *                     objectives are those of the point returned, as for every bounded entry)
+ *   status 2          the certificate as it stands: y, z, s with -b'y - u's > 0 and |A'y - z + s| <= 1e-8 (-b'y - u's)
+ *   status 4          the certificate as it stands: a ray x with c'x > 0 and max(|A x|, |x_j| over finite u_j) <= 1e-8 c'x
+ *                     (eps = 1e-10: the rule is 100 eps; under autoscale both hold for the LP as the kernel scaled it, b, u / max|b|
+ *                     and c / max|c|: in the caller's units the first ratio is divided by max|b|, the second by max|c|)
+ *   a fixed column (u = 0) ends at x = 0 with z = max(-r, 0), s = max(r, 0), r = c tau - A'y, on the same scaling
+ * Options: PYCLLP_FLAG_HSD is accepted and implied; PYCLLP_FLAG_AUTOSCALE and _AUTOSCALE_PER_LP apply exactly as for
+ * pycllp_hip_dense_solve_bounded (b, u, c are divided on load, the results scaled back); PYCLLP_FLAG_FORCE_GUARD_PATH applies;
+ * max_refine = PYCLLP_MAX_REFINE_AUTO resolves to 20.
+ * Returns PYCLLP_E_BADARG for a NULL handle or u_dev, both autoscale flags together, or any of the flags PREDCORR, WARM_START,
+ * WAVE_KERNEL, NO_SLACK_PATH -- before the handle is read --, and PYCLLP_E_UNSUPPORTED when the handle has no slack-aware
+ * lane-group shape or that shape's kernel was not compiled.  Asynchronous on `stream`. */
+int pycllp_hip_dense_solve_bounded_hsd(pycllp_hip_dense *handle, long B, const double *b_dev, const double *c_dev,
+                                       const double *u_dev, double *x_dev, double *y_dev, double *z_dev, double *s_dev,
+                                       double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
+                                       const pycllp_hip_opts *opts, void *stream);
+
 /* Solve B LPs that each have their OWN dense matrix, on the lane-group kernel for per-problem A (every lane group keeps the
  * image of its LP's matrix in LDS and refills it from A_dev when it takes its next LP).  The handle comes from
  * pycllp_hip_dense_init with any one matrix of the batch: that matrix fixes m, n and whether the last m columns are the

@@ -47,6 +47,7 @@ SIGNATURES = (
     ("pycllp_hip_dense_init", [_i, _i, _p, _p, _pp], _i),
     ("pycllp_hip_dense_solve", _solve(9), _i),                  # b, c, x, y, z, pobj, dobj, status, iters
     ("pycllp_hip_dense_solve_bounded", _solve(11), _i),         # b, c, u, x, y, z, s, pobj, dobj, status, iters
+    ("pycllp_hip_dense_solve_bounded_hsd", _solve(11), _i),     # as solve_bounded, on the self-dual embedding
     ("pycllp_hip_dense_solve_batch", [_p, _l, _p, _l] + [_p] * 9 + [_O, _p], _i),    # A [B, m, a_cols], a_cols, then as solve
     ("pycllp_hip_dense_solve_batch_bounded", [_p, _l, _p, _l] + [_p] * 11 + [_O, _p], _i),    # ... then as solve_bounded
     ("pycllp_hip_dense_newton", [_p, _l, _p, _p, _p, _p, _p, _d, _p, _p, _O, _p], _i),

@@ -215,6 +215,32 @@ int pycllp_hip_dense_solve_bounded(pycllp_hip_dense* h, long B, const double* b_
     return 0;
 }
 
+int pycllp_hip_dense_solve_bounded_hsd(pycllp_hip_dense* h, long B, const double* b_dev, const double* c_dev, const double* u_dev,
+                                       double* x_dev, double* y_dev, double* z_dev, double* s_dev, double* pobj_dev,
+                                       double* dobj_dev, int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
+    const int rc = check_restricted("pycllp_hip_dense_solve_bounded_hsd", h, B, u_dev, opts, kBoundedRejected & ~PYCLLP_FLAG_HSD,
+                                    "PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH are not available with upper bounds on "
+                                    "the self-dual embedding", b_dev && c_dev && x_dev && status_dev);
+    if (rc != 0) return rc;
+    if (h->sp || h->variant_sl < 0)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_bounded_hsd: A is not [A_dense | I] with m <= 32 and at most "
+                                             "96 dense columns (48 when m <= 16 on the 16-row kernels)");
+    const DenseKernel& k = kSlackVariants[h->variant_sl].solve_bounded_hsd;
+    if (!k.launch)
+        return set_err(PYCLLP_E_UNSUPPORTED, "pycllp_hip_dense_solve_bounded_hsd: no kernel of this shape was compiled");
+    if (B == 0) return 0;
+    pycllp_hip_opts ho;     // PYCLLP_FLAG_HSD is implied: max_refine AUTO resolves to the embedding's 20 passes
+    pycllp_hip_default_opts(&ho);
+    if (opts) ho = *opts;
+    ho.flags |= PYCLLP_FLAG_HSD;
+    DevOpts o = to_dev(&ho);
+    const GroupPaArgs a = {h->m, h->n, B, h->a_rm, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
+                           status_dev, iters_dev, nullptr};
+    hipError_t e = run_group(h, k, a, o, (hipStream_t)stream);
+    if (e != hipSuccess) return set_err((int)e, "bounded self-dual solve kernel launch");
+    return 0;
+}
+
 int pycllp_hip_dense_solve_batch(pycllp_hip_dense* h, long B, const double* A_dev, long a_cols, const double* b_dev,
                                  const double* c_dev, double* x_dev, double* y_dev, double* z_dev, double* pobj_dev, double* dobj_dev,
                                  int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {

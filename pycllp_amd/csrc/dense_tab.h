@@ -35,12 +35,37 @@ struct Variant {
 // slack-aware group kernels: (MP, NP) with NP - MP padded dense columns + the m identity columns
 // full_group: the full-shape instantiation of solve_group, launched on its plan, for a matrix with m == mp and n == np
 // exactly; null where none was compiled (ipm_dense.hip full_group_kernel)
+// solve_bounded_hsd: the bounded kernel on the homogeneous self-dual embedding (ipm_group_bdhsd.hip); its launcher is null for a
+// shape that was left out of BDHSD_SHAPES
 struct SlackVariant {
     int mp, np;
     DenseKernel solve_group, solve_hsd, solve_pc, solve_bounded;
     dense_launch_fn full_group;
     FirstGram first;          // (the full-shape instantiation reads it too: its Gram bits are the generic ones)
+    DenseKernel solve_bounded_hsd;
 };
+
+// The shapes ipm_bounded_hsd_kernel ships in: those of GROUP_SHAPES whose instantiation has no scratch (tools/kernel_resources.py;
+// DESIGN.md section 26).  ipm_group_bdhsd.hip instantiates the launcher for these; ipm_dense.hip puts it into the table.
+#if defined(PYCLLP_DEV_ONLY_3296)
+#define BDHSD_SHAPES(X) X(32, 96)
+#elif defined(PYCLLP_DEV_ONLY_1648)
+#define BDHSD_SHAPES(X) X(16, 48)
+#else
+#define BDHSD_SHAPES(X) X(16, 32) X(16, 48) X(16, 64) X(32, 64) X(32, 96) X(32, 128)
+#endif
+template <int MP, int NP>
+hipError_t launch_solve_bounded_hsd(const GroupPaArgs&, const LaunchPlan&, DevOpts, hipStream_t);
+constexpr bool bdhsd_ships(int mp, int np) {
+#define BDHSD_IS(MP, NP) if (mp == MP && np == NP) return true;
+    BDHSD_SHAPES(BDHSD_IS)
+#undef BDHSD_IS
+    return false;
+}
+template <int MP, int NP>
+constexpr dense_launch_fn bounded_hsd_launcher() {
+    if constexpr (bdhsd_ships(MP, NP)) return launch_solve_bounded_hsd<MP, NP>; else return nullptr;
+}
 
 // one row per lane-group shape of GROUP_SHAPES (group_pa.h), in its order: the first that covers (m, n) is used, in both tables
 extern const Variant kVariants[];

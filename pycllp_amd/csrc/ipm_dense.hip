@@ -572,7 +572,8 @@ static hipError_t launch_newton(const NewtonArgs& a, const LaunchPlan& p, DevOpt
 #define SLACK_VARIANT(MP, NP) \
     { MP, NP, GROUP_KERNEL(MP, NP, true, false, false), GROUP_KERNEL(MP, NP, true, true, false), \
       GROUP_KERNEL(MP, NP, true, false, true), { plan_group<MP, NP, true, PYCLLP_WPB_BOUNDED>, launch_solve_bounded<MP, NP> }, \
-      full_group_kernel<MP, NP>(), FIRST_GRAM(MP, NP, true) },
+      full_group_kernel<MP, NP>(), FIRST_GRAM(MP, NP, true), \
+      { plan_group<MP, NP, true, PYCLLP_WPB_BOUNDED>, bounded_hsd_launcher<MP, NP>() } },
 #define PA_PLAN(MP, NP) { MP, NP, 0, plan_group_pa<MP, NP, false> }, { MP, NP, 1, plan_group_pa<MP, NP, true> },
 // ... with upper bounds: the same rule, at most PYCLLP_WPB_BOUNDED waves per workgroup
 #define PABD_PLAN(MP, NP) { MP, NP, 1, plan_group_pa<MP, NP, true, GeoPA<GeoG<MP, NP, true>>::wpb_capped(PYCLLP_WPB_BOUNDED)> },

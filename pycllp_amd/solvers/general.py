@@ -149,15 +149,27 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
     _rejected = _REJECTED
     _rejected_names = "HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH"
     _native_kernel = "bounded group"
+    _hsd_entry = True         # the handle has ``solve_bounded_hsd``: hsd='native' is available
 
     def __init__(self, device=None, stream=None, autoscale="auto", hsd="auto", predcorr=False, warm_start=False, **options):
         """``hsd='auto'`` (default): the LPs that do not end optimal on the bounded kernel are solved again through the
         expansion on ``HipDensePrimalNormalSolver`` (whose own ``hsd='auto'`` gives infeasible / unbounded LPs the certified
-        statuses 2 / 4); ``hsd=False``: the bounded kernel's verdict stands.  ``hsd=True``, ``predcorr=True`` and
+        statuses 2 / 4); ``hsd=False``: the bounded kernel's verdict stands.  ``hsd='native'``
+        (``hip_general_primal_normal`` alone): as 'auto', but the LPs that do not end optimal on the bounded kernel are solved
+        again ON THE DEVICE, on the bounded kernel's self-dual embedding (``pycllp_hip_dense_solve_bounded_hsd``) with the same
+        handle -- no expansion, no second solver, no host conversion; an LP outside the native range (``kernel == 'expanded'``)
+        behaves as under 'auto'.  A status-2 LP then carries its certificate in ``y, z, s``, a status-4 LP has ``x = l +`` the
+        ray (as ``solve_expanded`` returns it).  ``hsd=True``, ``predcorr=True`` and
         ``warm_start=True`` are not available with bounds.  ``autoscale``: as ``HipDensePrimalNormalSolver`` (the 'auto' band
         rule also looks at the finite upper bounds).  Other keyword arguments are fields of ``pycllp_hip_opts``."""
         if not isinstance(hsd, str) and hsd:
-            raise ValueError("hsd must be 'auto' or False for %s (the bounded kernel has no embedding)" % self.name)
+            raise ValueError("hsd must be 'auto', False or (hip_general_primal_normal) 'native' for %s: the embedding with bounds "
+                             "serves the LPs that do not end optimal, or solve_device(..., hsd=True)" % self.name)
+        self.hsd_native = isinstance(hsd, str) and hsd == "native"
+        if self.hsd_native:
+            if not self._hsd_entry:
+                raise ValueError("hsd='native' is not available for %s (its kernel has no self-dual embedding)" % self.name)
+            hsd = "auto"          # (what the expansion and every other path see)
         if predcorr:
             raise ValueError("predcorr is not available with upper bounds")
         if warm_start:
@@ -213,19 +225,23 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
             self._handle = self._key = self._conv = None
         self.m, self.n = glp.nrows, glp.ncols
 
-    def solve_device(self, a, b, c, l, u, f=None, **options):
+    def solve_device(self, a, b, c, l, u, f=None, hsd=False, **options):
         """Device-resident entry, in the ORIGINAL variables: a, b [B, m], c, l, u [B, n], f [B] (torch CUDA tensors, or numpy
         arrays, which are uploaded; ``l`` and ``f`` may be None = 0) -> dict of CUDA tensors: ``RESULTS`` and ``invalid`` (i32
         [B]: 0, or the check of ``pycllp_hip_general_to_bounded`` the LP failed; such an LP has status 3 and NaN results).
         Conversion, bounded solve and back-conversion are queued on the solver's stream and nothing waits for them; the kernel's
-        verdict stands (no look at the data: ``autoscale='auto'`` and ``hsd='auto'`` count as off).  ``options``: fields of
-        ``pycllp_hip_opts`` for this call."""
+        verdict stands (no look at the data: ``autoscale='auto'``, ``hsd='auto'`` and ``hsd='native'`` count as off).
+        ``hsd=True`` (``hip_general_primal_normal`` alone): the whole batch runs on the bounded kernel's self-dual embedding
+        (``pycllp_hip_dense_solve_bounded_hsd``) in one launch, still without a sync: statuses 2 / 4 are certified and come
+        with their certificate (``y, z, s`` / ``x = l +`` the ray).  ``options``: fields of ``pycllp_hip_opts`` for this call."""
         if self._handle is None or self._conv is None:
             raise RuntimeError("solve_device() needs init() on an LP the %s kernel serves (after init() the LP takes the "
                                "expansion)" % self._native_kernel)
-        return self._solve_on_device(None, a, b, c, l, u, f, options)
+        if hsd and not self._hsd_entry:
+            raise ValueError("hsd=True is not available for %s (its kernel has no self-dual embedding)" % self.name)
+        return self._solve_on_device(None, a, b, c, l, u, f, options, hsd=bool(hsd))
 
-    def _solve_on_device(self, Adata, a, b, c, l, u, f, options):
+    def _solve_on_device(self, Adata, a, b, c, l, u, f, options, hsd=False):
         """The device-resident chain of ``solve_device`` (``Adata`` None) and ``solve_device_general``: upload what is numpy,
         check the shapes against the conversion's plan, convert, launch (``_launch_converted``), convert back; the inputs and
         everything between stay alive until the next call."""
@@ -241,21 +257,36 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
                 raise ValueError(("Adata must be [B,%d], a and b " % cv.nnz if mat else "a and b must be ")
                                  + "[B,%d], c, l and u [B,%d] and f [B] with equal B" % (cv.m, cv.n))
             bl = cv.to_bounded(self.stream, *mat, a, b, c, l, u, f)
-            out = self._launch_converted(bl, B, 0, options)
+            out = self._launch_converted(bl, B, 0, options, **(dict(hsd=True) if hsd else {}))
             res = cv.from_bounded(self.stream, l, bl["f"], bl["invalid"], out)
         self._keepalive = mat + (a, b, c, l, u, f, bl, out)
         self.kernel = self._native_kernel
         return res
 
-    def _launch_converted(self, bl, B, extra_flags, overrides):
+    def _launch_converted(self, bl, B, extra_flags, overrides, hsd=False):
         """The bounded solve of the B LPs that ``to_bounded`` left in ``bl``, queued on the solver's stream -> its outputs
-        (``bounded_outputs``).  ``NotImplementedError`` where the library declines."""
+        (``bounded_outputs``); ``hsd``: on the self-dual embedding.  ``NotImplementedError`` where the library declines."""
         cv = self._conv
         o = solve_opts(self.options, extra_flags, **overrides)
         out = bounded_outputs(B, cv.mk, cv.n + cv.mk, self.device)
         if B:
-            self._handle.solve_bounded(self.stream, bl["b"], bl["c"], bl["u"], out, o)
+            (self._handle.solve_bounded_hsd if hsd else self._handle.solve_bounded)(self.stream, bl["b"], bl["c"], bl["u"], out, o)
         return out
+
+    def _resolve_native(self, bl, out, extra_flags):
+        """hsd='native': the LPs of ``out`` that did not end optimal, solved again on the embedding with the same handle --
+        their b^, c^, u^ gathered on the device, the results scattered into ``out``.  (The one look at the statuses waits for
+        the first launch.)"""
+        idx = torch.nonzero(out["status"] != 0).reshape(-1)
+        if idx.numel() == 0:
+            return
+        sub = {k: bl[k].index_select(0, idx).contiguous() for k in ("b", "c", "u")}
+        try:
+            again = self._launch_converted(sub, int(idx.numel()), extra_flags, {}, hsd=True)
+        except NotImplementedError:
+            return                                  # (no kernel of this shape: the bounded kernel's verdict stands)
+        for k, v in again.items():
+            out[k].index_copy_(0, idx, v)
 
     def solve(self, lp, verbose=0):
         glp = as_general(lp)
@@ -275,7 +306,7 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
     def _finish(self, glp, res, redo=True):
         """The tail of ``solve``: with ``hsd='auto'`` the LPs of a native solve that did not end optimal are solved again
         (``_redo`` picks them, ``_solve_again`` solves them), then ``res`` becomes the result attributes."""
-        if redo and self.hsd == "auto":
+        if redo and self.hsd == "auto" and not self.hsd_native:      # (hsd='native': done on the device, in _solve_native)
             idx = self._redo(glp, np.flatnonzero(res["status"] != 0))
             r2 = self._solve_again(subset(glp, idx)) if idx.size else None
             if r2 is not None:
@@ -314,6 +345,8 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
                 out = self._launch_converted(bl, B, _native.FLAG_AUTOSCALE if wanted else 0, {})
             except NotImplementedError:
                 return None
+            if self.hsd_native:
+                self._resolve_native(bl, out, _native.FLAG_AUTOSCALE if wanted else 0)
             res = cv.from_bounded(self.stream, args[-2], fh, bl["invalid"], out)      # (args[-2]: l)
             torch.cuda.synchronize(self.device)
             return {k: res[k].cpu().numpy() for k in RESULTS}
@@ -375,6 +408,7 @@ class HipSparseGeneralPrimalNormalSolver(HipGeneralPrimalNormalSolver):
         _native.FLAG_PER_LP_FIRST_GRAM
     _rejected_names = "HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and FORCE_GUARD_PATH"
     _native_kernel = "bounded wave"
+    _hsd_entry = False
 
     @staticmethod
     def native_fits(glp, blp):
@@ -410,6 +444,7 @@ class PerProblemBounded(object):
     ``solve_device_general`` is the same chain on tensors.  ``conversion`` says which conversion serves ``solve``: ``'device'``,
     or ``'host'`` (``GeneralLP.to_bounded_equality_form`` and ``_values``) for a structure without a plan; None with a delegate."""
     _changed_what = "%d kept rows (%d at init), %d matrices"
+    _hsd_entry = False
 
     def __init__(self, *args, **kwargs):
         super(PerProblemBounded, self).__init__(*args, **kwargs)

@@ -270,6 +270,12 @@ class Handle(object):
         self._call(entry, self, int(b.shape[0]), *lead, b, c, u, *(out[k] for k in BOUNDED_RESULTS), ctypes.byref(o),
                    self._stream(stream))
 
+    def solve_bounded_hsd(self, stream, b, c, u, out, o):
+        """``solve_bounded`` on the homogeneous self-dual embedding with bounds (dense family, ``pycllp_hip_dense_solve_bounded_hsd``):
+        statuses 2 and 4 come with their certificate in ``out`` (y, z, s / x), 0 and 5 with the solution."""
+        self._call("solve_bounded_hsd", self, int(b.shape[0]), b, c, u, *(out[k] for k in BOUNDED_RESULTS), ctypes.byref(o),
+                   self._stream(stream))
+
     def _solve_batch(self, entry, stream, A, vectors, outputs, o):
         """``entry`` of the dense family on per-problem matrices: A must be a contiguous [B, m, a_cols] with the B of b."""
         B = int(vectors[0].shape[0])
