@@ -385,6 +385,31 @@ int pycllp_hip_sparse_solve_bounded(pycllp_hip_sparse *handle, long B, const dou
                                     const double *u_dev, double *x_dev, double *y_dev, double *z_dev, double *s_dev,
                                     double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
                                     const pycllp_hip_opts *opts, void *stream);
+/* The same LPs on the HOMOGENEOUS SELF-DUAL EMBEDDING with bounds, on the wavefront-per-LP kernel
+ * (csrc/ipm_wreg_bdhsd.inc; the system of section 26): an infeasible or unbounded LP ends with a certificate
+ * instead of the 10x-growth heuristic of pycllp_hip_sparse_solve_bounded.  Arguments as pycllp_hip_sparse_solve_bounded, on the
+ * same handle and the same plan (built by whichever of the two entries runs first); the outputs mean what they mean for
+ * pycllp_hip_dense_solve_bounded_hsd:
+ *   status 0 (and 5)  x, y, z, s, pobj, dobj are divided by the final tau (at the iteration limit the objectives are those of
+ *                     the point returned)
+ *   status 2          the certificate as it stands: y, z, s with -b'y - u's > 0 and |A'y - z + s| <= 1e-8 (-b'y - u's)
+ *   status 4          the certificate as it stands: a ray x with c'x > 0 and max(|A x|, |x_j| over finite u_j) <= 1e-8 c'x
+ *                     (under autoscale both hold for the LP as the kernel scaled it)
+ *   a fixed column (u = 0) ends at x = 0 with z = max(-r, 0), s = max(r, 0), r = c tau - A'y, on the same scaling
+ * y_dev, z_dev, s_dev, pobj_dev, dobj_dev, iters_dev may be NULL.  Options: PYCLLP_FLAG_HSD is accepted and implied;
+ * PYCLLP_FLAG_AUTOSCALE and _AUTOSCALE_PER_LP apply exactly as for pycllp_hip_sparse_solve_bounded; max_refine =
+ * PYCLLP_MAX_REFINE_AUTO resolves to 20.  An LP whose LDL' would need the Nocedal-Wright guard, or whose norms, tau, kappa or
+ * step turn non-finite, ends PYCLLP_STATUS_NUMERICAL.
+ * Returns PYCLLP_E_BADARG for a NULL handle or u_dev, B < 0, both autoscale flags together, or any of the flags PREDCORR,
+ * WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH, FORCE_GUARD_PATH -- before the handle is read and before any HIP call --,
+ * and PYCLLP_E_UNSUPPORTED for a handle on the large-LP kernel (m > 128 or n > 512), when no variant of the bounded kernel or
+ * LDS plan covers A, or when the kernel of the plan's shape was not compiled (an instantiation with scratch is not shipped).
+ * pycllp_hip_sparse_launch_info / _variant_info report the launch as they do for pycllp_hip_sparse_solve_bounded.
+ * Asynchronous on `stream`. */
+int pycllp_hip_sparse_solve_bounded_hsd(pycllp_hip_sparse *handle, long B, const double *b_dev, const double *c_dev,
+                                        const double *u_dev, double *x_dev, double *y_dev, double *z_dev, double *s_dev,
+                                        double *pobj_dev, double *dobj_dev, int *status_dev, int *iters_dev,
+                                        const pycllp_hip_opts *opts, void *stream);
 /* The bounded solve with PER-PROBLEM VALUES of A on the shared structure: the union of pycllp_hip_sparse_solve_batch and
  * pycllp_hip_sparse_solve_bounded, on the same kernel text compiled for per-problem values (csrc/ipm_wreg_bdpa.hip).
  *   Adata_dev [B, nnz]   the values of LP k in the CSR order of the arrays given to pycllp_hip_sparse_init (whose values only

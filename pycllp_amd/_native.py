@@ -63,6 +63,7 @@ SIGNATURES = (
     ("pycllp_hip_sparse_solve", _solve(9), _i),
     ("pycllp_hip_sparse_solve_batch", _solve(10), _i),          # A's values first
     ("pycllp_hip_sparse_solve_bounded", _solve(11), _i),
+    ("pycllp_hip_sparse_solve_bounded_hsd", _solve(11), _i),    # as solve_bounded, on the self-dual embedding
     ("pycllp_hip_sparse_solve_batch_bounded", _solve(12), _i),  # A's values first, then as solve_bounded
     ("pycllp_hip_sparse_newton", [_p, _l, _p, _p, _p, _p, _p, _d, _p, _p, _O, _p], _i),
     ("pycllp_hip_sparse_launch_info", [_p] + [_ip] * 4, _i), ("pycllp_hip_sparse_variant_info", [_p] + [_ip] * 2, _i),
@@ -80,7 +81,7 @@ EXPORTS = tuple(name for name, _, _ in SIGNATURES)
 # Entries that a library built from an earlier commit does not have.  Only a library named by PYCLLP_HIP_LIB (a diagnostic or
 # an earlier build, for A/B runs of two builds under one Python tree) may lack them: it loads without them, `has_entry` says so,
 # and what they report is then left out, never made up.  The product's own library must have every entry (AttributeError).
-LATER_ENTRIES = ("pycllp_hip_dense_full_shape",)
+LATER_ENTRIES = ("pycllp_hip_dense_full_shape", "pycllp_hip_sparse_solve_bounded_hsd")
 _absent = set()
 
 

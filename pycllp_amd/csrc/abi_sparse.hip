@@ -318,13 +318,14 @@ static int sparse_solve_impl(pycllp_hip_sparse* h, long B, const double* a_batch
 
 // The body of pycllp_hip_sparse_solve_bounded and, with a_batch, of pycllp_hip_sparse_solve_batch_bounded, behind their
 // argument checks (as sparse_solve_impl is of the entries without bounds).  lp: the entry's plan slot of the handle;
-// create: its constructor, named create_what in a HIP error of the build.
+// create: its constructor, named create_what in a HIP error of the build.  hsd: the batch runs on the homogeneous self-dual
+// embedding (ipm_wreg_bounded_hsd_kernel, on the same plan; shared A only) and `opts` carries PYCLLP_FLAG_HSD.
 typedef int (*bounded_plan_fn)(int, int, int, const double*, const int*, const int*, int, hipStream_t, WregPlan**);
 static int sparse_solve_bounded_impl(const char* entry, pycllp_hip_sparse* h, long B, const double* a_batch, LazyPlan* lp,
                                      bounded_plan_fn create, const char* create_what, const double* b_dev,
                                      const double* c_dev, const double* u_dev, double* x_dev, double* y_dev, double* z_dev,
                                      double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
-                                     const pycllp_hip_opts* opts, void* stream) {
+                                     const pycllp_hip_opts* opts, void* stream, bool hsd = false) {
     if (h->big) return entry_err(PYCLLP_E_UNSUPPORTED, entry, "the bounded wave kernel stops at m = 128, n = 512");
     hipStream_t st = (hipStream_t)stream;
     const int rc = lazy_plan(h, lp, create_what, [&](WregPlan** wp) {
@@ -336,15 +337,22 @@ static int sparse_solve_bounded_impl(const char* entry, pycllp_hip_sparse* h, lo
                          a_batch ? "no variant of the bounded wave kernel covers this structure on per-problem values (rows, "
                                    "columns, or its tables in LDS)"
                                  : "no variant of the bounded wave kernel covers this A (rows, columns, or its tables in LDS)");
+    if (hsd && !wreg_has_bounded_hsd(lp->plan))
+        return entry_err(PYCLLP_E_UNSUPPORTED, entry, "no kernel of this shape was compiled (the instantiation does not stay free of scratch)");
     if (B == 0) return 0;
     DevOpts o = to_dev(opts);
     int grid = 0;
     const hipError_t e = h->ring.run(st, [&](int* qw) {
+        if (hsd)
+            return wreg_launch_solve_bounded_hsd(lp->plan, B, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
+                                                 status_dev, iters_dev, qw, o, h->num_cu, st, &grid);
         return wreg_launch_solve_bounded(lp->plan, B, a_batch, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev, dobj_dev,
                                          status_dev, iters_dev, qw, o, h->num_cu, st, &grid);
     });
     record_launch(h, lp->plan, grid);
-    if (e != hipSuccess) return set_err((int)e, a_batch ? "ipm_wreg_bounded_pa_kernel launch" : "ipm_wreg_bounded_kernel launch");
+    if (e != hipSuccess)
+        return set_err((int)e, hsd ? "ipm_wreg_bounded_hsd_kernel launch"
+                                   : (a_batch ? "ipm_wreg_bounded_pa_kernel launch" : "ipm_wreg_bounded_kernel launch"));
     return 0;
 }
 
@@ -408,6 +416,22 @@ int pycllp_hip_sparse_solve_bounded(pycllp_hip_sparse* h, long B, const double* 
     return sparse_solve_bounded_impl("pycllp_hip_sparse_solve_bounded", h, B, nullptr, &h->lazy[LAZY_BD],
                                      wreg_plan_create_bounded, "wreg_plan_create_bounded", b_dev, c_dev, u_dev, x_dev, y_dev, z_dev,
                                      s_dev, pobj_dev, dobj_dev, status_dev, iters_dev, opts, stream);
+}
+
+int pycllp_hip_sparse_solve_bounded_hsd(pycllp_hip_sparse* h, long B, const double* b_dev, const double* c_dev, const double* u_dev,
+                                        double* x_dev, double* y_dev, double* z_dev, double* s_dev, double* pobj_dev,
+                                        double* dobj_dev, int* status_dev, int* iters_dev, const pycllp_hip_opts* opts, void* stream) {
+    const int rc = check_restricted("pycllp_hip_sparse_solve_bounded_hsd", h, B, u_dev, opts, kWaveBoundedRejected & ~PYCLLP_FLAG_HSD,
+                                    "PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and FORCE_GUARD_PATH are not "
+                                    "available with upper bounds on the self-dual embedding", b_dev && c_dev && x_dev && status_dev);
+    if (rc != 0) return rc;
+    pycllp_hip_opts ho;     // PYCLLP_FLAG_HSD is implied: max_refine AUTO resolves to the embedding's 20 passes
+    pycllp_hip_default_opts(&ho);
+    if (opts) ho = *opts;
+    ho.flags |= PYCLLP_FLAG_HSD;
+    return sparse_solve_bounded_impl("pycllp_hip_sparse_solve_bounded_hsd", h, B, nullptr, &h->lazy[LAZY_BD],
+                                     wreg_plan_create_bounded, "wreg_plan_create_bounded", b_dev, c_dev, u_dev, x_dev, y_dev, z_dev,
+                                     s_dev, pobj_dev, dobj_dev, status_dev, iters_dev, &ho, stream, true);
 }
 
 int pycllp_hip_sparse_solve_batch_bounded(pycllp_hip_sparse* h, long B, const double* Adata_dev, const double* b_dev,

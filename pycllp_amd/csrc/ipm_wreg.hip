@@ -231,6 +231,27 @@ hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* a_batch,
     return v->solve_bounded(p->tab, B, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o, grid, st);
 }
 
+// the launcher of the bounded kernel on the self-dual embedding for a shared-A bounded plan's (MB, NQ), or null
+static wbsolve_fn bounded_hsd_launcher(const WregPlan* p) {
+    if (!p || !p->bd || p->pa) return nullptr;
+    const WVariants& t = p->da ? kWBDHDA : kWBDH;
+    for (int i = 0; i < t.n; i++)
+        if (t.v[i].mb == p->mb && t.v[i].nq == p->nq) return t.v[i].solve_bounded;
+    return nullptr;
+}
+int wreg_has_bounded_hsd(const WregPlan* p) { return bounded_hsd_launcher(p) ? 1 : 0; }
+
+hipError_t wreg_launch_solve_bounded_hsd(WregPlan* p, long B, const double* b, const double* c, const double* u, double* x, double* y,
+                                         double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead,
+                                         DevOpts o, int num_cu, hipStream_t st, int* grid_out) {
+    if (!p || !p->bd || p->pa) return hipErrorInvalidValue;
+    const wbsolve_fn fn = bounded_hsd_launcher(p);
+    if (!fn) return hipErrorNotSupported;
+    const int grid = solve_grid(p, B, o, num_cu);
+    if (grid_out) *grid_out = grid;
+    return fn(p->tab, B, b, c, u, x, y, z, s, pobj, dobj, status, iters, qhead, o, grid, st);
+}
+
 hipError_t wreg_launch_newton(WregPlan* p, long B, const double* x, const double* z, const double* y, const double* b,
                               const double* c, double mu, double* dy, int* nref, DevOpts o, int num_cu, hipStream_t st,
                               int* grid_out) {

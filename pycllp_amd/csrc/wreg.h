@@ -5,7 +5,7 @@
 #define PYCLLP_WREG_H
 #include "wave_common.h"
 
-// ---- shared between the host unit (ipm_wreg.hip) and the ten units the wave kernels are compiled in (ipm_wreg_*.hip) ----
+// ---- shared between the host unit (ipm_wreg.hip) and the eleven units the wave kernels are compiled in (ipm_wreg_*.hip) ----
 constexpr int MAX_NQ = 8;
 constexpr int META_COFF = MAX_NQ, META_SEG = 2 * MAX_NQ, META_N = META_SEG + 16;
 
@@ -100,6 +100,11 @@ typedef hipError_t (*wbpsolve_fn)(const WregTab&, long, const double*, const dou
 #define WREG_DAPA_SHAPES(X) X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4)
 // ... and those of the bounded kernel on per-problem dense matrices (kWBDDAPA): a list of its own, under the same rule -- DESIGN.md section 25
 #define WREG_BDDAPA_SHAPES(X) X(1, 4) X(2, 4) X(3, 4) X(4, 2) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4)
+// The bounded kernel on the homogeneous self-dual embedding (kWBDH, kWBDHDA; ipm_wreg_bdh.hip) runs on the plans of the bounded
+// kernel, so its tables list the shapes of WREG_TAB_SHAPES / WREG_DA_SHAPES; a shape whose instantiation does not stay free of
+// scratch (tools/kernel_resources.py, profiles/bounded_wave_hsd/kernel_resources.txt) keeps its row with a null launcher --
+// the five shapes with MB = 8 (m' > 112) spill 10 to 82 VGPRs past the 512 registers of a lane
+__host__ __device__ constexpr bool wreg_bdhsd_ships(int MB, int NQ, bool DA) { return MB < 8; }
 
 // The launchers of one (MB, NQ) of one kernel kind; a launcher the kind does not have is null.
 struct WVariant { int mb, nq; wsolve_fn solve, solve_hsd; wnewton_fn newton; wbsolve_fn solve_bounded; wbpsolve_fn solve_bounded_pa; };
@@ -117,6 +122,8 @@ extern const WVariants kWBD;       // ipm_wreg_bd.hip:   upper bounds, term tabl
 extern const WVariants kWBDDA;     // ipm_wreg_bd.hip:   upper bounds, dense image
 extern const WVariants kWBDPA;     // ipm_wreg_bdpa.hip: upper bounds, per-problem A on structure tables
 extern const WVariants kWBDDAPA;   // ipm_wreg_bddapa.hip: upper bounds, per-problem dense A, a dense image per wave
+extern const WVariants kWBDH;      // ipm_wreg_bdh.hip:  upper bounds on the self-dual embedding, term tables (solve_bounded; null: not shipped)
+extern const WVariants kWBDHDA;    // ipm_wreg_bdh.hip:  upper bounds on the self-dual embedding, dense image
 
 struct WregPlan;   // host tables + device copies for one shared constraint matrix
 
@@ -166,6 +173,14 @@ hipError_t wreg_launch_solve(WregPlan* p, long B, const double* a_batch, const d
 hipError_t wreg_launch_solve_bounded(WregPlan* p, long B, const double* a_batch, const double* b, const double* c, const double* u, double* x, double* y,
                                      double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead,
                                      DevOpts o, int num_cu, hipStream_t st, int* grid_out);
+// The same batch on the homogeneous self-dual embedding (ipm_wreg_bounded_hsd_kernel; argument meaning of
+// pycllp_hip_sparse_solve_bounded_hsd), on a plan of wreg_plan_create_bounded: the kernel keeps nothing more behind the wave area.
+// hipErrorInvalidValue on any other plan (a per-problem plan has no such kernel), hipErrorNotSupported where the plan's shape is
+// not shipped (wreg_has_bounded_hsd says so beforehand).
+hipError_t wreg_launch_solve_bounded_hsd(WregPlan* p, long B, const double* b, const double* c, const double* u, double* x, double* y,
+                                         double* z, double* s, double* pobj, double* dobj, int* status, int* iters, int* qhead,
+                                         DevOpts o, int num_cu, hipStream_t st, int* grid_out);
+int wreg_has_bounded_hsd(const WregPlan* p);   // 1 when p is a shared-A bounded plan whose shape ipm_wreg_bounded_hsd_kernel ships in
 
 // One Newton step for B states (semantics of pycllp_hip_dense_newton).  guard_hit[0] is set to 1 if any state would
 // have needed the guard (the stand-alone step then simply ran without it).  *grid_out (optional): the workgroups launched.

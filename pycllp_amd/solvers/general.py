@@ -149,7 +149,8 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
     _rejected = _REJECTED
     _rejected_names = "HSD, PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH"
     _native_kernel = "bounded group"
-    _hsd_entry = True         # the handle has ``solve_bounded_hsd``: hsd='native' is available
+    _hsd_entry = True         # the handle has ``solve_bounded_hsd``: solve_device(..., hsd=True) is available
+    _hsd_spellings = ("native", "device")      # the values of ``hsd`` that ask for the embedding on this plugin's own kernel
 
     def __init__(self, device=None, stream=None, autoscale="auto", hsd="auto", predcorr=False, warm_start=False, **options):
         """``hsd='auto'`` (default): the LPs that do not end optimal on the bounded kernel are solved again through the
@@ -159,16 +160,21 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
         again ON THE DEVICE, on the bounded kernel's self-dual embedding (``pycllp_hip_dense_solve_bounded_hsd``) with the same
         handle -- no expansion, no second solver, no host conversion; an LP outside the native range (``kernel == 'expanded'``)
         behaves as under 'auto'.  A status-2 LP then carries its certificate in ``y, z, s``, a status-4 LP has ``x = l +`` the
-        ray (as ``solve_expanded`` returns it).  ``hsd=True``, ``predcorr=True`` and
+        ray (as ``solve_expanded`` returns it).  ``hsd='device'`` (both shared-A plugins): the same re-solve on the device, on
+        the embedding of whichever bounded kernel the plugin runs -- on ``hip_general_primal_normal`` a synonym of 'native', on
+        ``hip_sparse_general_primal_normal`` the wave kernel's (``pycllp_hip_sparse_solve_bounded_hsd``), where what the
+        embedding returns stands: no expansion at any size.  ``hsd=True``, ``predcorr=True`` and
         ``warm_start=True`` are not available with bounds.  ``autoscale``: as ``HipDensePrimalNormalSolver`` (the 'auto' band
         rule also looks at the finite upper bounds).  Other keyword arguments are fields of ``pycllp_hip_opts``."""
         if not isinstance(hsd, str) and hsd:
-            raise ValueError("hsd must be 'auto', False or (hip_general_primal_normal) 'native' for %s: the embedding with bounds "
-                             "serves the LPs that do not end optimal, or solve_device(..., hsd=True)" % self.name)
-        self.hsd_native = isinstance(hsd, str) and hsd == "native"
+            raise ValueError("hsd must be 'auto', False, (the shared-A plugins) 'device' or (hip_general_primal_normal) 'native' "
+                             "for %s: the embedding with bounds serves the LPs that do not end optimal, or "
+                             "solve_device(..., hsd=True)" % self.name)
+        self.hsd_native = isinstance(hsd, str) and hsd in ("native", "device")
         if self.hsd_native:
-            if not self._hsd_entry:
-                raise ValueError("hsd='native' is not available for %s (its kernel has no self-dual embedding)" % self.name)
+            if hsd not in self._hsd_spellings:      # (a check of its own: 'native' stays the lane-group plugin's spelling)
+                raise ValueError("hsd=%r is not available for %s%s" % (hsd, self.name, " (its kernel has no self-dual embedding)"
+                                 if not self._hsd_spellings else ": its spelling there is hsd='device'"))
             hsd = "auto"          # (what the expansion and every other path see)
         if predcorr:
             raise ValueError("predcorr is not available with upper bounds")
@@ -230,9 +236,10 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
         arrays, which are uploaded; ``l`` and ``f`` may be None = 0) -> dict of CUDA tensors: ``RESULTS`` and ``invalid`` (i32
         [B]: 0, or the check of ``pycllp_hip_general_to_bounded`` the LP failed; such an LP has status 3 and NaN results).
         Conversion, bounded solve and back-conversion are queued on the solver's stream and nothing waits for them; the kernel's
-        verdict stands (no look at the data: ``autoscale='auto'``, ``hsd='auto'`` and ``hsd='native'`` count as off).
-        ``hsd=True`` (``hip_general_primal_normal`` alone): the whole batch runs on the bounded kernel's self-dual embedding
-        (``pycllp_hip_dense_solve_bounded_hsd``) in one launch, still without a sync: statuses 2 / 4 are certified and come
+        verdict stands (no look at the data: ``autoscale='auto'``, ``hsd='auto'``, ``hsd='native'`` and ``hsd='device'`` count as
+        off).  ``hsd=True`` (the two shared-A plugins): the whole batch runs on the bounded kernel's self-dual embedding
+        (``pycllp_hip_dense_solve_bounded_hsd`` / ``pycllp_hip_sparse_solve_bounded_hsd``) in one launch, still without a sync:
+        statuses 2 / 4 are certified and come
         with their certificate (``y, z, s`` / ``x = l +`` the ray).  ``options``: fields of ``pycllp_hip_opts`` for this call."""
         if self._handle is None or self._conv is None:
             raise RuntimeError("solve_device() needs init() on an LP the %s kernel serves (after init() the LP takes the "
@@ -274,7 +281,7 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
         return out
 
     def _resolve_native(self, bl, out, extra_flags):
-        """hsd='native': the LPs of ``out`` that did not end optimal, solved again on the embedding with the same handle --
+        """hsd='native' / 'device': the LPs of ``out`` that did not end optimal, solved again on the embedding with the same handle --
         their b^, c^, u^ gathered on the device, the results scattered into ``out``.  (The one look at the statuses waits for
         the first launch.)"""
         idx = torch.nonzero(out["status"] != 0).reshape(-1)
@@ -306,7 +313,7 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
     def _finish(self, glp, res, redo=True):
         """The tail of ``solve``: with ``hsd='auto'`` the LPs of a native solve that did not end optimal are solved again
         (``_redo`` picks them, ``_solve_again`` solves them), then ``res`` becomes the result attributes."""
-        if redo and self.hsd == "auto" and not self.hsd_native:      # (hsd='native': done on the device, in _solve_native)
+        if redo and self.hsd == "auto" and not self.hsd_native:      # (hsd='native' / 'device': done on the device, in _solve_native)
             idx = self._redo(glp, np.flatnonzero(res["status"] != 0))
             r2 = self._solve_again(subset(glp, idx)) if idx.size else None
             if r2 is not None:
@@ -402,13 +409,17 @@ class HipSparseGeneralPrimalNormalSolver(HipGeneralPrimalNormalSolver):
     contract, options and results, for bounded forms of up to 128 kept rows and 512 columns, sparse or dense.  ``kernel`` is
     ``'bounded wave'`` or ``'expanded'`` (per-problem values of A, a bounded form no variant of the kernel covers).  With
     ``hsd='auto'`` the LPs that do not end optimal -- NUMERICAL included -- are solved again through the expansion where it
-    fits the library (``pycllp_hip_dense_max_rows()`` / ``_max_cols()``); elsewhere the wave kernel's status stands."""
+    fits the library (``pycllp_hip_dense_max_rows()`` / ``_max_cols()``); elsewhere the wave kernel's status stands.  With
+    ``hsd='device'`` they are solved again on the wave kernel's own self-dual embedding (``pycllp_hip_sparse_solve_bounded_hsd``,
+    DESIGN.md section 27) with the same handle, at every size the kernel serves, and what the embedding returns stands;
+    ``solve_device(..., hsd=True)`` runs the whole batch there.  ``hsd='native'`` stays the lane-group plugin's spelling."""
     name = 'hip_sparse_general_primal_normal'
     _rejected = _REJECTED | _native.FLAG_BLOCK_KERNEL | _native.FLAG_FORCE_GUARD_PATH | _native.FLAG_EXACT_NORMS | \
         _native.FLAG_PER_LP_FIRST_GRAM
     _rejected_names = "HSD, PREDCORR, WARM_START, WAVE_KERNEL, BLOCK_KERNEL, NO_SLACK_PATH and FORCE_GUARD_PATH"
     _native_kernel = "bounded wave"
-    _hsd_entry = False
+    _hsd_entry = True
+    _hsd_spellings = ("device",)
 
     @staticmethod
     def native_fits(glp, blp):
@@ -445,6 +456,7 @@ class PerProblemBounded(object):
     or ``'host'`` (``GeneralLP.to_bounded_equality_form`` and ``_values``) for a structure without a plan; None with a delegate."""
     _changed_what = "%d kept rows (%d at init), %d matrices"
     _hsd_entry = False
+    _hsd_spellings = ()
 
     def __init__(self, *args, **kwargs):
         super(PerProblemBounded, self).__init__(*args, **kwargs)

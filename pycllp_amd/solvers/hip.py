@@ -271,7 +271,8 @@ class Handle(object):
                    self._stream(stream))
 
     def solve_bounded_hsd(self, stream, b, c, u, out, o):
-        """``solve_bounded`` on the homogeneous self-dual embedding with bounds (dense family, ``pycllp_hip_dense_solve_bounded_hsd``):
+        """``solve_bounded`` on the homogeneous self-dual embedding with bounds (``pycllp_hip_dense_solve_bounded_hsd`` on the
+        lane-group kernel, ``pycllp_hip_sparse_solve_bounded_hsd`` on the wave kernel: the handle's family names the entry):
         statuses 2 and 4 come with their certificate in ``out`` (y, z, s / x), 0 and 5 with the solution."""
         self._call("solve_bounded_hsd", self, int(b.shape[0]), b, c, u, *(out[k] for k in BOUNDED_RESULTS), ctypes.byref(o),
                    self._stream(stream))
