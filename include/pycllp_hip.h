@@ -291,6 +291,26 @@ int pycllp_hip_dense_solve_batch_bounded(pycllp_hip_dense *handle, long B, const
                                          double *dobj_dev, int *status_dev, int *iters_dev,
                                          const pycllp_hip_opts *opts, void *stream);
 
+/* The same LPs -- upper bounds, every LP its OWN dense matrix [A_k | I] -- on the HOMOGENEOUS SELF-DUAL EMBEDDING with bounds
+ * (csrc/ipm_group_pabdhsd.inc, DESIGN.md section 28: the system of pycllp_hip_dense_solve_bounded_hsd on the per-slot matrix
+ * images of pycllp_hip_dense_solve_batch_bounded): an infeasible or unbounded LP ends with a certificate instead of the
+ * 10x-growth heuristic.  Arguments as pycllp_hip_dense_solve_batch_bounded (A_dev [B, m, a_cols], a_cols = n - m); outputs,
+ * statuses and certificates as pycllp_hip_dense_solve_bounded_hsd: statuses 0 and 5 divided by the final tau, statuses 2 and 4
+ * the certificate as it stands (with A_k in place of A), a fixed column at x = 0.
+ * Options: PYCLLP_FLAG_HSD is accepted and implied; PYCLLP_FLAG_AUTOSCALE and _AUTOSCALE_PER_LP apply as for
+ * pycllp_hip_dense_solve_bounded_hsd; PYCLLP_FLAG_FORCE_GUARD_PATH applies; max_refine = PYCLLP_MAX_REFINE_AUTO resolves to 20.
+ * Returns PYCLLP_E_BADARG for a NULL handle or u_dev, B < 0, both autoscale flags together, or any of the flags PREDCORR,
+ * WARM_START, WAVE_KERNEL, NO_SLACK_PATH -- before the handle is read --, and for an a_cols other than n - m;
+ * PYCLLP_E_UNSUPPORTED for a handle beyond the lane-group kernels (m > 32 or n > 128: the wave kernel with an image per wave
+ * has no embedding), for one without a slack-aware lane-group shape, and for a shape whose kernel was not compiled; all before
+ * any HIP call, with nothing touched.  Uses the handle's launch-queue ring; pycllp_hip_dense_launch_info / _variant_info report
+ * the launch (slack = 1).  Asynchronous on `stream`. */
+int pycllp_hip_dense_solve_batch_bounded_hsd(pycllp_hip_dense *handle, long B, const double *A_dev, long a_cols,
+                                             const double *b_dev, const double *c_dev, const double *u_dev,
+                                             double *x_dev, double *y_dev, double *z_dev, double *s_dev, double *pobj_dev,
+                                             double *dobj_dev, int *status_dev, int *iters_dev,
+                                             const pycllp_hip_opts *opts, void *stream);
+
 /* One Newton step of the primal normal equations for B independent states:
  *   dy <- solve( A diag(x/z) A' , -(b - A x - A diag(x/z) (c - A'y + mu/x)) )
  * x,z,c [B,n]; y,b,dy [B,m].  nrefine_dev [B] (optional) receives the refinement passes used. */

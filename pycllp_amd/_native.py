@@ -50,6 +50,7 @@ SIGNATURES = (
     ("pycllp_hip_dense_solve_bounded_hsd", _solve(11), _i),     # as solve_bounded, on the self-dual embedding
     ("pycllp_hip_dense_solve_batch", [_p, _l, _p, _l] + [_p] * 9 + [_O, _p], _i),    # A [B, m, a_cols], a_cols, then as solve
     ("pycllp_hip_dense_solve_batch_bounded", [_p, _l, _p, _l] + [_p] * 11 + [_O, _p], _i),    # ... then as solve_bounded
+    ("pycllp_hip_dense_solve_batch_bounded_hsd", [_p, _l, _p, _l] + [_p] * 11 + [_O, _p], _i),    # ... on the self-dual embedding
     ("pycllp_hip_dense_newton", [_p, _l, _p, _p, _p, _p, _p, _d, _p, _p, _O, _p], _i),
     ("pycllp_hip_dense_launch_info", [_p] + [_ip] * 5, _i), ("pycllp_hip_dense_kernel_kind", [_p], _i),
     ("pycllp_hip_dense_variant_info", [_p] + [_ip] * 3, _i), ("pycllp_hip_dense_plan_info", [_p] + [_ip] * 4, _i),
@@ -81,7 +82,7 @@ EXPORTS = tuple(name for name, _, _ in SIGNATURES)
 # Entries that a library built from an earlier commit does not have.  Only a library named by PYCLLP_HIP_LIB (a diagnostic or
 # an earlier build, for A/B runs of two builds under one Python tree) may lack them: it loads without them, `has_entry` says so,
 # and what they report is then left out, never made up.  The product's own library must have every entry (AttributeError).
-LATER_ENTRIES = ("pycllp_hip_dense_full_shape", "pycllp_hip_sparse_solve_bounded_hsd")
+LATER_ENTRIES = ("pycllp_hip_dense_full_shape", "pycllp_hip_sparse_solve_bounded_hsd", "pycllp_hip_dense_solve_batch_bounded_hsd")
 _absent = set()
 
 

@@ -1,5 +1,5 @@
 // abi_dense.hip -- the C ABI of the dense handle (include/pycllp_hip.h: pycllp_hip_dense_*).  Host code only: the lane-group
-// kernels are reached through the tables of dense_tab.h (ipm_dense.hip) and group_pa.h (ipm_group_pa.hip, ipm_group_pabd.hip);
+// kernels are reached through the tables of dense_tab.h (ipm_dense.hip) and group_pa.h (ipm_group_pa.hip, ipm_group_pabd.hip, ipm_group_pabdh.hip);
 // a matrix beyond them (m > 32 or n > 128) gets a sparse handle, whose entries and bodies are abi_sparse.hip's (host.h).
 #include "dense_tab.h"
 
@@ -29,19 +29,20 @@ static auto find_pa(const Table& t, int mp, int np, bool sl) -> decltype(t.v) {
     return nullptr;
 }
 
-// The body of pycllp_hip_dense_solve_batch and, with u_dev, of pycllp_hip_dense_solve_batch_bounded, behind their argument
+// The body of pycllp_hip_dense_solve_batch and, with u_dev, of pycllp_hip_dense_solve_batch_bounded and (hsd: on the
+// self-dual embedding, kGroupPABDH on the plans of kPaBdPlans) of pycllp_hip_dense_solve_batch_bounded_hsd, behind their argument
 // checks and their look at the handle.  sl: the matrices come without the identity tail (the slack-aware kernels).
 static int dense_solve_batch_impl(const char* entry, pycllp_hip_dense* h, long B, bool sl, const double* A_dev, long a_cols,
                                   const double* b_dev, const double* c_dev, const double* u_dev, double* x_dev, double* y_dev,
                                   double* z_dev, double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
-                                  const pycllp_hip_opts* opts, void* stream) {
+                                  const pycllp_hip_opts* opts, void* stream, bool hsd = false) {
     const bool bd = u_dev != nullptr;
     if (a_cols != (long)(sl ? h->n - h->m : h->n)) return pycllp_a_cols_error(entry, a_cols, sl ? h->n - h->m : h->n, sl);
     const int mp = sl ? kSlackVariants[h->variant_sl].mp : kVariants[h->variant].mp;
     const int np = sl ? kSlackVariants[h->variant_sl].np : kVariants[h->variant].np;
     const PaPlan* pp = find_pa(bd ? kPaBdPlans : kPaPlans, mp, np, sl);
-    const GroupPaVariant* pv = find_pa(bd ? kGroupPABD : kGroupPA, mp, np, sl);
-    if (!pp || !pv) return entry_err(PYCLLP_E_UNSUPPORTED, entry, "no kernel of this shape was compiled");
+    const GroupPaVariant* pv = find_pa(hsd ? kGroupPABDH : (bd ? kGroupPABD : kGroupPA), mp, np, sl);
+    if (!pp || !pv || !pv->launch) return entry_err(PYCLLP_E_UNSUPPORTED, entry, "no kernel of this shape was compiled");
     if (B == 0) return 0;
     DevOpts o = to_dev(opts);
     hipStream_t st = (hipStream_t)stream;
@@ -53,7 +54,9 @@ static int dense_solve_batch_impl(const char* entry, pycllp_hip_dense* h, long B
         publish(h, p);
         return el;
     });
-    if (e != hipSuccess) return set_err((int)e, bd ? "bounded per-problem solve kernel launch" : "per-problem solve kernel launch");
+    if (e != hipSuccess)
+        return set_err((int)e, hsd ? "bounded per-problem self-dual solve kernel launch"
+                                   : (bd ? "bounded per-problem solve kernel launch" : "per-problem solve kernel launch"));
     return 0;
 }
 
@@ -272,6 +275,30 @@ int pycllp_hip_dense_solve_batch_bounded(pycllp_hip_dense* h, long B, const doub
                                              "96 dense columns (48 when m <= 16 on the 16-row kernels)");
     return dense_solve_batch_impl("pycllp_hip_dense_solve_batch_bounded", h, B, true, A_dev, a_cols, b_dev, c_dev, u_dev, x_dev,
                                   y_dev, z_dev, s_dev, pobj_dev, dobj_dev, status_dev, iters_dev, opts, stream);
+}
+
+int pycllp_hip_dense_solve_batch_bounded_hsd(pycllp_hip_dense* h, long B, const double* A_dev, long a_cols, const double* b_dev,
+                                             const double* c_dev, const double* u_dev, double* x_dev, double* y_dev, double* z_dev,
+                                             double* s_dev, double* pobj_dev, double* dobj_dev, int* status_dev, int* iters_dev,
+                                             const pycllp_hip_opts* opts, void* stream) {
+    static const char* const entry = "pycllp_hip_dense_solve_batch_bounded_hsd";
+    const int rc = check_restricted(entry, h, B, u_dev, opts, kBoundedRejected & ~PYCLLP_FLAG_HSD,
+                                    "PREDCORR, WARM_START, WAVE_KERNEL and NO_SLACK_PATH are not available with upper bounds on "
+                                    "per-problem matrices on the self-dual embedding",
+                                    A_dev && b_dev && c_dev && x_dev && status_dev);
+    if (rc != 0) return rc;
+    if (h->sp)      // beyond the lane-group kernels: the wave kernel with an image per wave has no embedding
+        return entry_err(PYCLLP_E_UNSUPPORTED, entry, "the self-dual embedding on per-problem matrices exists on the lane-group "
+                                                      "kernels only (m <= 32, n <= 128)");
+    if (h->variant_sl < 0)
+        return entry_err(PYCLLP_E_UNSUPPORTED, entry, "A is not [A_dense | I] with m <= 32 and at most 96 dense columns (48 when "
+                                                      "m <= 16 on the 16-row kernels)");
+    pycllp_hip_opts ho;     // PYCLLP_FLAG_HSD is implied: max_refine AUTO resolves to the embedding's 20 passes
+    pycllp_hip_default_opts(&ho);
+    if (opts) ho = *opts;
+    ho.flags |= PYCLLP_FLAG_HSD;
+    return dense_solve_batch_impl(entry, h, B, true, A_dev, a_cols, b_dev, c_dev, u_dev, x_dev, y_dev, z_dev, s_dev, pobj_dev,
+                                  dobj_dev, status_dev, iters_dev, &ho, stream, true);
 }
 
 int pycllp_hip_dense_newton(pycllp_hip_dense* h, long B, const double* x_dev, const double* z_dev,

@@ -67,6 +67,23 @@ constexpr dense_launch_fn bounded_hsd_launcher() {
     if constexpr (bdhsd_ships(MP, NP)) return launch_solve_bounded_hsd<MP, NP>; else return nullptr;
 }
 
+// The shapes ipm_bounded_pa_hsd_kernel (ipm_group_pabdhsd.inc: the same embedding on per-problem matrices) ships in, by the same
+// rule.  ipm_group_pabdh.hip instantiates the launchers for these and puts them into kGroupPABDH
+// (group_pa.h); a shape left out has a null launcher there.
+#if defined(PYCLLP_DEV_ONLY_3296)
+#define PABDHSD_SHAPES(X) X(32, 96)
+#elif defined(PYCLLP_DEV_ONLY_1648)
+#define PABDHSD_SHAPES(X) X(16, 48)
+#else
+#define PABDHSD_SHAPES(X) X(16, 32) X(16, 48) X(16, 64) X(32, 64) X(32, 96) X(32, 128)
+#endif
+constexpr bool pabdhsd_ships(int mp, int np) {
+#define PABDHSD_IS(MP, NP) if (mp == MP && np == NP) return true;
+    PABDHSD_SHAPES(PABDHSD_IS)
+#undef PABDHSD_IS
+    return false;
+}
+
 // one row per lane-group shape of GROUP_SHAPES (group_pa.h), in its order: the first that covers (m, n) is used, in both tables
 extern const Variant kVariants[];
 extern const int kNumVariants;

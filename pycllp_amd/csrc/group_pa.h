@@ -1,6 +1,7 @@
-// group_pa.h -- internal interface between abi_dense.hip (C ABI, handles; the launch plans are dense_tab.h's) and ipm_group_pa.hip / ipm_group_pabd.hip,
-// the translation units of the lane-group kernels for per-problem dense A (ipm_group_slot.inc), and the home of GROUP_SHAPES,
-// the shape list of all three.  Not part of the public ABI.
+// group_pa.h -- internal interface between abi_dense.hip (C ABI, handles; the launch plans are dense_tab.h's) and ipm_group_pa.hip /
+// ipm_group_pabd.hip / ipm_group_pabdh.hip, the translation units of the lane-group kernels for per-problem dense A
+// (ipm_group_slot.inc; on the self-dual embedding ipm_group_pabdhsd.inc), and the home of GROUP_SHAPES, the shape list of them all.
+// Not part of the public ABI.
 #ifndef PYCLLP_GROUP_PA_H
 #define PYCLLP_GROUP_PA_H
 #include "wave_common.h"
@@ -24,7 +25,7 @@ struct GeoPA {
 };
 
 // the lane-group shapes (MP, NP), ordered by cost: the first that covers (m, n) is used, in every table of ipm_dense.hip,
-// ipm_group_pa.hip and ipm_group_pabd.hip (the one list; tests/test_kernel_variants.py compares it with the Python side's)
+// ipm_group_pa.hip, ipm_group_pabd.hip and ipm_group_pabdh.hip (the one list; tests/test_kernel_variants.py compares it with the Python side's)
 #if defined(PYCLLP_DEV_ONLY_3296)   // development builds (tools/ab_*.sh): only the headline shape, compiles in a fraction of the time
 #define GROUP_SHAPES(X) X(32, 96)
 #elif defined(PYCLLP_DEV_ONLY_1648)
@@ -51,4 +52,7 @@ struct GroupPaVariants { const GroupPaVariant* v; int n; };
 extern const GroupPaVariants kGroupPA;
 // ... and with upper bounds: every GROUP_SHAPES shape, slack-aware only (sl = 1: the bounded equality form ends in the identity)
 extern const GroupPaVariants kGroupPABD;
+// ... with upper bounds on the homogeneous self-dual embedding (ipm_bounded_pa_hsd_kernel, ipm_group_pabdh.hip): every
+// GROUP_SHAPES shape, sl = 1; the launcher is null for a shape the kernel does not ship in (PABDHSD_SHAPES, dense_tab.h)
+extern const GroupPaVariants kGroupPABDH;
 #endif

@@ -32,6 +32,6 @@ ipm_bounded_hsd_kernel(int m, int n, long B, const double* __restrict__ Ag, cons
                        double* __restrict__ yg, double* __restrict__ zg, double* __restrict__ sg, double* __restrict__ pobj,
                        double* __restrict__ dobj, int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue,
                        DevOpts o) {
-    constexpr bool SL = true, BD = true;
+    constexpr bool SL = true, BD = true, PA = false;
 #include "ipm_group_hsd_body.inc"
 }

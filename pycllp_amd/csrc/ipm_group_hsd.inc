@@ -150,7 +150,8 @@ struct GWaveH : GWave<MP, NP, SL> {
 template <int MP> constexpr int hsd_wpb() { return MP == 16 ? PYCLLP_WPB : PYCLLP_WPB_HSD; }
 
 // The kernel is the text of ipm_group_hsd_body.inc under BD = false; ipm_bounded_hsd_kernel (ipm_group_bdhsd.inc) is the same
-// text with upper bounds, BD = true.
+// text with upper bounds, BD = true, and ipm_bounded_pa_hsd_kernel (ipm_group_pabdhsd.inc) with upper bounds and per-slot areas
+// for per-problem matrices, PA = true (GeoPA: group_pa.h).
 
 template <int MP, int NP, bool SL>
 __global__ void __launch_bounds__(hsd_wpb<MP>() * 64)
@@ -158,7 +159,7 @@ hsd_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                  const double* __restrict__ cg, double* __restrict__ xg, double* __restrict__ yg,
                  double* __restrict__ zg, double* __restrict__ pobj, double* __restrict__ dobj,
                  int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue, DevOpts o) {
-    constexpr bool BD = false;
+    constexpr bool BD = false, PA = false;
     const double* const ug = nullptr; double* const sg = nullptr;   // BD only
 #include "ipm_group_hsd_body.inc"
 }

@@ -1,31 +1,49 @@
 // ipm_group_hsd_body.inc -- the text of one lane-group kernel on the homogeneous self-dual embedding, included into the body of
-// hsd_group_kernel (ipm_group_hsd.inc, which has the model and GWaveH) and of ipm_bounded_hsd_kernel (ipm_group_bdhsd.inc, which
-// has the bounded system).  It expects in scope: MP, NP and the constants SL, BD (upper bounds: t, s, u); the kernel arguments
+// hsd_group_kernel (ipm_group_hsd.inc, which has the model and GWaveH), of ipm_bounded_hsd_kernel (ipm_group_bdhsd.inc, which
+// has the bounded system) and of ipm_bounded_pa_hsd_kernel (ipm_group_pabdhsd.inc: every LP has its own A).  It expects in
+// scope: MP, NP and the constants SL, BD (upper bounds: t, s, u), PA (per-slot A areas, Ag [B, m, n - m]; with SL and BD only);
+// the kernel arguments
 // m, n, B, Ag, bg, cg, ug, xg, yg, zg, sg, pobj, dobj, status, iters, queue, o (ug, sg: BD only).  Each phase is written once, in
 // the form of the bounded system (DESIGN.md section 26); strike the BD parts and the step of section 9 is left.  Where the two
 // kernels form the same quantity in different instruction forms, each keeps its own under BD: both stay instruction for
 // instruction what they were as texts of their own (profiles/group_hsd_body).  Included, not called: see ipm_group_slot.inc.
     using G_ = GeoG<MP, NP, SL>;
+    using P_ = GeoPA<G_>;                   // PA only
     constexpr int G = G_::G, NCG = G_::NCG, NCD = G_::NCD, ND = G_::ND, AS = G_::AS;
     static_assert(SL || !BD, "the bounded equality form ends in the identity");
+    static_assert(!PA || (SL && BD), "per-slot areas exist on the bounded embedding only");
     const int nd = SL ? n - m : n;          // dense columns of A as stored (the last m columns of the LP are the identity when SL)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
     const int wpb = blockDim.x / WAVE;
     double* Aimg = lds;
-    for (int i = tid; i < G_::AIMG; i += blockDim.x) {
-        const int r = i / AS, cidx = i % AS;
-        Aimg[i] = (r < m && cidx < nd) ? Ag[(size_t)r * n + cidx] : 0.0;
+    if constexpr (!PA) {   // the one A of the batch: image and Gram table, once per workgroup
+        for (int i = tid; i < G_::AIMG; i += blockDim.x) {
+            const int r = i / AS, cidx = i % AS;
+            Aimg[i] = (r < m && cidx < nd) ? Ag[(size_t)r * n + cidx] : 0.0;
+        }
+        G_::fill_gram_table(lds, tid, blockDim.x);
+        __syncthreads();
     }
-    G_::fill_gram_table(lds, tid, blockDim.x);
-    __syncthreads();
 
     GWaveH<MP, NP, SL> w;
     const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
     const int lane = tid & 63, gl = lane & (MP - 1), grp = lane / MP;
+    // PA (as ipm_group_slot_body.inc): G areas of this wave -- image, the place of the column sums, Gram table --, then its slabs
+    // and staging region; nothing is shared between the waves, so there is no workgroup barrier
+    double* const areas = PA ? lds + wave * P_::PW : nullptr;
+    if constexpr (PA) {
+        // pad rows and columns of every image are zero from here on: a refill writes rows < m, columns < nd only.  The column
+        // sums behind an image stay zero: the embedding starts at y = 0, A'y = 0 and never reads them.  (A slot that parks keeps
+        // its last LP's matrix; a NaN in it turns the parked group's own values NaN, and the `live` masks keep them there)
+        for (int i = lane; i < G * P_::AREA; i += WAVE) areas[i] = 0.0;
+        wave_lds_sync();
+        for (int g = 0; g < G; g++) G_::fill_gram_table(areas + g * P_::AREA, lane, WAVE);
+        Aimg = areas + grp * P_::AREA;      // the lane's own group's area
+    }
     w.lane = lane; w.gl = gl; w.grp = grp; w.m = m; w.n = n;
     w.Aimg = Aimg;
-    w.slab0 = lds + G_::SHARED + wave * G_::WSZ;
+    w.slab0 = PA ? areas + G * P_::AREA : lds + G_::SHARED + wave * G_::WSZ;
     w.slab = w.slab0 + grp * G_::SLAB;
     w.stage = w.slab0 + G * G_::SLAB;
     if constexpr (GWave<MP, NP, SL>::COLB) {
@@ -80,6 +98,37 @@
 
     while (__any(live)) {
         if (__any(fresh)) {
+            if constexpr (PA) {
+                // ---- refill: the whole wave copies the matrix of every fresh slot into that slot's image (no column sums:
+                // the start is y = 0) ----
+                const int asz = m * nd;     // doubles of one A_k
+#pragma unroll 1
+                for (int g = 0; g < G; g++) {
+                    if (__shfl((int)fresh, g * MP, WAVE) == 0) continue;
+                    const unsigned lo_ = (unsigned)__shfl((int)(unsigned)(lp & 0xFFFFFFFFl), g * MP, WAVE);
+                    const int hi_ = __shfl((int)(lp >> 32), g * MP, WAVE);
+                    const long lpg = ((long)hi_ << 32) | (long)lo_;
+                    const double* src = Ag + (size_t)lpg * (size_t)asz;
+                    double* img = areas + g * P_::AREA;
+                    // flat, coalesced reads, eight in flight per lane; (row, column) of element i advance by WAVE per step without a
+                    // division: WAVE = sr nd + sc
+                    int r = lane / nd, cidx = lane - r * nd;
+                    const int sr = WAVE / nd, sc = WAVE - sr * nd;
+#pragma unroll 1
+                    for (int i0 = lane; i0 < asz; i0 += 8 * WAVE) {
+                        double av[8];
+#pragma unroll
+                        for (int k = 0; k < 8; k++) av[k] = (i0 + k * WAVE < asz) ? src[i0 + k * WAVE] : 0.0;
+#pragma unroll
+                        for (int k = 0; k < 8; k++) {
+                            if (i0 + k * WAVE < asz) img[r * AS + cidx] = av[k];
+                            cidx += sc; r += sr;
+                            if (cidx >= nd) { cidx -= nd; r++; }
+                        }
+                    }
+                }
+                wave_lds_sync();
+            }
             if (fresh) {
                 const int go = w.ogl();
 #pragma unroll
@@ -340,7 +389,9 @@
                 }
                 wave_lds_sync();
                 double axg, adg;
+                if constexpr (PA) w.Aimg = areas + g * P_::AREA;       // group g's matrix (wave-uniform)
                 w.template gram_one<true, BD>(g, axg, adg);
+                if constexpr (PA) w.Aimg = Aimg;
                 wave_lds_sync();
                 if (grp == g) { Adc_ = axg; Adr_ = adg; }
             }

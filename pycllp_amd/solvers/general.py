@@ -151,6 +151,9 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
     _native_kernel = "bounded group"
     _hsd_entry = True         # the handle has ``solve_bounded_hsd``: solve_device(..., hsd=True) is available
     _hsd_spellings = ("native", "device")      # the values of ``hsd`` that ask for the embedding on this plugin's own kernel
+    hsd_device = False        # (``hip_general_batch_primal_normal``'s own option: the same re-solve on per-problem matrices)
+    _device_resolved = False  # the last native solve's non-optimal LPs were solved again on the device
+    _hsd_refused = None       # the handle whose embedding entry answered PYCLLP_E_UNSUPPORTED: not asked again, nothing gathered
 
     def __init__(self, device=None, stream=None, autoscale="auto", hsd="auto", predcorr=False, warm_start=False, **options):
         """``hsd='auto'`` (default): the LPs that do not end optimal on the bounded kernel are solved again through the
@@ -281,19 +284,25 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
         return out
 
     def _resolve_native(self, bl, out, extra_flags):
-        """hsd='native' / 'device': the LPs of ``out`` that did not end optimal, solved again on the embedding with the same handle --
-        their b^, c^, u^ gathered on the device, the results scattered into ``out``.  (The one look at the statuses waits for
-        the first launch.)"""
+        """hsd='native' / 'device' (and ``hsd_device`` of the batch plugin): the LPs of ``out`` that did not end optimal, solved
+        again on the embedding with the same handle -- their b^, c^, u^ (and, with per-problem values, their matrices A^)
+        gathered on the device, the results scattered into ``out``.  (The one look at the statuses waits for the first
+        launch.)  False where the library declines the embedding for this handle: the answer is the handle's, so it is asked
+        once."""
+        if self._hsd_refused is not None and self._hsd_refused is self._handle:
+            return False
         idx = torch.nonzero(out["status"] != 0).reshape(-1)
         if idx.numel() == 0:
-            return
-        sub = {k: bl[k].index_select(0, idx).contiguous() for k in ("b", "c", "u")}
+            return True
+        sub = {k: bl[k].index_select(0, idx).contiguous() for k in ("A", "b", "c", "u") if k in bl}
         try:
             again = self._launch_converted(sub, int(idx.numel()), extra_flags, {}, hsd=True)
         except NotImplementedError:
-            return                                  # (no kernel of this shape: the bounded kernel's verdict stands)
+            self._hsd_refused = self._handle
+            return False                            # (no kernel of this shape: the bounded kernel's verdict stands)
         for k, v in again.items():
             out[k].index_copy_(0, idx, v)
+        return True
 
     def solve(self, lp, verbose=0):
         glp = as_general(lp)
@@ -313,7 +322,8 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
     def _finish(self, glp, res, redo=True):
         """The tail of ``solve``: with ``hsd='auto'`` the LPs of a native solve that did not end optimal are solved again
         (``_redo`` picks them, ``_solve_again`` solves them), then ``res`` becomes the result attributes."""
-        if redo and self.hsd == "auto" and not self.hsd_native:      # (hsd='native' / 'device': done on the device, in _solve_native)
+        # (hsd='native' / 'device', and hsd_device where the embedding served: done on the device, in _solve_native)
+        if redo and self.hsd == "auto" and not self.hsd_native and not (self.hsd_device and self._device_resolved):
             idx = self._redo(glp, np.flatnonzero(res["status"] != 0))
             r2 = self._solve_again(subset(glp, idx)) if idx.size else None
             if r2 is not None:
@@ -352,8 +362,9 @@ class HipGeneralPrimalNormalSolver(DeviceArrays, BaseGeneralSolver):
                 out = self._launch_converted(bl, B, _native.FLAG_AUTOSCALE if wanted else 0, {})
             except NotImplementedError:
                 return None
-            if self.hsd_native:
-                self._resolve_native(bl, out, _native.FLAG_AUTOSCALE if wanted else 0)
+            self._device_resolved = False
+            if self.hsd_native or self.hsd_device:
+                self._device_resolved = self._resolve_native(bl, out, _native.FLAG_AUTOSCALE if wanted else 0)
             res = cv.from_bounded(self.stream, args[-2], fh, bl["invalid"], out)      # (args[-2]: l)
             torch.cuda.synchronize(self.device)
             return {k: res[k].cpu().numpy() for k in RESULTS}
@@ -446,7 +457,7 @@ class PerProblemBounded(object):
     ``solve`` launch the one entry.  A subclass states ``_delegate_class``, ``native_fits``, ``_make_handle(blp)`` (the
     ``Handle`` of the bounded form; ``NotImplementedError`` where the library declines it), ``_values(blp)`` (the per-problem
     array as the entry takes it, numpy), ``_values_spec(B)`` (the shape that array must have, and the text that says so),
-    ``_call(A, b, c, u, out, o)`` (the ``Handle`` call), ``_gather(glp, keep, sign)`` (the plan of that array as a gather
+    ``_call(A, b, c, u, out, o)`` (the ``Handle`` call; ``_call_hsd`` where ``_hsd_entry``: the same on the self-dual embedding), ``_gather(glp, keep, sign)`` (the plan of that array as a gather
     from one LP's values, ``lp.bounded_gather_*``; None where it is none) and ``_needs`` (what ``solve_device`` asks of
     ``init``); ``_unchanged``, ``_solve_delegate`` and ``_solve_again`` where it differs.
 
@@ -510,31 +521,39 @@ class PerProblemBounded(object):
         else:
             self._ensure_conversion(glp, keep, sign)
 
-    def solve_device(self, A_dev, b_dev, c_dev, u_dev, **options):
+    def solve_device(self, A_dev, b_dev, c_dev, u_dev, hsd=False, **options):
         """Device-resident entry, in the bounded form's variables: the per-problem array (``_values_spec``; the subclass says
         how to make it), b [B, m'], c and u [B, N] (torch CUDA tensors or numpy) -> dict of CUDA tensors (``BOUNDED_RESULTS``).
         Asynchronous on the solver's stream; the kernel's verdict stands (no look at the data: ``autoscale='auto'`` and
-        ``hsd='auto'`` count as off)."""
+        ``hsd='auto'`` count as off).  ``hsd=True`` (``hip_general_batch_primal_normal``): the whole batch runs on the kernel's
+        self-dual embedding (``_call_hsd``) in one launch, still without a sync; ``ValueError`` on a plugin without one."""
+        self._check_hsd(hsd)
         if self._handle is None:
             raise RuntimeError("solve_device() needs init() on an LP the %s" % self._needs)
-        return self._launch(self._dev(A_dev), self._dev(b_dev), self._dev(c_dev), self._dev(u_dev), 0, options)
+        return self._launch(self._dev(A_dev), self._dev(b_dev), self._dev(c_dev), self._dev(u_dev), 0, options, hsd=bool(hsd))
 
-    def solve_device_general(self, Adata, a, b, c, l, u, f=None, **options):
+    def _check_hsd(self, hsd):
+        if hsd and not self._hsd_entry:
+            raise ValueError("hsd=True is not available for %s (its kernel has no self-dual embedding)" % self.name)
+
+    def solve_device_general(self, Adata, a, b, c, l, u, f=None, hsd=False, **options):
         """Device-resident entry, in the ORIGINAL variables: Adata [B, nnz] (every LP's values in the order of the coordinate
         lists given to ``init``), a, b [B, m], c, l, u [B, n], f [B] (torch CUDA tensors, or numpy arrays, which are uploaded;
         ``l`` and ``f`` may be None = 0) -> dict of CUDA tensors: ``RESULTS`` and ``invalid`` (i32 [B]: 0, or the check of
         ``pycllp_hip_general_to_bounded_batch`` the LP failed; such an LP has status 3 and NaN results).  Conversion, bounded
         solve and back-conversion are queued on the solver's stream and nothing waits for them; the kernel's verdict stands (no
-        look at the data: ``autoscale='auto'`` and ``hsd='auto'`` count as off).  ``options``: fields of ``pycllp_hip_opts``
-        for this call."""
+        look at the data: ``autoscale='auto'`` and ``hsd='auto'`` count as off).  ``hsd=True``: as ``solve_device``'s, with the
+        certificates in the GeneralLP's variables (``y, z, s`` / ``x = l +`` the ray).  ``options``: fields of
+        ``pycllp_hip_opts`` for this call."""
+        self._check_hsd(hsd)
         if self._handle is None or self._conv is None:
             raise RuntimeError("solve_device_general() needs init() on an LP the %s" % self._needs)
-        return self._solve_on_device(Adata, a, b, c, l, u, f, options)
+        return self._solve_on_device(Adata, a, b, c, l, u, f, options, hsd=bool(hsd))
 
-    def _launch_converted(self, bl, B, extra_flags, overrides):
-        return self._launch(bl["A"].view(self._values_spec(B)[0]), bl["b"], bl["c"], bl["u"], extra_flags, overrides)
+    def _launch_converted(self, bl, B, extra_flags, overrides, hsd=False):
+        return self._launch(bl["A"].view(self._values_spec(B)[0]), bl["b"], bl["c"], bl["u"], extra_flags, overrides, hsd=hsd)
 
-    def _launch(self, A, b, c, u, extra_flags, overrides):
+    def _launch(self, A, b, c, u, extra_flags, overrides, hsd=False):
         B, mk, N = int(b.shape[0]), self.mk, self.n + self.mk
         a_shape, a_text = self._values_spec(B)
         if (b.dim() != 2 or b.shape[1] != mk or tuple(c.shape) != (B, N) or tuple(u.shape) != (B, N)
@@ -544,7 +563,7 @@ class PerProblemBounded(object):
         out = bounded_outputs(B, mk, N, self.device)
         o = solve_opts(self.options, extra_flags, **overrides)
         if B:                                   # (an empty tensor has no address to hand over; the entry launches nothing for B = 0)
-            self._call(A, b, c, u, out, o)
+            (self._call_hsd if hsd else self._call)(A, b, c, u, out, o)
         self._keepalive = (A, b, c, u)
         self.kernel = self._native_kernel
         return out
@@ -563,6 +582,7 @@ class PerProblemBounded(object):
         if glp.nrows != self.m or glp.ncols != self.n:
             raise ValueError("LP shape changed since init(): (%d,%d) vs (%d,%d)" % (glp.nrows, glp.ncols, self.m, self.n))
         res = None
+        self._device_resolved = False
         if self._delegate is None:
             form, keep, sign = self._form(glp)
             if not self._unchanged(glp, form):

@@ -42,17 +42,32 @@ class HipGeneralBatchPrimalNormalSolver(PerProblemBounded, HipGeneralPrimalNorma
     kept rows and N = n + m' = 256 columns, the structure of A fully dense -- on the bounded wave kernel with a dense image per
     wave: ``kernel == 'bounded wave per-problem'``, the same three entries.  There ``hsd='auto'`` solves the LPs that do not end
     optimal again only where their expansion fits the sparse path's per-problem kernels (128 rows, 512 columns); elsewhere the
-    kernel's status stands.  The option is this plugin's alone: a delegate does not get it."""
+    kernel's status stands.  The option is this plugin's alone: a delegate does not get it.
+
+    ``hsd_device=True`` (default False; needs ``hsd='auto'``): the LPs that do not end optimal on the lane-group kernel are
+    solved again ON THE DEVICE, on that kernel's self-dual embedding (``pycllp_hip_dense_solve_batch_bounded_hsd``, DESIGN.md
+    section 28) with the same handle -- their rows of A^, b^, c^, u^ gathered on the device, the results scattered back before the
+    back-conversion; no expansion, no second solver, no host conversion.  A status-2 LP then carries its certificate in
+    ``y, z, s``, a status-4 LP has ``x = l +`` the ray.  Where the library declines the embedding (a ``dense_wave`` handle
+    beyond the lane-group kernels) those LPs take the route of ``hsd='auto'``; a delegate does not get the option.
+    ``solve_device(..., hsd=True)`` and ``solve_device_general(..., hsd=True)`` run the whole batch on the embedding in one
+    launch, with or without ``hsd_device``."""
     name = 'hip_general_batch_primal_normal'
     _native_kernel = "bounded group per-problem"
     _delegate_class = HipGeneralPrimalNormalSolver
     _needs = "bounded per-problem kernel serves (per-problem A, m' <= 32, n <= 96)"
     _wave = False       # the handle is one beyond the lane-group kernels (dense_wave)
+    _hsd_entry = True   # the handle has ``solve_batch_bounded_hsd``: solve_device(..., hsd=True) is available
 
-    def __init__(self, *args, dense_wave=False, **kwargs):
+    def __init__(self, *args, dense_wave=False, hsd_device=False, **kwargs):
         if not isinstance(dense_wave, (bool, np.bool_)):
             raise ValueError("dense_wave must be True or False; got %r" % (dense_wave,))
+        if not isinstance(hsd_device, (bool, np.bool_)):
+            raise ValueError("hsd_device must be True or False; got %r" % (hsd_device,))
         super(HipGeneralBatchPrimalNormalSolver, self).__init__(*args, **kwargs)
+        if hsd_device and self.hsd != "auto":
+            raise ValueError("hsd_device=True needs hsd='auto': it says where the LPs that do not end optimal are solved again")
+        self.hsd_device = bool(hsd_device)
         self.dense_wave = bool(dense_wave)
         if self.dense_wave:
             self.native_fits = functools.partial(type(self).native_fits, dense_wave=True)
@@ -106,6 +121,9 @@ class HipGeneralBatchPrimalNormalSolver(PerProblemBounded, HipGeneralPrimalNorma
 
     def _call(self, A, b, c, u, out, o):
         self._handle.solve_batch_bounded(self.stream, A, b, c, u, out, o)
+
+    def _call_hsd(self, A, b, c, u, out, o):
+        self._handle.solve_batch_bounded_hsd(self.stream, A, b, c, u, out, o)
 
     # hsd='auto' on the wave kernel's handle: as sparse_general_batch -- the expansion has per-problem values too
     def _redo(self, glp, idx):

@@ -295,6 +295,13 @@ class Handle(object):
         n <= 256) on the bounded wave kernel with an image per wave."""
         self._solve_batch("solve_batch_bounded", stream, A, (b, c, u), [out[k] for k in BOUNDED_RESULTS], o)
 
+    def solve_batch_bounded_hsd(self, stream, A, b, c, u, out, o):
+        """``solve_batch_bounded`` on the homogeneous self-dual embedding with bounds
+        (``pycllp_hip_dense_solve_batch_bounded_hsd``, lane-group kernels only): statuses 2 and 4 come with their certificate in
+        ``out`` (y, z, s / x), 0 and 5 with the solution.  ``NotImplementedError`` beyond the lane-group kernels and for a shape
+        the kernel does not ship in."""
+        self._solve_batch("solve_batch_bounded_hsd", stream, A, (b, c, u), [out[k] for k in BOUNDED_RESULTS], o)
+
     def plan_batch_bounded(self, stream, a_cols):
         """An empty batch (B = 0) through ``solve_batch_bounded``'s entry with matrices of ``a_cols`` columns: nothing is
         launched, but a handle beyond the lane-group kernels builds the bounded wave kernel's plan now, and
