@@ -374,8 +374,29 @@ struct GWave {
     // swap hands to both rows (whole wave active at every call site).  STAGED: u through the wave's staging area instead -- a
     // write, a wave sync and MP broadcast reads, as before the lane swaps -- for the kernel that pays for the registers with
     // scratch (AT_STAGED in the HSD kernel).  Same FMAs in the same order either way.
-    template <bool STAGED = false>
+    // FUSED (not with STAGED): no copy of u_i at all -- each FMA takes the row broadcast itself (v_fmac_f64_dpp, as subst15_up):
+    // the same two factors and the same addend, so the same bits, for two moves per row of A less.  The s_nop in front of a
+    // batch covers the VALU-write -> DPP-read hazard of `ur`, which the hazard recogniser does not see through inline asm.
+    // One statement per batch, so that nothing the compiler places (a copy of `ur`, say) can stand between the s_nop and a DPP read.
+    template <int K0>
+    __device__ __forceinline__ static void at_batch_fused(double (&out)[NCG], double ur, const double (&a)[PYCLLP_AT_RB][NCD]) {
+        static_assert(PYCLLP_AT_RB == 4 && NCD == 2, "written for batches of four rows and two dense registers per lane");
+        asm volatile("s_nop 1\n\t"
+                     "v_fmac_f64_dpp %0, %2, %3 row_newbcast:" DPP_STR(%11) " row_mask:0xf bank_mask:0xf\n\t"
+                     "v_fmac_f64_dpp %1, %2, %4 row_newbcast:" DPP_STR(%11) " row_mask:0xf bank_mask:0xf\n\t"
+                     "v_fmac_f64_dpp %0, %2, %5 row_newbcast:" DPP_STR(%12) " row_mask:0xf bank_mask:0xf\n\t"
+                     "v_fmac_f64_dpp %1, %2, %6 row_newbcast:" DPP_STR(%12) " row_mask:0xf bank_mask:0xf\n\t"
+                     "v_fmac_f64_dpp %0, %2, %7 row_newbcast:" DPP_STR(%13) " row_mask:0xf bank_mask:0xf\n\t"
+                     "v_fmac_f64_dpp %1, %2, %8 row_newbcast:" DPP_STR(%13) " row_mask:0xf bank_mask:0xf\n\t"
+                     "v_fmac_f64_dpp %0, %2, %9 row_newbcast:" DPP_STR(%14) " row_mask:0xf bank_mask:0xf\n\t"
+                     "v_fmac_f64_dpp %1, %2, %10 row_newbcast:" DPP_STR(%14) " row_mask:0xf bank_mask:0xf"
+                     : "+v"(out[0]), "+v"(out[1])
+                     : "v"(ur), "v"(a[0][0]), "v"(a[0][1]), "v"(a[1][0]), "v"(a[1][1]), "v"(a[2][0]), "v"(a[2][1]), "v"(a[3][0]), "v"(a[3][1]),
+                       "n"(K0), "n"(K0 + 1), "n"(K0 + 2), "n"(K0 + 3));
+    }
+    template <bool STAGED = false, bool FUSED = false>
     __device__ __forceinline__ void At_times(double u, double (&out)[NCG]) const {
+        static_assert(!(STAGED && FUSED), "FUSED reads u from registers");
         const int g = ogl();
         double ur[2] = {u, u};
         const __attribute__((address_space(3))) double* ub = nullptr;
@@ -395,17 +416,21 @@ struct GWave {
     static_for<0, RB>([&](auto ic_) {                                                           \
         constexpr int ii = decltype(ic_)::value, i_ = (I0) + ii;                                \
         if constexpr (STAGED) U_[ii] = ub[i_ + tok];                                            \
-        else U_[ii] = row_bcast<(i_ & 15)>(ur[i_ >> 4]);                                        \
+        else if constexpr (!FUSED) U_[ii] = row_bcast<(i_ & 15)>(ur[i_ >> 4]);                  \
         _Pragma("unroll") for (int q = 0; q < NCD; q++) A_[ii][q] = ac[i_ * AS + MP * q + tok]; \
     });
-#define AT_USE(A_, U_)                                                                          \
+#define AT_USE(A_, U_, I0)                                                                      \
     _Pragma("unroll") for (int ii = 0; ii < RB; ii++) {                                         \
-        asm volatile("" : "+v"(U_[ii]));                                                        \
+        if constexpr (!FUSED) asm volatile("" : "+v"(U_[ii]));                                  \
         _Pragma("unroll") for (int q = 0; q < NCD; q++) asm volatile("" : "+v"(A_[ii][q]));     \
     }                                                                                           \
     asm volatile("" : "+v"(tok));                                                               \
-    _Pragma("unroll") for (int ii = 0; ii < RB; ii++)                                           \
-        _Pragma("unroll") for (int q = 0; q < NCD; q++) out[q] = fma(A_[ii][q], U_[ii], out[q]); \
+    if constexpr (FUSED) {                                                                      \
+        at_batch_fused<(I0) & 15>(out, ur[(I0) >> 4], A_);                                      \
+    } else {                                                                                 \
+        _Pragma("unroll") for (int ii = 0; ii < RB; ii++)                                       \
+            _Pragma("unroll") for (int q = 0; q < NCD; q++) out[q] = fma(A_[ii][q], U_[ii], out[q]); \
+    }                                                                                           \
     _Pragma("unroll") for (int q = 0; q < NCD; q++) asm volatile("" : "+v"(out[q]));
 #pragma unroll
         for (int q = 0; q < NCG; q++) out[q] = 0.0;
@@ -419,9 +444,9 @@ struct GWave {
         static_for<0, NB / 2>([&](auto bc) {
             constexpr int b2 = 2 * decltype(bc)::value;
             AT_LOAD(a1, u1, (b2 + 1) * RB)
-            AT_USE(a0, u0)
+            AT_USE(a0, u0, b2 * RB)
             if constexpr (b2 + 2 < NB) { AT_LOAD(a0, u0, (b2 + 2) * RB) }
-            AT_USE(a1, u1)
+            AT_USE(a1, u1, (b2 + 1) * RB)
         });
 #undef AT_LOAD
 #undef AT_USE
@@ -471,7 +496,7 @@ struct GWave {
     // group (ax is left alone without AX).  Reached with the whole wave active, which the lane swaps of its last lines need.
     // LATE: the store offsets are read after the k-loop instead of before it (their latency is then exposed, but they are not live
     // across the loop: the bounded kernel, which has no registers to spare there, spilt four without it).
-    template <bool AX = true, bool LATE = false>
+    template <bool AX = true, bool LATE = false, bool SELB = false>
     __device__ __forceinline__ void gram_one(int g, double& ax, double& ad) const {
         double axp[JB], adp[JB];
         int lo0_ = lane;                      // opaque copy: see ogl()
@@ -504,6 +529,9 @@ struct GWave {
                 for (int r = 0; r < GRAM_INSTS; r++) so[r] = tab[64 * r];
             }
             const bool top = cc < 8;              // instruction 4: blocks 0, 1 own tile b, blocks 2, 3 own tile b + 4
+            // SELB: that choice as a lane-dependent base formed once, read and scaled again in every k-step (one read and one
+            // multiply on the factors of ad[0] or ad[1]: the same product) instead of two selects per k-step
+            const double* asel = arow + (top ? 0 : 16 * AS);
             double4_t acc10 = (double4_t){0.0, 0.0, 0.0, 0.0};
             double acc[GRAM_INSTS];
 #pragma unroll
@@ -528,7 +556,8 @@ struct GWave {
                     acc[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad[1], a[1], acc[1], 0, 0, 0);
                     acc[2] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad[0], p3, acc[2], 0, 0, 0);
                     acc[3] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad[1], p7, acc[3], 0, 0, 0);
-                    acc[4] = __builtin_amdgcn_mfma_f64_4x4x4f64(top ? ad[0] : ad[1], p2, acc[4], 0, 0, 0);
+                    if constexpr (SELB) acc[4] = __builtin_amdgcn_mfma_f64_4x4x4f64(asel[4 * s] * dk, p2, acc[4], 0, 0, 0);
+                    else acc[4] = __builtin_amdgcn_mfma_f64_4x4x4f64(top ? ad[0] : ad[1], p2, acc[4], 0, 0, 0);
                 }
             }
             int lo_ = lane;                       // opaque copy: see ogl()
@@ -696,16 +725,36 @@ struct GWave {
     //   LDS but cost 0.011 ms of the 0.089 ms this split gains on 65 536 LPs of 32 x 64, profiles/sweep_split).  Columns 16 .. 31,
     //   the carried forward substitution, the column stores of L and the guard's running maximum are those of the plain sweep.
     // A kernel takes SP where it costs no scratch and no spilt register (its `SPLIT` constant, next to `CARRY`).
-    template <bool RELF = false, bool SP = SPLIT>
+    // SIGN: the verdict "the Nocedal-Wright guard would have bitten" (some u_i^2 / D_j > beta^2) from the pivots instead of a
+    // running maximum of y_ij = l_i u_i per column and lane.  If no pivot of a group is <= 0 or NaN, nothing bit:
+    //   1. rD > 0 and l_i = fl(u_i rD) has the sign of u_i (or is a zero of that sign), so every product l_i u_i is >= 0.
+    //   2. A trailing diagonal entry changes only by W_ii <- fma(-l_i, u_i, W_ii): the exact value does not grow, and rounding
+    //      is monotone, so W_ii never increases.  It starts at M_ii <= beta^2 = max |diag M|.
+    //   3. fl(l_i u_i) > beta^2 implies that the exact product exceeds beta^2 (rounding is monotone and beta^2 is a double), so
+    //      at that column the exact W_ii - l_i u_i is below zero and W_ii comes out negative (or -0: a sign bit that no later
+    //      update clears, since -l_i u_i always carries it) and stays at or below that value.
+    //   4. So row i's own pivot is not > 0 when its column comes.  A NaN on the diagonal stays NaN and fails `> 0` as well.
+    // The converse does not hold: a pivot <= 0 where nothing bit (M singular to rounding) now takes the redo too.  The redo is
+    // factor_guarded_inplace, whose arithmetic is the sweep's wherever the guard does not bite (what PYCLLP_FLAG_FORCE_GUARD_PATH
+    // and tests/test_fused_forward.py rest on), so the results keep their bits (tests/test_guard_sign.py).  Two limits.  That
+    // equality is not a theorem at every magnitude: on the diverging LPs of tests/golden/status_cases.npz the forced path leaves
+    // the sweep's trajectory (in the parent too), so there "the parent's bits" is a measurement (the eight shapes and three
+    // singular batches of tools/dev/outputs_vs_parent.py, byte for byte), not an argument.  And the redo costs time: a batch whose
+    // M has a zero or a redundant row has a pivot that is zero or negative by rounding in most iterations, and every such wave
+    // re-forms M and runs the run-time loops of the guarded path, where the parent stayed on the hot sweep -- 16 384 LPs of
+    // 32 x 96 with a duplicated and a zero row 2.02 -> 9.00 ms, of 12 x 40 0.50 -> 1.30 ms (profiles/guard_sign).  Only the pivot's own
+    // lane votes (chain_colp_*: the one-hot mask that captures rdiag): in columns 16 .. 31 the top DPP row's W[j] is a don't-care
+    // value.  Padded rows are identity rows, pivot 1.
+    template <bool RELF = false, bool SP = SPLIT, bool SIGN = false>
     __device__ __forceinline__ bool factor_dpp(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
                                                const double* fl = nullptr) const {
-        return factor_sweep<RELF, 0, SP>(W, beta2, floor_, live, rdiag, fl, nullptr);
+        return factor_sweep<RELF, 0, SP, SIGN>(W, beta2, floor_, live, rdiag, fl, nullptr);
     }
     // r <- L^-1 r for the NR right-hand sides r (lane = row) along with the factorisation; the caller goes on with backward()
-    template <bool RELF = false, bool SP = SPLIT, int NR>
+    template <bool RELF = false, bool SP = SPLIT, bool SIGN = false, int NR>
     __device__ __forceinline__ bool factor_dpp_fwd(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
                                                    double (&r)[NR], const double* fl = nullptr) const {
-        return factor_sweep<RELF, NR, SP>(W, beta2, floor_, live, rdiag, fl, r);
+        return factor_sweep<RELF, NR, SP, SIGN>(W, beta2, floor_, live, rdiag, fl, r);
     }
     // operation `op` (0 .. 31) of the bottom DPP row's part of the carried forward substitution, MP = 32 (see above)
     template <int OP, int NR>
@@ -721,7 +770,7 @@ struct GWave {
             for (int i = 0; i < NR; i++) fwd_step<OP - 17, 0xA>(r[i], W[OP - 1]);    // step of column OP - 1
         }
     }
-    template <bool RELF, int NR, bool SP>
+    template <bool RELF, int NR, bool SP, bool SIGN>
     __device__ __forceinline__ bool factor_sweep(double (&W)[MP], double beta2, double floor_, bool live, double& rdiag,
                                                  const double* fl, double* r) const {
         rdiag = 1.0;
@@ -738,6 +787,7 @@ struct GWave {
 #pragma unroll
         for (int i = 0; i < NR1; i++) { so[i] = 0.0; acc[i] = 0.0; }
         double ymax = 0.0;         // running max of u^2 / D over the lanes below the pivots: the guard bites iff it exceeds beta^2
+        double pv = 1.0;           // SIGN: the lane's own pivot, kept when its column comes (see above)
         static_for<0, MP>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             const double u = W[j];
@@ -761,9 +811,11 @@ struct GWave {
             double l = 0.0;        // L[gl][j] = u / D below the pivot, 0 on and above it
             asm volatile("" : "+v"(l));
             if constexpr (MP == 16) {
-                chain_step_exec<j, MB_, MB_, 1, ONE_, ONE_>(W, 0.0, rD, l, ymax, rdiag);
+                if constexpr (SIGN) chain_step_piv<j, MB_, MB_, 1, ONE_, ONE_>(W, 0.0, rD, l, pv, rdiag);
+                else chain_step_exec<j, MB_, MB_, 1, ONE_, ONE_>(W, 0.0, rD, l, ymax, rdiag);
             } else if constexpr (j < 16) {
-                chain_step_exec<j, MB_, MB_, 0, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[0]), src, rD, l, ymax, rdiag);
+                if constexpr (SIGN) chain_step_piv<j, MB_, MB_, 0, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[0]), src, rD, l, pv, rdiag);
+                else chain_step_exec<j, MB_, MB_, 0, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[0]), src, rD, l, ymax, rdiag);
                 // the bottom-right block's columns.  SP: half of them per DPP row (see above; the top lanes' W[24 .. 31] are M22's
                 // columns 16 .. 23 of row R).  Plain: all sixteen in ALL lanes -- what the top row's lanes hold in W[16..31] is then
                 // never read (upper triangle; overwritten with 0 when its column comes), so the EXEC mask of rounds 2-3 only cost
@@ -771,7 +823,8 @@ struct GWave {
                 if constexpr (SP) chain_half_neg(*reinterpret_cast<double (*)[8]>(&W[24]), ror8_top_d(ub), rD);
                 else chain_all_neg(*reinterpret_cast<double (*)[16]>(&W[16]), W[j], l);
             } else {
-                chain_step_exec<j - 16, MB_, MB_, 1, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[16]), 0.0, rD, l, ymax, rdiag);
+                if constexpr (SIGN) chain_step_piv<j - 16, MB_, MB_, 1, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[16]), 0.0, rD, l, pv, rdiag);
+                else chain_step_exec<j - 16, MB_, MB_, 1, ONE_, ONE_>(*reinterpret_cast<double (*)[16]>(&W[16]), 0.0, rD, l, ymax, rdiag);
             }
             W[j] = l;
             if constexpr (COLB) *(__attribute__((address_space(3))) double*)(size_t)(xb[j & 15] + 256u * (unsigned)(j & ~15)) = l;
@@ -787,7 +840,9 @@ struct GWave {
             if constexpr (SP && j == 15) merge_through_slab(W);
         });
         if constexpr (NR > 0 && MP == 32) fwd_bottom_op<31, NR>(W, r, so, acc);
-        const bool viol = live && (ymax > beta2);
+        // SIGN: every lane is the pivot lane of one column of its group and votes with its own pivot (zero, negative or NaN);
+        // the lanes of an idle group do not vote, as before
+        const bool viol = SIGN ? live && !(pv > 0.0) : live && (ymax > beta2);
         if constexpr (PRIO_ != 0) __builtin_amdgcn_s_setprio(0);
         if constexpr (!CARRY) {    // (32, 128): the swizzled addresses are formed here, not held across the sweep
             const int g = ogl();
@@ -931,6 +986,13 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
     // (32, 96) one and the general (32, 128) one spill 2 VGPRs each (the copy after the k-loop, rolled, or half of it: 11 to
     // 49), so they keep the product
     constexpr bool FIRST_IMAGE = GWave<MP, NP, SL>::FIRST_IMAGE && !(PC && ((SL && NP == 96) || (!SL && NP == 128)));
+    // Three cuts of vector issue that the plain-step instantiations take (profiles/guard_sign; the predictor-corrector kernels sit
+    // at the register limit -- the slack-aware (32, 96) one spills 2 to 3 VGPRs with GRAM_SELB or AT_FUSED, the general one 1 with
+    // PIVOT_SIGN -- and keep the parent's text): the guard's verdict from the pivots' signs (GWave::factor_sweep), the Gram loop's
+    // fifth tile without its selects (GWave::gram_one) and A'u with the row broadcast inside the FMA where a lane holds two
+    // dense registers (GWave::At_times)
+    constexpr bool PIVOT_SIGN = !PC, GRAM_SELB = !PC;
+    constexpr bool AT_FUSED = !PC && NCD == 2 && PYCLLP_AT_RB == 4;
     const int nd = SL ? n - m : n;          // dense columns of A (the last m columns are the identity when SL)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
@@ -1042,7 +1104,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             for (int q = 0; q < NCG; q++) c2 = fma(c[q], c[q], c2);
             const double nb2 = grp_sum<MP>(b * b), nc2 = grp_sum<MP>(c2);
             double vw[NCG];
-            if (warm) w.At_times(y, vw);
+            if (warm) w.template At_times<false, AT_FUSED>(y, vw);
             if (fresh) {
                 tol_r = o.eps * (1.0 + sqrt(nb2));
                 tol_s = o.eps * (1.0 + sqrt(nc2));
@@ -1193,9 +1255,9 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
                 }
                 wave_lds_sync();
                 double axg = 0.0, adg;
-                if (carried) w.template gram_one<false>(g, axg, adg);
+                if (carried) w.template gram_one<false, false, GRAM_SELB>(g, axg, adg);
                 else if (from_image) w.gram_first(g, first, axg, adg);
-                else w.template gram_one<true>(g, axg, adg);
+                else w.template gram_one<true, false, GRAM_SELB>(g, axg, adg);
                 wave_lds_sync();
                 if (grp == g) { Ax_ = axg; Adt_ = adg; }
             }
@@ -1240,8 +1302,8 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             wave_lds_sync();
             STAMP(3)
             bool redo;
-            if constexpr (CARRY) redo = w.template factor_dpp_fwd<false, SPLIT>(W, beta2, o.pivot_floor, live, rdiag, fs);
-            else redo = w.template factor_dpp<false, SPLIT>(W, beta2, o.pivot_floor, live, rdiag);
+            if constexpr (CARRY) redo = w.template factor_dpp_fwd<false, SPLIT, PIVOT_SIGN>(W, beta2, o.pivot_floor, live, rdiag, fs);
+            else redo = w.template factor_dpp<false, SPLIT, PIVOT_SIGN>(W, beta2, o.pivot_floor, live, rdiag);
             if (redo || (o.flags & PYCLLP_FLAG_FORCE_GUARD_PATH)) {
                 // the Nocedal-Wright guard would have bitten somewhere: re-form M and factor with the guard applied
                 double Ax2, Adt2;
@@ -1257,7 +1319,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             // ---- predictor (mu = 0): dy_a, dx_a, dz_a; how far it gets; centering; the corrector's right-hand side ----
             const double dya = fused ? w.back_after_sweep(fs[0], rdiag) : w.fwd_back(rhs, rdiag);
             double wva[NCG], dxa[NCG], dza[NCG], dt[NCG];
-            w.At_times(dya, wva);
+            w.template At_times<false, AT_FUSED>(dya, wva);
             double tha = 0.0;
 #pragma unroll
             for (int q = 0; q < NCG; q++) {
@@ -1288,7 +1350,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
         double dy = (!PC && fused) ? w.back_after_sweep(fs[0], rdiag) : w.fwd_back(rhs_c, rdiag);
         STAMP(5)
         double wv[NCG], dx[NCG], d[NCG];
-        w.At_times(dy, wv);
+        w.template At_times<false, AT_FUSED>(dy, wv);
         // d and t are recomputed (bit-identical) rather than kept alive across the factorisation: 12 VGPRs
 #pragma unroll
         for (int q = 0; q < NCG; q++) {
@@ -1309,7 +1371,7 @@ ipm_group_kernel(int m, int n, long B, const double* __restrict__ Ag, const doub
             if (!__any(need)) break;
             const double eta = w.fwd_back(need ? e : 0.0, rdiag);
             double w2[NCG];
-            w.At_times(eta, w2);
+            w.template At_times<false, AT_FUSED>(eta, w2);
 #pragma unroll
             for (int q = 0; q < NCG; q++) {
                 dx[q] = fma(d[q], w2[q], dx[q]);

@@ -4,10 +4,10 @@
     PYCLLP_HIP_LIB=<new library>    python tools/dev/outputs_vs_parent.py --dump DIR_B
     python tools/dev/outputs_vs_parent.py --compare DIR_A DIR_B [BENCH_DIR_A BENCH_DIR_B]
 
---dump solves 26 seeded batches of 8 192 LPs (one per family and option: plain, HSD, predictor-corrector, guarded path,
+--dump solves 37 seeded batches, 26 of 8 192 LPs (one per family and option: plain, HSD, predictor-corrector, guarded path,
 refinement, autoscale, the (16, .), (32, 64), (32, 128) shapes, without identity tail, bounded, per-problem A, bounded per-problem
-A) and writes status, iters, pobj, dobj, x, y, z of each to DIR/<case>.npz, with one line per case (kernel, lane-group shape, LPs
-at status 0).  --compare wants np.array_equal on every array (and on the <name>.npy files of two `bench.py --dump-outputs`
+A), the eight shapes of tests/golden/status_cases.npz on the plain path and three batches with a duplicated and a zero row, and writes status, iters, pobj, dobj, x, y, z of each to DIR/<case>.npz, with one line per case (kernel, lane-group shape, LPs
+at status 0).  --compare wants equal bytes on every array (and on the <name>.npy files of two `bench.py --dump-outputs`
 directories, if given) and exits 1 otherwise.  The library is the one PYCLLP_HIP_LIB names, as everywhere."""
 import os
 import sys
@@ -47,6 +47,22 @@ def bounded_per_problem(shape, seed):
     return "hip_general_batch_primal_normal", time_bounded_perA.workload(*shape, B, seed), dict(hsd=False, autoscale=False)
 
 
+def status_case(k):
+    """Shape k of tests/golden/status_cases.npz on the plain path: mixed-sign LPs, most of them infeasible or unbounded, whose
+    iterates diverge -- pivots of every size and sign, and non-finite values, pass through the sweep."""
+    from conftest import status_cases
+    from pycllp_amd.lp import SparseMatrix, StandardLP
+    A, b, c = status_cases()[k][:3]
+    lp = StandardLP(SparseMatrix(matrix=np.asarray(A)), b, c, 0.0).to_equality_form()
+    return "hip_dense_primal_normal", lp, dict(autoscale=False, hsd=False)
+
+
+def singular(m, N):
+    """A duplicated and a zero row (tests/test_guard_sign.py): M singular to rounding, pivots <= 0 where the guard does not bite."""
+    from test_guard_sign import singular_lp
+    return "hip_dense_primal_normal", singular_lp(m, N, 2048, seed=100 * m + N), dict(autoscale=False, hsd=False)
+
+
 PC = dict(predcorr=True)
 CASES = [
     ("dense3 plain 32x64", lambda: dense(32, 64)),
@@ -75,7 +91,17 @@ CASES = [
     ("perA 24x30", lambda: per_problem(24, 30)),
     ("bounded perA 24x64", lambda: bounded_per_problem((8, 8, 8, 64), 1)),
     ("bounded perA 12x32", lambda: bounded_per_problem((4, 4, 4, 32), 2)),
+    # where the hot sweep's redo verdict decides something: non-positive and non-finite pivots
+] + [("status cases %d" % k, lambda k=k: status_case(k)) for k in range(8)] + [
+    ("singular 32x96", lambda: singular(32, 96)),
+    ("singular 24x60 (32,64)", lambda: singular(24, 60)),
+    ("singular 12x40 (16,48)", lambda: singular(12, 40)),
 ]
+
+
+def same_bits(x, y):
+    """np.array_equal on the bytes: a NaN equals the same NaN, -0 does not equal +0"""
+    return x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes()
 
 
 def dump(out):
@@ -96,13 +122,13 @@ def compare(a, b, bench_a=None, bench_b=None):
     bad = 0
     for f in sorted(os.listdir(a)):
         x, y = np.load(os.path.join(a, f)), np.load(os.path.join(b, f))
-        diff = [q for q in x.files if q not in y.files or not np.array_equal(x[q], y[q])]
+        diff = [q for q in x.files if q not in y.files or not same_bits(x[q], y[q])]
         bad += len(diff)
         print("%-40s %d arrays  %s" % (f[:-4].replace("_", " "), len(x.files), "bit-identical" if not diff else "DIFFER: %s" % diff))
     if bench_a:
         for f in sorted(os.listdir(bench_a)):
             x, y = np.load(os.path.join(bench_a, f)), np.load(os.path.join(bench_b, f))
-            same = np.array_equal(x, y)
+            same = same_bits(x, y)
             bad += not same
             print("bench.py --dump-outputs %-20s shape %-16s %s" % (f, x.shape, "bit-identical" if same else "DIFFERS"))
     print("arrays that differ: %d" % bad)
