@@ -14,12 +14,17 @@
 //     t <  s:  ds = dz + eta sigma + c dtau - A'dy,  dt = dmu/s - t - (t/s) ds
 // The wave mechanics are hsd_wreg_kernel's (ipm_wreg_hsd.inc): one loop around the ONE copy of the block substitution (pass 0
 // solves for p, pass 1 for q and combines them through dtau, later passes refine A dx - b dtau = eta rho in x-space),
-// factor<true> with the floor vector pivot_floor^2 |M_jj|, tau and kappa wave-uniform through uni(); the per-column phases with
-// t, s and u are ipm_wreg_bounded.inc's, and so is the LDS plan (wreg_plan_create_bounded: t at W0[TS, TS + NP), s behind it).
+// factor<true> with the floor vector pivot_floor^2 |M_jj|, tau and kappa wave-uniform through uni(); the LDS plan is
+// ipm_wreg_bounded_kernel's (wreg_plan_create_bounded: t at W0[TS, TS + NP), s behind it).  What this text has in common with
+// either of the two is written once, in wreg_wave.h:
+//   with ipm_wreg_bounded.inc   col_class, WReg::pt / ps, bounded_scales, WREG_BOUNDED_STORE, WREG_BOUNDED_ADVANCE
+//   with ipm_wreg_hsd.inc       WREG_HSD_RAYS / WREG_HSD_VERDICT (the stop verdict; forced and the loop bound go in front of it),
+//                               hsd_hand_over_p, WREG_HSD_DY, WREG_HSD_REFINE_TAIL, hsd_dkappa, hsd_ratio0
+// The per-column arithmetic (d, r0, h, w, the two dt / ds branches), the start point and the control flow are this kernel's own.
 // What waits where, per wave:
 //   x, z      px(), pz() across the factorisation, the passes and the loop's back edge (registers across gram(), which stages
 //             through the whole stage on term tables)
-//   t, s      W0[TS ..), W0[TS + NP ..): written by the start and by the step only
+//   t, s      pt(), ps() (W0[TS ..), W0[TS + NP ..)): written by the start and by the step only
 //   sigma     stage_()[0, NP) from the factorisation to pass 1, which forms r0 again from it and the parked x, z (the same
 //             expression as in front of the factorisation: the same bits); behind pass 1 the place is vx, the staging of A dx
 //   vd_()     d for Arow<true> and gram(); A'p from pass 0 to pass 1; from pass 1 on g = eta sigma + c dtau - A'dy, which every
@@ -43,7 +48,7 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
                             double* __restrict__ dobj, int* __restrict__ status, int* __restrict__ iters,
                             int* __restrict__ queue, DevOpts o) {
     using G = WGeo<MB>;
-    constexpr int MR = G::MR, MP = G::MP, NP = 64 * NQ, TS = G::WAVE_D(NQ);   // t at W0[TS, TS + NP), s behind it
+    constexpr int MR = G::MR, MP = G::MP, TS = G::WAVE_D(NQ);   // t at W0[TS, TS + NP), s behind it
     extern __shared__ __attribute__((aligned(16))) unsigned char lraw[];
     WReg<MB, NQ, DA> w;
     USE_AGPR_FORM();
@@ -64,25 +69,9 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
     while (lp < B) {
         // padded positions read u = 0 (buffer offset past the row): they take no part, like a fixed column
         const __amdgpu_buffer_rsrc_t rc = row_rsrc(cg + lp * n, n), ru = row_rsrc(ug + lp * n, n);
-        // PYCLLP_FLAG_AUTOSCALE: b, u / max|b| and c / max|c| over the columns that take part, exactly as ipm_wreg_bounded_kernel
-        double sb = 1.0, sc = 1.0;
-        if (autoscale) {
-            double cm = 0.0, bm = 0.0, ca = 0.0, um = 0.0;
-#pragma unroll
-            for (int qq = 0; qq < NQ; qq++) {
-                const unsigned jo = w.coff(qq);
-                const double uj = buf_ld(ru, jo), cj = buf_ld(rc, jo);
-                cm = fmax(cm, uj > 0.0 ? fabs(cj) : 0.0);
-                ca = fmax(ca, fabs(cj));
-                um = fmax(um, (uj > 0.0 && uj < HUGE_VAL) ? uj : 0.0);
-            }
-#pragma unroll
-            for (int r2 = 0; r2 < MR; r2++) bm = fmax(bm, okr[r2] ? fabs(bg[lp * m + lane + 64 * r2]) : 0.0);
-            sb = wmax(bm); sc = wmax(cm);
-            const bool scaled = autoscale_lp(o.flags, sb, wmax(ca), wmax(um));
-            // (an Inf in b is no scale factor: see ipm_wreg_bounded_kernel)
-            sb = uni((scaled && sb > 0.0 && sb < HUGE_VAL) ? sb : 1.0); sc = uni((scaled && sc > 0.0) ? sc : 1.0);
-        }
+        // PYCLLP_FLAG_AUTOSCALE: b, u / sb and c / sc (else both are 1)
+        const LpScales sf = bounded_scales(w, okr, lp, bg, rc, ru, o.flags);
+        const double sb = sf.sb, sc = sf.sc;
         // ---- start: x = z = 1 (act), t = s = 1 (bnd), y = 0, tau = kappa = 1; norms for the tolerances ----
         double c2 = 0.0, bu2 = 0.0, cnt = 0.0;
 #pragma unroll
@@ -90,14 +79,14 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
             const unsigned jo = w.coff(qq);
             double cj = buf_ld(rc, jo), uj = buf_ld(ru, jo);
             if (autoscale) { cj = cj / sc; uj = uj / sb; }
-            const bool a = uj > 0.0, bq = a && uj < HUGE_VAL;
+            const auto [a, bq] = col_class(uj);
             c2 += a ? cj * cj : 0.0;
             bu2 += bq ? uj * uj : 0.0;
             cnt += (a ? 1.0 : 0.0) + (bq ? 1.0 : 0.0);
             w.px(qq) = 1.0;
             w.pz(qq) = 1.0;
-            w.W0[TS + lane + 64 * qq] = 1.0;
-            w.W0[TS + NP + lane + 64 * qq] = 1.0;
+            w.pt(TS, qq) = 1.0;
+            w.ps(TS, qq) = 1.0;
         }
 #pragma unroll
         for (int r2 = 0; r2 < MR; r2++) {
@@ -127,8 +116,8 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
                 if (autoscale) { cq[qq] = cq[qq] / sc; uq[qq] = uq[qq] / sb; }
                 x[qq] = w.px(qq);
                 z[qq] = w.pz(qq);
-                const bool a = uq[qq] > 0.0, bq = a && uq[qq] < HUGE_VAL;
-                const double tq = w.W0[TS + j], sq = w.W0[TS + NP + j];
+                const auto [a, bq] = col_class(uq[qq]);
+                const double tq = w.pt(TS, qq), sq = w.ps(TS, qq);
                 const double sgq = a ? fma(cq[qq], tau, z[qq] - v[qq]) - (bq ? sq : 0.0) : 0.0;
                 const double om = bq ? fma(uq[qq], tau, -x[qq]) - tq : 0.0;
                 sgm[qq] = sgq;
@@ -160,46 +149,16 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
             // ---- stop tests (oracle hsd_one_raw on the expansion): the loop bound, NUMERICAL, OPTIMAL, a primal / dual ray ----
             int stat = PYCLLP_STATUS_ITERATION_LIMIT;
             {
-                const bool p_ray = po > 0.0 && fma(nbn, tau, normr) <= BH_EINF * po;
-                const bool d_ray = du < 0.0 && fma(ncn, tau, norms) <= BH_EINF * -du;
+                WREG_HSD_RAYS(BH_EINF)
                 if (forced >= 0) { stat = forced; running = false; }
                 else if (it >= o.max_iter) running = false;
-                else if (!(isfinite(normr) && isfinite(norms) && isfinite(gam) && isfinite(tau) && isfinite(kap))) { stat = PYCLLP_STATUS_NUMERICAL; running = false; }
-                else if (normr <= o.eps * (1.0 + nbn) * tau && norms <= o.eps * (1.0 + ncn) * tau && gam <= o.eps * tau * (tau + fabs(po))) {
-                    stat = PYCLLP_STATUS_OPTIMAL; running = false;
-                } else if (p_ray || d_ray) {
-                    stat = (p_ray && d_ray) ? ((-du > po) ? PYCLLP_STATUS_PRIMAL_INFEASIBLE : PYCLLP_STATUS_DUAL_INFEASIBLE)
-                                            : (p_ray ? PYCLLP_STATUS_DUAL_INFEASIBLE : PYCLLP_STATUS_PRIMAL_INFEASIBLE);
-                    running = false;
-                }
+                else WREG_HSD_VERDICT(o.eps * (1.0 + nbn), o.eps * (1.0 + ncn))
             }
             if (!running) {
-                // ---- store the LP (padded positions and null z / s: dropped by the buffer descriptors) ----
+                // ---- store the LP; the reduced cost of a fixed column is c tau - A'y ----
                 // optimal (and iteration-limit) points leave the homogeneous scaling; certificates stay
                 const double rt = (stat == PYCLLP_STATUS_OPTIMAL || stat == PYCLLP_STATUS_ITERATION_LIMIT) ? 1.0 / tau : 1.0;
-                const __amdgpu_buffer_rsrc_t rx = row_rsrc(xg + lp * n, n), rz = row_rsrc(zg ? zg + lp * n : nullptr, n),
-                                             rs = row_rsrc(sg ? sg + lp * n : nullptr, n);
-#pragma unroll
-                for (int qq = 0; qq < NQ; qq++) {
-                    const unsigned jo = w.coff(qq);
-                    const bool a = uq[qq] > 0.0, bq = a && uq[qq] < HUGE_VAL;
-                    const double r = fma(cq[qq], tau, -v[qq]);          // reduced cost of a fixed column
-                    const double sq = w.W0[TS + NP + lane + 64 * qq];
-                    buf_st(rx, jo, a ? x[qq] * rt * sb : 0.0);
-                    buf_st(rz, jo, (a ? z[qq] : fmax(-r, 0.0)) * rt * sc);
-                    buf_st(rs, jo, (bq ? sq : (a ? 0.0 : fmax(r, 0.0))) * rt * sc);
-                }
-#pragma unroll
-                for (int r2 = 0; r2 < MR; r2++) {
-                    const int i = lane + 64 * r2;
-                    if (yg && okr[r2]) yg[lp * m + i] = w.ys_()[i] * rt * sc;
-                }
-                if (lane == 0) {
-                    if (pobj) pobj[lp] = po * rt * (sb * sc);
-                    if (dobj) dobj[lp] = du * rt * (sb * sc);
-                    status[lp] = stat;
-                    if (iters) iters[lp] = it;
-                }
+                WREG_BOUNDED_STORE(rt, fma(cq[qq], tau, -v[qq]))
                 break;
             }
             const double dmu = uni(o.delta * ((gam + tau * kap) / ncomp));
@@ -210,8 +169,8 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
 #pragma unroll
             for (int qq = 0; qq < NQ; qq++) {
                 const int j = lane + 64 * qq;
-                const bool a = uq[qq] > 0.0, bq = a && uq[qq] < HUGE_VAL;
-                const double tq = w.W0[TS + j], sq = w.W0[TS + NP + j];
+                const auto [a, bq] = col_class(uq[qq]);
+                const double tq = w.pt(TS, qq), sq = w.ps(TS, qq);
                 const double dq = w.vd_()[j];
                 const double wq = dq * (bq ? sq * fast_rcp(tq) : 0.0);
                 const double om = bq ? fma(uq[qq], tau, -x[qq]) - tq : 0.0;
@@ -284,12 +243,7 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
 #pragma unroll
                     for (int qq = 0; qq < NQ; qq++) w.vd_()[lane + 64 * qq] = w2[qq];
                     wave_lds_sync();
-#pragma unroll
-                    for (int r2 = 0; r2 < MR; r2++) {
-                        const int i = lane + 64 * r2;
-                        if (i < MP) { pv[i] = w.um_()[i]; w.um_()[i] = rq[r2]; }
-                    }
-                    wave_lds_sync();
+                    hsd_hand_over_p(w, rq);
                 } else {
                     if (autoscale) {
 #pragma unroll
@@ -305,8 +259,8 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
 #pragma unroll
                         for (int qq = 0; qq < NQ; qq++) {
                             const int j = lane + 64 * qq;
-                            const bool a = u2q[qq] > 0.0, bq = a && u2q[qq] < HUGE_VAL;
-                            const double xq = w.px(qq), zq = w.pz(qq), tq = w.W0[TS + j], sq = w.W0[TS + NP + j];
+                            const auto [a, bq] = col_class(u2q[qq]);
+                            const double xq = w.px(qq), zq = w.pz(qq), tq = w.pt(TS, qq), sq = w.ps(TS, qq);
                             const double sgq = w.stage_()[j], ap = w.vd_()[j];
                             const double rx = fast_rcp(xq);
                             const double zxq = zq * rx;
@@ -334,17 +288,11 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
                         const double den = wsum(dsum) + kap / tau;
                         const double num = fma(BH_ETA, phi, dmu / tau - kap) + wsum(bqs) - wsum(nsum);
                         dtau = uni(num / den);
-#pragma unroll
-                        for (int r2 = 0; r2 < MR; r2++) {
-                            const int i = lane + 64 * r2;
-                            dy[r2] = (i < MP) ? fma(pv[i], dtau, w.um_()[i]) : 0.0;
-                            rhot[r2] = okr[r2] ? fma(w.bs_()[i], dtau, BH_ETA * rho[r2]) : 0.0;   // A dx - b dtau = eta rho
-                            bad = bad | !isfinite(dy[r2]);
-                        }
+                        WREG_HSD_DY(BH_ETA)
 #pragma unroll
                         for (int qq = 0; qq < NQ; qq++) {
                             const int j = lane + 64 * qq;
-                            const bool a = u2q[qq] > 0.0;
+                            const bool a = col_class(u2q[qq]).a;
                             dx[qq] = fma(uu[qq], dtau, dx[qq]);                                   // dx = uu dtau + v
                             const double wv = fma(w.vd_()[j], dtau, w2[qq]);                      // A'dy = A'p dtau + A'q
                             w.vd_()[j] = a ? fma(BH_ETA, w.stage_()[j], fma(c2q[qq], dtau, -wv)) : 0.0;   // g = eta sigma + c dtau - A'dy
@@ -354,8 +302,8 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
 #pragma unroll
                         for (int qq = 0; qq < NQ; qq++) {
                             const int j = lane + 64 * qq;
-                            const bool a = u2q[qq] > 0.0, bq = a && u2q[qq] < HUGE_VAL;
-                            const double tq = w.W0[TS + j], sq = w.W0[TS + NP + j];
+                            const auto [a, bq] = col_class(u2q[qq]);
+                            const double tq = w.pt(TS, qq), sq = w.ps(TS, qq);
                             const double stq = bq ? sq * fast_rcp(tq) : 0.0;
                             const double dq = a ? fast_rcp(fma(w.pz(qq), fast_rcp(w.px(qq)), stq)) : 0.0;
                             dx[qq] = fma(dq, w2[qq], dx[qq]);
@@ -364,40 +312,22 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
 #pragma unroll
                         for (int r2 = 0; r2 < MR; r2++) dy[r2] -= (lane + 64 * r2 < MP) ? w.um_()[lane + 64 * r2] : 0.0;
                     }
-                    wave_lds_sync();
-#pragma unroll
-                    for (int qq = 0; qq < NQ; qq++) vx[lane + 64 * qq] = (u2q[qq] > 0.0) ? dx[qq] : 0.0;
-                    wave_lds_sync();
-                    double Adx[MR], e[MR], dm[MR], me = 0.0;
-                    w.template Arow<false>(vx, Adx, dm);
-#pragma unroll
-                    for (int r2 = 0; r2 < MR; r2++) {
-                        e[r2] = okr[r2] ? rhot[r2] - Adx[r2] : 0.0;
-                        me = fmax(me, fabs(e[r2]));
-                    }
-                    const double maxe = wmax(me);
-                    STAMP(8)
-                    if (!(maxe > etol_it) || pass - 1 >= o.max_refine) more = false;
-                    else {
-#pragma unroll
-                        for (int r2 = 0; r2 < MR; r2++) if (lane + 64 * r2 < MP) w.um_()[lane + 64 * r2] = e[r2];
-                        wave_lds_sync();
-                    }
+                    WREG_HSD_REFINE_TAIL(col_class(u2q[qq]).a)
                 }
                 if (!more) break;
                 pass++;
             }
             if (__any(bad) || !isfinite(dtau)) { forced = PYCLLP_STATUS_NUMERICAL; continue; }
             // ---- step: ratio test over x, z, t, s, tau, kappa; the two branches for dt, ds switched at t < s ----
-            const double dkap = dmu / tau - kap - kap / tau * dtau;
-            double dz[NQ], dt[NQ], ds[NQ], th = fmax(fmax(-dtau / tau, -dkap / kap), 0.0);
+            const double dkap = hsd_dkappa(dmu, tau, kap, dtau);
+            double dz[NQ], dt[NQ], ds[NQ], th = hsd_ratio0(tau, kap, dtau, dkap);
 #pragma unroll
             for (int qq = 0; qq < NQ; qq++) {
                 const int j = lane + 64 * qq;
                 double uj = buf_ld(ru, w.coff(qq));
                 if (autoscale) uj = uj / sb;
-                const bool a = uj > 0.0, bq = a && uj < HUGE_VAL;
-                const double xq = w.px(qq), zq = w.pz(qq), tq = w.W0[TS + j], sq = w.W0[TS + NP + j];
+                const auto [a, bq] = col_class(uj);
+                const double xq = w.px(qq), zq = w.pz(qq), tq = w.pt(TS, qq), sq = w.ps(TS, qq);
                 const double rx = fast_rcp(xq), rz = fast_rcp(zq), rt = fast_rcp(tq), rs = fast_rcp(sq);
                 const double om = bq ? fma(uj, tau, -xq) - tq : 0.0;
                 dx[qq] = a ? dx[qq] : 0.0;
@@ -416,20 +346,7 @@ ipm_wreg_bounded_hsd_kernel(WregTab T, long B, const double* __restrict__ bg, co
             th = wmax(th);
             const double theta = uni(fmin(o.r / th, 1.0));
             wave_lds_sync();
-#pragma unroll
-            for (int r2 = 0; r2 < MR; r2++) {
-                const int i = lane + 64 * r2;
-                if (i < MP) w.ys_()[i] = fma(theta, dy[r2], w.ys_()[i]);
-            }
-#pragma unroll
-            for (int qq = 0; qq < NQ; qq++) {
-                // (dx, dz are 0 where the column takes no part, dt, ds where it has no bound: those values stay)
-                const int j = lane + 64 * qq;
-                w.px(qq) = fma(theta, dx[qq], w.px(qq));
-                w.pz(qq) = fma(theta, dz[qq], w.pz(qq));
-                w.W0[TS + j] = fma(theta, dt[qq], w.W0[TS + j]);
-                w.W0[TS + NP + j] = fma(theta, ds[qq], w.W0[TS + NP + j]);
-            }
+            WREG_BOUNDED_ADVANCE()
             tau = uni(fma(theta, dtau, tau)); kap = uni(fma(theta, dkap, kap));
             wave_lds_sync();
             it++;

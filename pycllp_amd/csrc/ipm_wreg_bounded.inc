@@ -19,6 +19,9 @@
 //   * a verdict reached inside an iteration (NUMERICAL, ITERATION_LIMIT) is stored at the top of the next pass, where the
 //     point's A'y is at hand for the duals of the fixed columns; the point itself is the one the verdict was reached on.
 // No warm start, no predictor-corrector, no HSD.
+// Written once in wreg_wave.h, for this text and ipm_wreg_bdhsd.inc: the class of a column (col_class), the places of t and s
+// (WReg::pt, ps), the per-LP scale factors (bounded_scales), the store of a finished LP (WREG_BOUNDED_STORE) and the tail of the
+// step (WREG_BOUNDED_ADVANCE).
 // The text serves three units: ipm_wreg_bd.hip (ipm_wreg_bounded_kernel, a shared A), ipm_wreg_bdpa.hip
 // (ipm_wreg_bounded_pa_kernel, per-problem values of A on structure tables; DESIGN.md section 18) and ipm_wreg_bddapa.hip
 // (ipm_wreg_bounded_dapa_kernel, per-problem dense matrices, an image per wave; DESIGN.md section 25).
@@ -45,7 +48,7 @@ ipm_wreg_bounded_dapa_kernel(WregTab T, long B, const double* __restrict__ ag, c
                              double* __restrict__ dobj, int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue,
                              DevOpts o) {
     using G = WGeo<MB>;
-    constexpr int MR = G::MR, MP = G::MP, NP = 64 * NQ;
+    constexpr int MR = G::MR, MP = G::MP;
     const int TS = G::WAVE_D(NQ) + T.img_rows * T.as;                         // t at W0[TS, TS + NP), s behind it
     extern __shared__ __attribute__((aligned(16))) unsigned char lraw[];
     WReg<MB, NQ, true, true> w;
@@ -58,7 +61,7 @@ ipm_wreg_bounded_pa_kernel(WregTab T, long B, const double* __restrict__ ag, con
                            double* __restrict__ dobj, int* __restrict__ status, int* __restrict__ iters, int* __restrict__ queue,
                            DevOpts o) {
     using G = WGeo<MB>;
-    constexpr int MR = G::MR, MP = G::MP, NP = 64 * NQ;
+    constexpr int MR = G::MR, MP = G::MP;
     const int TS = G::WAVE_D(NQ) + T.nnzp;                                    // t at W0[TS, TS + NP), s behind it
     extern __shared__ __attribute__((aligned(16))) unsigned char lraw[];
     WReg<MB, NQ, false, true> w;
@@ -70,7 +73,7 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
                         double* __restrict__ sg, double* __restrict__ pobj, double* __restrict__ dobj, int* __restrict__ status,
                         int* __restrict__ iters, int* __restrict__ queue, DevOpts o) {
     using G = WGeo<MB>;
-    constexpr int MR = G::MR, MP = G::MP, NP = 64 * NQ, TS = G::WAVE_D(NQ);   // t at W0[TS, TS + NP), s behind it
+    constexpr int MR = G::MR, MP = G::MP, TS = G::WAVE_D(NQ);   // t at W0[TS, TS + NP), s behind it
     extern __shared__ __attribute__((aligned(16))) unsigned char lraw[];
     WReg<MB, NQ, DA> w;
 #endif
@@ -91,27 +94,9 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
 #endif
         // padded positions read u = 0 (buffer offset past the row): they take no part, like a fixed column
         const __amdgpu_buffer_rsrc_t rc = row_rsrc(cg + lp * n, n), ru = row_rsrc(ug + lp * n, n);
-        // PYCLLP_FLAG_AUTOSCALE: b, u / max|b| and c / max|c| over the columns that take part (as the lane-group kernel)
-        double sb = 1.0, sc = 1.0;
-        if (autoscale) {
-            // (the per-LP verdict, autoscale_lp, looks at max|c| over ALL columns and at the largest finite positive u)
-            double cm = 0.0, bm = 0.0, ca = 0.0, um = 0.0;
-#pragma unroll
-            for (int qq = 0; qq < NQ; qq++) {
-                const unsigned jo = w.coff(qq);
-                const double uj = buf_ld(ru, jo), cj = buf_ld(rc, jo);
-                cm = fmax(cm, uj > 0.0 ? fabs(cj) : 0.0);
-                ca = fmax(ca, fabs(cj));
-                um = fmax(um, (uj > 0.0 && uj < HUGE_VAL) ? uj : 0.0);
-            }
-#pragma unroll
-            for (int r2 = 0; r2 < MR; r2++) bm = fmax(bm, okr[r2] ? fabs(bg[lp * m + lane + 64 * r2]) : 0.0);
-            sb = wmax(bm); sc = wmax(cm);
-            const bool scaled = autoscale_lp(o.flags, sb, wmax(ca), wmax(um));
-            // (sb = inf -- an Inf in b: the LP ends NUMERICAL at iteration 0 either way -- is no scale factor: u / inf = 0 would turn
-            // every column into a fixed one, at the store too, where y, z and s depend on which columns take part)
-            sb = uni((scaled && sb > 0.0 && sb < HUGE_VAL) ? sb : 1.0); sc = uni((scaled && sc > 0.0) ? sc : 1.0);
-        }
+        // PYCLLP_FLAG_AUTOSCALE: b, u / sb and c / sc (else both are 1)
+        const LpScales sf = bounded_scales(w, okr, lp, bg, rc, ru, o.flags);
+        const double sb = sf.sb, sc = sf.sc;
         // ---- start: z = s = y = 1, x = min(1, u/2), t = u - x (tau = 0); norms for the tolerances ----
         double c2 = 0.0, u2 = 0.0, nbc = 0.0;
 #pragma unroll
@@ -119,15 +104,15 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
             const unsigned jo = w.coff(qq);
             double cj = buf_ld(rc, jo), uj = buf_ld(ru, jo);
             if (autoscale) { cj = cj / sc; uj = uj / sb; }
-            const bool a = uj > 0.0, bq = a && uj < HUGE_VAL;
+            const auto [a, bq] = col_class(uj);
             c2 += a ? cj * cj : 0.0;
             u2 += bq ? uj * uj : 0.0;
             nbc += bq ? 1.0 : 0.0;
             const double xq = bq ? fmin(1.0, 0.5 * uj) : 1.0;
             w.px(qq) = xq;
             w.pz(qq) = 1.0;
-            w.W0[TS + lane + 64 * qq] = bq ? uj - xq : 1.0;
-            w.W0[TS + NP + lane + 64 * qq] = 1.0;
+            w.pt(TS, qq) = bq ? uj - xq : 1.0;
+            w.ps(TS, qq) = 1.0;
         }
         double b2 = 0.0;
 #pragma unroll
@@ -157,7 +142,7 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
                 if (autoscale) { cq[qq] = cq[qq] / sc; uq[qq] = uq[qq] / sb; }
                 x[qq] = w.px(qq);
                 z[qq] = w.pz(qq);
-                vx[lane + 64 * qq] = (uq[qq] > 0.0) ? x[qq] : 0.0;
+                vx[lane + 64 * qq] = col_class(uq[qq]).a ? x[qq] : 0.0;
             }
             wave_lds_sync();
             {
@@ -170,8 +155,8 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
             double s2 = 0.0, gam = 0.0, tau2 = 0.0, pp = 0.0, dd = 0.0, r2s = 0.0;
 #pragma unroll
             for (int qq = 0; qq < NQ; qq++) {
-                const bool a = uq[qq] > 0.0, bq = a && uq[qq] < HUGE_VAL;
-                const double tq = w.W0[TS + lane + 64 * qq], sq = w.W0[TS + NP + lane + 64 * qq];
+                const auto [a, bq] = col_class(uq[qq]);
+                const double tq = w.pt(TS, qq), sq = w.ps(TS, qq);
                 const double sgq = a ? (cq[qq] - v[qq]) + z[qq] - (bq ? sq : 0.0) : 0.0;
                 const double tau = bq ? (uq[qq] - x[qq]) - tq : 0.0;
                 s2 = fma(sgq, sgq, s2);
@@ -199,38 +184,16 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
             else if (normr > 10.0 * normr0 && normr > PYCLLP_GROWTH_FLOOR * tol_r) { stat = PYCLLP_STATUS_PRIMAL_INFEASIBLE; running = false; }
             else if (norms > 10.0 * norms0 && norms > PYCLLP_GROWTH_FLOOR * tol_s) { stat = PYCLLP_STATUS_DUAL_INFEASIBLE; running = false; }
             if (!running) {
-                // ---- store the LP (padded positions and null z / s: dropped by the buffer descriptors) ----
-                const __amdgpu_buffer_rsrc_t rx = row_rsrc(xg + lp * n, n), rz = row_rsrc(zg ? zg + lp * n : nullptr, n),
-                                             rs = row_rsrc(sg ? sg + lp * n : nullptr, n);
-#pragma unroll
-                for (int qq = 0; qq < NQ; qq++) {
-                    const unsigned jo = w.coff(qq);
-                    const bool a = uq[qq] > 0.0, bq = a && uq[qq] < HUGE_VAL;
-                    const double r = cq[qq] - v[qq];          // reduced cost of a fixed column
-                    const double sq = w.W0[TS + NP + lane + 64 * qq];
-                    buf_st(rx, jo, a ? x[qq] * sb : 0.0);
-                    buf_st(rz, jo, (a ? z[qq] : fmax(-r, 0.0)) * sc);
-                    buf_st(rs, jo, (bq ? sq : (a ? 0.0 : fmax(r, 0.0))) * sc);
-                }
-#pragma unroll
-                for (int r2 = 0; r2 < MR; r2++) {
-                    const int i = lane + 64 * r2;
-                    if (yg && okr[r2]) yg[lp * m + i] = w.ys_()[i] * sc;
-                }
-                if (lane == 0) {
-                    if (pobj) pobj[lp] = po * (sb * sc);
-                    if (dobj) dobj[lp] = du * (sb * sc);
-                    status[lp] = stat;
-                    if (iters) iters[lp] = it;
-                }
+                // ---- store the LP; the reduced cost of a fixed column is c - A'y ----
+                WREG_BOUNDED_STORE(1.0, cq[qq] - v[qq])
                 break;
             }
             // ---- d = 1 / (z/x + s/t), t~ = c - A'y + mu/x - mu/t + (s/t) tau; rhs = A (d t~) - rho, diag(M) ----
             double tt[NQ];
 #pragma unroll
             for (int qq = 0; qq < NQ; qq++) {
-                const bool a = uq[qq] > 0.0, bq = a && uq[qq] < HUGE_VAL;
-                const double tq = w.W0[TS + lane + 64 * qq], sq = w.W0[TS + NP + lane + 64 * qq];
+                const auto [a, bq] = col_class(uq[qq]);
+                const double tq = w.pt(TS, qq), sq = w.ps(TS, qq);
                 const double rx = fast_rcp(x[qq]), rt = fast_rcp(tq);
                 const double tau = (uq[qq] - x[qq]) - tq;
                 double dq, tn;
@@ -285,9 +248,9 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
                 const unsigned jo = w.coff(qq);
                 double uj = buf_ld(ru, jo);
                 if (autoscale) uj = uj / sb;
-                const bool a = uj > 0.0, bq = a && uj < HUGE_VAL;
+                const auto [a, bq] = col_class(uj);
                 const double xq = w.px(qq), zq = w.pz(qq);
-                const double tq = w.W0[TS + lane + 64 * qq], sq = w.W0[TS + NP + lane + 64 * qq];
+                const double tq = w.pt(TS, qq), sq = w.ps(TS, qq);
                 const double rx = fast_rcp(xq), rz = fast_rcp(zq), rt = fast_rcp(tq);
                 const double tau = (uj - xq) - tq;
                 dz[qq] = a ? (mu - zq * dx[qq]) * rx - zq : 0.0;
@@ -299,19 +262,7 @@ ipm_wreg_bounded_kernel(WregTab T, long B, const double* __restrict__ bg, const 
             th = wmax(th);
             const double theta = uni(fmin(o.r / th, 1.0));
             wave_lds_sync();
-#pragma unroll
-            for (int r2 = 0; r2 < MR; r2++) {
-                const int i = lane + 64 * r2;
-                if (i < MP) w.ys_()[i] = fma(theta, dy[r2], w.ys_()[i]);
-            }
-#pragma unroll
-            for (int qq = 0; qq < NQ; qq++) {
-                // (dx, dz are 0 where the column takes no part, dt, ds where it has no bound: those values stay)
-                w.px(qq) = fma(theta, dx[qq], w.px(qq));
-                w.pz(qq) = fma(theta, dz[qq], w.pz(qq));
-                w.W0[TS + lane + 64 * qq] = fma(theta, dt[qq], w.W0[TS + lane + 64 * qq]);
-                w.W0[TS + NP + lane + 64 * qq] = fma(theta, ds[qq], w.W0[TS + NP + lane + 64 * qq]);
-            }
+            WREG_BOUNDED_ADVANCE()
             normr0 = normr; norms0 = norms;
             wave_lds_sync();
             it++;

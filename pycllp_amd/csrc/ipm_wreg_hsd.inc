@@ -5,6 +5,10 @@ namespace {
 // the same solve on the homogeneous self-dual embedding (PYCLLP_FLAG_HSD; oracle hsd_one_raw, ipm_block_kernel's run-time
 // branch, csrc/ipm_group_hsd.inc): tau and kappa are wave-uniform scalars, one factorisation serves the two right-hand
 // sides  M p = A(d c) - b  and  M q = A(d r1) - eta rho, the pivot floor of column j is pivot_floor^2 |M_jj|
+// Written once in wreg_wave.h, for this kernel and ipm_wreg_bounded_hsd_kernel (ipm_wreg_bdhsd.inc): the stop verdict
+// (WREG_HSD_RAYS, WREG_HSD_VERDICT), pass 0's hand-over (hsd_hand_over_p), dy and the refinement's right-hand side behind dtau
+// (WREG_HSD_DY), the tail of a refinement pass (WREG_HSD_REFINE_TAIL), dkappa and the start of the ratio test (hsd_dkappa,
+// hsd_ratio0); the LP's load and store (load_lp, store_lp) are shared with ipm_wreg_kernel.
 // ------------------------------------------------------------------------------------------------------------------
 template <int MB, int NQ, bool DA, bool PA>
 __global__ void __launch_bounds__(256, 1)
@@ -101,15 +105,8 @@ hsd_wreg_kernel(WregTab T, long B, const double* __restrict__ ag, const double* 
             }
             const double normr = uni(sqrt(wsum(r2s)));
             // ---- stop tests (oracle hsd_one_raw): optimal, or a primal / dual ray ----
-            const bool p_ray = po > 0.0 && fma(nbn, tau, normr) <= einf * po;
-            const bool d_ray = du < 0.0 && fma(ncn, tau, norms) <= einf * -du;
-            if (!(isfinite(normr) && isfinite(norms) && isfinite(gam) && isfinite(tau) && isfinite(kap))) { stat = PYCLLP_STATUS_NUMERICAL; running = false; }
-            else if (normr <= tol_r * tau && norms <= tol_s * tau && gam <= o.eps * tau * (tau + fabs(po))) { stat = PYCLLP_STATUS_OPTIMAL; running = false; }
-            else if (p_ray || d_ray) {
-                stat = (p_ray && d_ray) ? ((-du > po) ? PYCLLP_STATUS_PRIMAL_INFEASIBLE : PYCLLP_STATUS_DUAL_INFEASIBLE)
-                                        : (p_ray ? PYCLLP_STATUS_DUAL_INFEASIBLE : PYCLLP_STATUS_PRIMAL_INFEASIBLE);
-                running = false;
-            }
+            WREG_HSD_RAYS(einf)
+            WREG_HSD_VERDICT(tol_r, tol_s)
             if (running) {
                 // ---- A(d r1), diag(M), A(d c) ----
                 wave_lds_sync();
@@ -180,12 +177,7 @@ hsd_wreg_kernel(WregTab T, long B, const double* __restrict__ ag, const double* 
 #pragma unroll
                             for (int qq = 0; qq < NQ; qq++) w.vd_()[lane + 64 * qq] = c2q[qq] - w2[qq];
                             wave_lds_sync();
-#pragma unroll
-                            for (int r2 = 0; r2 < MR; r2++) {
-                                const int i = lane + 64 * r2;
-                                if (i < MP) { pv[i] = w.um_()[i]; w.um_()[i] = rq[r2]; }
-                            }
-                            wave_lds_sync();
+                            hsd_hand_over_p(w, rq);
                         } else {
                             if (pass == 1) {
                                 double dsum = 0.0, nsum = 0.0, bq = 0.0;
@@ -206,13 +198,7 @@ hsd_wreg_kernel(WregTab T, long B, const double* __restrict__ ag, const double* 
                                 const double den = wsum(dsum) + kap / tau;
                                 const double num = fma(eta, phi, mu / tau - kap) + wsum(bq) - wsum(nsum);
                                 dtau = uni(num / den);
-#pragma unroll
-                                for (int r2 = 0; r2 < MR; r2++) {
-                                    const int i = lane + 64 * r2;
-                                    dy[r2] = (i < MP) ? fma(pv[i], dtau, w.um_()[i]) : 0.0;
-                                    rhot[r2] = okr[r2] ? fma(w.bs_()[i], dtau, eta * rho[r2]) : 0.0;   // A dx - b dtau = eta rho
-                                    bad = bad | !isfinite(dy[r2]);
-                                }
+                                WREG_HSD_DY(eta)
 #pragma unroll
                                 for (int qq = 0; qq < NQ; qq++) dx[qq] = fma(d[qq] * u[qq], dtau, dx[qq]);   // dx = u dtau + v, u = d (c - A'p)
                                 etol_it = uni(o.refine_tol * (1.0 + nbn) * fmax(tau, kap));
@@ -222,25 +208,7 @@ hsd_wreg_kernel(WregTab T, long B, const double* __restrict__ ag, const double* 
 #pragma unroll
                                 for (int r2 = 0; r2 < MR; r2++) dy[r2] -= (lane + 64 * r2 < MP) ? w.um_()[lane + 64 * r2] : 0.0;
                             }
-                            wave_lds_sync();
-#pragma unroll
-                            for (int qq = 0; qq < NQ; qq++) vx[lane + 64 * qq] = okc[qq] ? dx[qq] : 0.0;
-                            wave_lds_sync();
-                            double Adx[MR], e[MR], dm[MR], me = 0.0;
-                            w.template Arow<false>(vx, Adx, dm);
-#pragma unroll
-                            for (int r2 = 0; r2 < MR; r2++) {
-                                e[r2] = okr[r2] ? rhot[r2] - Adx[r2] : 0.0;
-                                me = fmax(me, fabs(e[r2]));
-                            }
-                            const double maxe = wmax(me);
-                            STAMP(8)
-                            if (!(maxe > etol_it) || pass - 1 >= o.max_refine) more = false;
-                            else {
-#pragma unroll
-                                for (int r2 = 0; r2 < MR; r2++) if (lane + 64 * r2 < MP) w.um_()[lane + 64 * r2] = e[r2];
-                                wave_lds_sync();
-                            }
+                            WREG_HSD_REFINE_TAIL(okc[qq])
                         }
                         if (!more) break;
                         pass++;
@@ -248,8 +216,8 @@ hsd_wreg_kernel(WregTab T, long B, const double* __restrict__ ag, const double* 
                     if (__any(bad) || !isfinite(dtau)) { stat = PYCLLP_STATUS_NUMERICAL; running = false; }
                     else {
                         // ---- step: ratio test over x, z, tau, kappa ----
-                        const double dkap = mu / tau - kap - kap / tau * dtau;
-                        double dz[NQ], xs[NQ], zs[NQ], th = fmax(fmax(-dtau / tau, -dkap / kap), 0.0);
+                        const double dkap = hsd_dkappa(mu, tau, kap, dtau);
+                        double dz[NQ], xs[NQ], zs[NQ], th = hsd_ratio0(tau, kap, dtau, dkap);
 #pragma unroll
                         for (int qq = 0; qq < NQ; qq++) {
                             xs[qq] = w.px(qq);

@@ -39,9 +39,11 @@
 // tools/wreg_sim.py is a lane-level numpy model of the layouts used below.
 //
 // This file is the per-wave machinery (WReg, the batched LDS reads, newton_solve), the phases the kernels share (next_item,
-// load_lp, store_lp), the launcher template and the launcher table macro.  The kernels
-// on top of it: ipm_wreg_solve.inc, ipm_wreg_hsd.inc, ipm_wreg_newton.inc, ipm_wreg_bounded.inc, compiled by the units
-// ipm_wreg_{tab,da,pa,dapa,pc,pcda,pcpa,bd}.hip (one launcher table of wreg.h each); ipm_wreg.hip is the host side.
+// load_lp, store_lp; the phases of the two kernels with upper bounds and of the two self-dual kernels behind them), the launcher
+// template and the launcher table macro.  The kernels
+// on top of it: ipm_wreg_solve.inc, ipm_wreg_hsd.inc, ipm_wreg_newton.inc, ipm_wreg_bounded.inc, ipm_wreg_bdhsd.inc, compiled by
+// the units ipm_wreg_{tab,da,pa,dapa,pc,pcda,pcpa,bd,bdpa,bddapa,bdh}.hip (one launcher table of wreg.h each); ipm_wreg.hip is
+// the host side.
 #ifndef PYCLLP_WREG_WAVE_H
 #define PYCLLP_WREG_WAVE_H
 #include "wreg.h"
@@ -268,6 +270,10 @@ struct WReg {
     // solve, and across the back edge of the iteration loop
     __device__ __forceinline__ double& px(int qq) const { return stage_()[NP + lane + 64 * qq]; }
     __device__ __forceinline__ double& pz(int qq) const { return stage_()[2 * NP + lane + 64 * qq]; }
+    // t and s of that column in the kernels for LPs with upper bounds: 2 NP doubles BEHIND the wave area, at W0[TS, TS + NP) and
+    // behind it (TS = WAVE_D, or the wave-uniform run-time offset behind the wave's values or image: ipm_wreg_bounded.inc)
+    __device__ __forceinline__ double& pt(int TS, int qq) const { return W0[TS + lane + 64 * qq]; }
+    __device__ __forceinline__ double& ps(int TS, int qq) const { return W0[TS + NP + lane + 64 * qq]; }
     // which of this lane's column positions and rows the LP has (the others are padding)
     __device__ __forceinline__ void masks(bool (&okc)[NQ], bool (&okr)[MR]) const {
 #pragma unroll
@@ -1234,6 +1240,175 @@ __device__ __forceinline__ void store_lp(const WReg<MB, NQ, DA, PA>& w, const bo
             if (iters) iters[lp] = it;
         }
     }
+}
+
+// ---- phases of the kernels for LPs with UPPER BOUNDS (ipm_wreg_bounded.inc, ipm_wreg_bdhsd.inc), written once -----------------
+// The class of a column by its (scaled) bound u: a -- it takes part (u > 0; a fixed column and a padded position have u = 0);
+// bq -- it has a bound as well (0 < u < inf), and with it a t and an s (WReg::pt, ps).
+struct ColClass { bool a, bq; };
+__device__ __forceinline__ ColClass col_class(double u) { const bool a = u > 0.0; return {a, a && u < HUGE_VAL}; }
+
+// PYCLLP_FLAG_AUTOSCALE: the LP is solved with b, u / sb and c / sc, sb = max|b|, sc = max|c| over the columns that take part
+// (as the lane-group kernel); the per-LP verdict, autoscale_lp, looks at max|c| over ALL columns and at the largest finite
+// positive u.  sb = inf -- an Inf in b: the LP ends NUMERICAL at iteration 0 either way -- is no scale factor: u / inf = 0 would
+// turn every column into a fixed one, at the store too, where y, z and s depend on which columns take part.
+// (No __restrict__ here: its scope, inlined, changes the schedule of the kernels around it.)
+struct LpScales { double sb, sc; };
+template <int MB, int NQ, bool DA, bool PA>
+__device__ __forceinline__ LpScales bounded_scales(const WReg<MB, NQ, DA, PA>& w, const bool (&okr)[WGeo<MB>::MR], long lp, const double* bg,
+                                                   __amdgpu_buffer_rsrc_t rc, __amdgpu_buffer_rsrc_t ru, int flags) {
+    constexpr int MR = WGeo<MB>::MR;
+    const int& lane = w.lane;
+    const int m = w.m;
+    double sb = 1.0, sc = 1.0;
+    if ((flags & PYCLLP_FLAG_AUTOSCALE) != 0) {
+        double cm = 0.0, bm = 0.0, ca = 0.0, um = 0.0;
+#pragma unroll
+        for (int qq = 0; qq < NQ; qq++) {
+            const unsigned jo = w.coff(qq);
+            const double uj = buf_ld(ru, jo), cj = buf_ld(rc, jo);
+            // (the two classes spelled out: through col_class the 57 kernels this is inlined into came out with another schedule)
+            cm = fmax(cm, uj > 0.0 ? fabs(cj) : 0.0);
+            ca = fmax(ca, fabs(cj));
+            um = fmax(um, (uj > 0.0 && uj < HUGE_VAL) ? uj : 0.0);
+        }
+#pragma unroll
+        for (int r2 = 0; r2 < MR; r2++) bm = fmax(bm, okr[r2] ? fabs(bg[lp * m + lane + 64 * r2]) : 0.0);
+        sb = wmax(bm); sc = wmax(cm);
+        const bool scaled = autoscale_lp(flags, sb, wmax(ca), wmax(um));
+        sb = uni((scaled && sb > 0.0 && sb < HUGE_VAL) ? sb : 1.0); sc = uni((scaled && sc > 0.0) ? sc : 1.0);
+    }
+    return {sb, sc};
+}
+
+// The two phases below are text in the kernel's own scope, not functions: as functions that take the kernels' N-vectors by
+// reference they changed the machine code of 37 and of all 41 plain bounded kernels (profiles/wave_shared_phases/README.md).
+//
+// End of one LP: x, z, s (padded positions and a null z / s: dropped by the buffer descriptors) and y leave with the scaling
+// undone and with the factor RT (1 / tau where the self-dual point leaves the homogeneous scaling, else the constant 1.0), then
+// objectives, status, iterations.  x, z are the point in registers, s is read where it waits; a fixed column ends at x = 0 with
+// z = max(-r, 0), s = max(r, 0), r = RCOST its reduced cost at the point, an expression in qq (c - A'y; on the embedding
+// c tau - A'y, on the same scaling).  Names of the scope: NQ, MR, lane, m, n, w, TS, okr, lp, x, z, uq, sb, sc, po, du, stat, it and
+// the kernel's output arrays.
+#define WREG_BOUNDED_STORE(RT, RCOST)                                                                                        \
+    {                                                                                                                        \
+        const __amdgpu_buffer_rsrc_t rx = row_rsrc(xg + lp * n, n), rz = row_rsrc(zg ? zg + lp * n : nullptr, n),            \
+                                     rs = row_rsrc(sg ? sg + lp * n : nullptr, n);                                           \
+        _Pragma("unroll")                                                                                                    \
+        for (int qq = 0; qq < NQ; qq++) {                                                                                    \
+            const unsigned jo = w.coff(qq);                                                                                  \
+            const auto [a, bq] = col_class(uq[qq]);                                                                          \
+            const double r = RCOST;                                                                                          \
+            const double sq = w.ps(TS, qq);                                                                                  \
+            buf_st(rx, jo, a ? x[qq] * (RT) * sb : 0.0);                                                                     \
+            buf_st(rz, jo, (a ? z[qq] : fmax(-r, 0.0)) * (RT) * sc);                                                         \
+            buf_st(rs, jo, (bq ? sq : (a ? 0.0 : fmax(r, 0.0))) * (RT) * sc);                                                \
+        }                                                                                                                    \
+        _Pragma("unroll")                                                                                                    \
+        for (int r2 = 0; r2 < MR; r2++) {                                                                                    \
+            const int i = lane + 64 * r2;                                                                                    \
+            if (yg && okr[r2]) yg[lp * m + i] = w.ys_()[i] * (RT) * sc;                                                      \
+        }                                                                                                                    \
+        if (lane == 0) {                                                                                                     \
+            if (pobj) pobj[lp] = po * (RT) * (sb * sc);                                                                      \
+            if (dobj) dobj[lp] = du * (RT) * (sb * sc);                                                                      \
+            status[lp] = stat;                                                                                               \
+            if (iters) iters[lp] = it;                                                                                       \
+        }                                                                                                                    \
+    }
+// The tail of the step: y, x, z, t, s advanced by theta.  (dx, dz are 0 where the column takes no part, dt, ds where it has no
+// bound: those values stay.)  Names of the scope: NQ, MR, MP, lane, w, TS, theta, dy, dx, dz, dt, ds.
+#define WREG_BOUNDED_ADVANCE()                                                                                               \
+    {                                                                                                                        \
+        _Pragma("unroll")                                                                                                    \
+        for (int r2 = 0; r2 < MR; r2++) {                                                                                    \
+            const int i = lane + 64 * r2;                                                                                    \
+            if (i < MP) w.ys_()[i] = fma(theta, dy[r2], w.ys_()[i]);                                                         \
+        }                                                                                                                    \
+        _Pragma("unroll")                                                                                                    \
+        for (int qq = 0; qq < NQ; qq++) {                                                                                    \
+            w.px(qq) = fma(theta, dx[qq], w.px(qq));                                                                         \
+            w.pz(qq) = fma(theta, dz[qq], w.pz(qq));                                                                         \
+            w.pt(TS, qq) = fma(theta, dt[qq], w.pt(TS, qq));                                                                 \
+            w.ps(TS, qq) = fma(theta, ds[qq], w.ps(TS, qq));                                                                 \
+        }                                                                                                                    \
+    }
+
+// ---- phases of the kernels on the homogeneous self-dual embedding (ipm_wreg_hsd.inc, ipm_wreg_bdhsd.inc), written once ---------
+// The verdict and the phase behind dtau are text in the kernel's own scope: eta = 1 - delta and 100 eps are an expression of the
+// kernel's, evaluated where it stands (ipm_wreg_bounded_hsd_kernel forms them from the SGPR at every use, hsd_wreg_kernel keeps
+// them in variables).
+//
+// The stop verdict (oracle hsd_one_raw) on the norms, objectives, tau and kappa of the point: NUMERICAL on a non-finite one,
+// OPTIMAL, or a primal / dual ray; where both rays pass, the larger objective decides.  WREG_HSD_RAYS declares the two ray
+// tests; WREG_HSD_VERDICT is ONE if-statement that sets stat and clears running, so a kernel's own tests go in front of it with
+// `else`.  Names of the scope: po, du, nbn, ncn, normr, norms, gam, tau, kap, stat, running, o.  TOLR, TOLS: eps (1 + |b|), eps (1 + |c|).
+#define WREG_HSD_RAYS(EINF)                                                                                                  \
+    const bool p_ray = po > 0.0 && fma(nbn, tau, normr) <= (EINF) * po;                                                      \
+    const bool d_ray = du < 0.0 && fma(ncn, tau, norms) <= (EINF) * -du;
+#define WREG_HSD_VERDICT(TOLR, TOLS)                                                                                         \
+    if (!(isfinite(normr) && isfinite(norms) && isfinite(gam) && isfinite(tau) && isfinite(kap))) { stat = PYCLLP_STATUS_NUMERICAL; running = false; } \
+    else if (normr <= (TOLR) * tau && norms <= (TOLS) * tau && gam <= o.eps * tau * (tau + fabs(po))) { stat = PYCLLP_STATUS_OPTIMAL; running = false; } \
+    else if (p_ray || d_ray) {                                                                                               \
+        stat = (p_ray && d_ray) ? ((-du > po) ? PYCLLP_STATUS_PRIMAL_INFEASIBLE : PYCLLP_STATUS_DUAL_INFEASIBLE)             \
+                                : (p_ray ? PYCLLP_STATUS_DUAL_INFEASIBLE : PYCLLP_STATUS_PRIMAL_INFEASIBLE);                 \
+        running = false;                                                                                                     \
+    }
+// Behind dtau: dy = p dtau + q, the right-hand side of the refinement (A dx - b dtau = eta rho) and the non-finite flag.  Names of
+// the scope: MR, MP, lane, w, pv, okr, rho, dtau, dy, rhot, bad.
+#define WREG_HSD_DY(ETA)                                                                                                     \
+    _Pragma("unroll")                                                                                                        \
+    for (int r2 = 0; r2 < MR; r2++) {                                                                                        \
+        const int i = lane + 64 * r2;                                                                                        \
+        dy[r2] = (i < MP) ? fma(pv[i], dtau, w.um_()[i]) : 0.0;                                                              \
+        rhot[r2] = okr[r2] ? fma(w.bs_()[i], dtau, (ETA) * rho[r2]) : 0.0;                                                   \
+        bad = bad | !isfinite(dy[r2]);                                                                                       \
+    }
+
+// Pass 0's hand-over: p moves from um_() to flr_() (the floor vector is dead once the factor exists), q's right-hand side into um_()
+template <int MB, int NQ, bool DA, bool PA>
+__device__ __forceinline__ void hsd_hand_over_p(const WReg<MB, NQ, DA, PA>& w, const double (&rq)[WGeo<MB>::MR]) {
+    constexpr int MR = WGeo<MB>::MR, MP = WGeo<MB>::MP;
+#pragma unroll
+    for (int r2 = 0; r2 < MR; r2++) {
+        const int i = w.lane + 64 * r2;
+        if (i < MP) { w.flr_()[i] = w.um_()[i]; w.um_()[i] = rq[r2]; }
+    }
+    wave_lds_sync();
+}
+
+// The tail of a pass behind pass 0: e = rhot - A dx over the columns that take part (ON, an expression in qq), and whether a
+// refinement pass follows: max|e| above etol_it and passes left; um_() is then e, its right-hand side.  Text in the kernel's scope
+// for the reason given at WREG_BOUNDED_STORE.  Names of the scope: NQ, MR, MP, lane, w, vx, okr, dx, rhot, etol_it, pass, o, more.
+#define WREG_HSD_REFINE_TAIL(ON)                                                                                             \
+    {                                                                                                                        \
+        wave_lds_sync();                                                                                                     \
+        _Pragma("unroll")                                                                                                    \
+        for (int qq = 0; qq < NQ; qq++) vx[lane + 64 * qq] = (ON) ? dx[qq] : 0.0;                                            \
+        wave_lds_sync();                                                                                                     \
+        double Adx[MR], e[MR], dm[MR], me = 0.0;                                                                             \
+        w.template Arow<false>(vx, Adx, dm);                                                                                 \
+        _Pragma("unroll")                                                                                                    \
+        for (int r2 = 0; r2 < MR; r2++) {                                                                                    \
+            e[r2] = okr[r2] ? rhot[r2] - Adx[r2] : 0.0;                                                                      \
+            me = fmax(me, fabs(e[r2]));                                                                                      \
+        }                                                                                                                    \
+        const double maxe = wmax(me);                                                                                        \
+        STAMP(8)                                                                                                             \
+        if (!(maxe > etol_it) || pass - 1 >= o.max_refine) more = false;                                                     \
+        else {                                                                                                               \
+            _Pragma("unroll")                                                                                                \
+            for (int r2 = 0; r2 < MR; r2++) if (lane + 64 * r2 < MP) w.um_()[lane + 64 * r2] = e[r2];                        \
+            wave_lds_sync();                                                                                                 \
+        }                                                                                                                    \
+    }
+
+// tau and kappa in the step: dkappa = dmu / tau - kappa - (kappa / tau) dtau, and the start of the ratio test from the two.  (Their
+// update, tau = uni(fma(theta, dtau, tau)) and the same for kappa, is a line of each kernel: a function over the two references
+// changed hsd_wreg_kernel's machine code.)
+__device__ __forceinline__ double hsd_dkappa(double dmu, double tau, double kap, double dtau) { return dmu / tau - kap - kap / tau * dtau; }
+__device__ __forceinline__ double hsd_ratio0(double tau, double kap, double dtau, double dkap) {
+    return fmax(fmax(-dtau / tau, -dkap / kap), 0.0);
 }
 
 // One launcher for every kernel of the family: the kernel's arguments, then the grid and the stream (wsolve_fn, wnewton_fn,
